@@ -3,6 +3,7 @@
 achieved HBM GB/s vs peak").
 
     python bench.py --gpus 1 --steps 20 --warmup 3          # 20 steps x 96 reference views
+    python bench.py --gpus 1 --steps 20 --warmup 3 --dump-outputs DIR   # + the last timed step's outputs as DIR/<name>.npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port P bench.py --gpus 8 ...
 
 One "step" = one batch of `--views-per-step` (default 96) reference views, each pushed through the whole 4-stage cascade with
@@ -164,6 +165,69 @@ def cpu_baseline(head, feats, projs, dv, max_threads=None, shipped=False):
     return res, out
 
 
+DUMP_BUDGET_BYTES = 60 * 10 ** 6          # data bytes; with the .npy headers and the manifest the directory stays below 64 MB
+DUMP_SAMPLE_SEED = 0
+
+
+def dump_outputs(dirname, outputs):
+    """Write the tensors of a nested output dict as <dirname>/<dotted name>.npy: floating tensors as float32, integer / bool ones as float64.
+    A tensor met again under another name (the cascade repeats its last stage's outputs at the top level) is written once; the manifest
+    names it under both.  If all of them together exceed DUMP_BUDGET_BYTES, the budget is shared out smallest tensor first (a tensor
+    within an equal share of what is left is kept whole) and a larger tensor is replaced by its share of elements (flattened), at
+    indices drawn without replacement by a generator seeded with DUMP_SAMPLE_SEED and sorted - the same indices for the same shape in
+    every run.  manifest.json records each file's source shape and dtype and whether it is a sample."""
+    import numpy as np
+    flat, seen, aliases = [], {}, {}
+
+    def walk(prefix, v):
+        if torch.is_tensor(v):
+            key = (v.data_ptr(), v.dtype, tuple(v.shape), v.stride())
+            if key in seen:
+                aliases[prefix] = seen[key]
+            else:
+                seen[key] = prefix
+                flat.append((prefix, v.detach()))
+        elif isinstance(v, dict):
+            for k in sorted(v, key=lambda k: (k not in ("refined_depth", "photometric_confidence"), str(k))):   # the path's results first
+                walk(prefix + "." + str(k), v[k])
+        elif isinstance(v, (list, tuple)):
+            for i, x in enumerate(v):
+                walk(prefix + "." + str(i), x)
+    for k in sorted(outputs):
+        walk(k, outputs[k])
+    arrays = []
+    for name, t in flat:
+        t = t.cpu()
+        arrays.append((name, t.float() if t.is_floating_point() else t.double(), t))
+    total = sum(x.numel() * x.element_size() for _, x, _ in arrays)
+    keep, left = {}, DUMP_BUDGET_BYTES
+    for i, (name, x, _) in enumerate(sorted(arrays, key=lambda e: (e[1].numel() * e[1].element_size(), e[0]))):
+        n = min(x.numel(), left // (len(arrays) - i) // x.element_size()) if total > DUMP_BUDGET_BYTES else x.numel()
+        keep[name] = n
+        left -= n * x.element_size()
+    os.makedirs(dirname, exist_ok=True)
+    manifest, written = {}, 0
+    for name, x, src in arrays:
+        entry = {"shape": list(src.shape), "dtype": str(src.dtype).replace("torch.", ""), "sampled": False}
+        x = x.reshape(-1)
+        n = keep[name]
+        if n < x.numel():
+            idx = torch.randperm(x.numel(), generator=torch.Generator().manual_seed(DUMP_SAMPLE_SEED))[:n].sort().values
+            x = x[idx]
+            entry.update(sampled=True, sample_size=n, sample_seed=DUMP_SAMPLE_SEED)
+        else:
+            x = x.reshape(src.shape)
+        np.save(os.path.join(dirname, name + ".npy"), x.numpy())
+        written += x.numel() * x.element_size()
+        manifest[name] = entry
+    for name, first in aliases.items():
+        manifest[name] = {"same_as": first}
+    with open(os.path.join(dirname, "manifest.json"), "w") as f:
+        json.dump({"note": "outputs of the timed path's last step, per input set: the last forward call of the step on that set", "arrays": manifest},
+                  f, indent=1, sort_keys=True)
+    print("bench.py: wrote %d arrays (%.1f MB) to %s" % (len(arrays), written / 1e6, dirname), file=sys.stderr)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -223,7 +287,13 @@ def main():
                     help="A/B: pass 2 of every stage gathers again instead of streaming the fp16 correlations kept by pass 1 (StageNet.keep_correlations)")
     ap.add_argument("--cost-reg", choices=["normal", "shipped"], default="normal",
                     help="normal: all-'Normal' regularisers (Track R headline); shipped: stage-1 transformer + PE3D as in the shipped config")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last step - for every input set, the outputs of its last "
+                         "reference view of that step - as DIR/<name>.npy (float32 / float64, at most 64 MB in all: larger tensors as a fixed "
+                         "seeded sample, see DIR/manifest.json).  Inputs depend only on the arguments, so two builds compare output for output")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be >= 1")
     a.graph = a.graph or a.issue == "graph"
 
     rank = int(os.environ.get("RANK", "0"))
@@ -335,12 +405,14 @@ def main():
                     graphs, issue = {}, "eager launches (hipGraph capture failed: %r)" % (e,)
                     torch.cuda.synchronize()
 
-            def run(n_steps, first=0):
-                """n_steps steps; step k = the R reference views k*R .. k*R+R-1, view j on input set j % nsets and stream j % nstreams."""
+            def run(n_steps, first=0, last_step_outputs=None):
+                """n_steps steps; step k = the R reference views k*R .. k*R+R-1, view j on input set j % nsets and stream j % nstreams.
+                last_step_outputs: a dict that receives, per input set, the outputs of that set's last forward call in the last step."""
                 o = None
                 if streams is not None:
                     for st in streams:
                         st.wait_stream(torch.cuda.current_stream(device))
+                last_first = (first + n_steps - 1) * R // BATCH
                 for j in range(first * R // BATCH, (first + n_steps) * R // BATCH):       # one forward call = BATCH reference views
                     f, p, d = sets[j % nsets]
                     if streams is None:
@@ -348,6 +420,8 @@ def main():
                     else:
                         with torch.cuda.stream(streams[j % len(streams)]):
                             o = graphs[(j % len(streams), j % nsets)]() if graphs else hd(f, p, d, tmp=TMP)
+                    if last_step_outputs is not None and j >= last_first:
+                        last_step_outputs[j % nsets] = o      # a graph's outputs are fixed buffers: no later call of this step rewrites them
                 if streams is not None:
                     for st in streams:
                         torch.cuda.current_stream(device).wait_stream(st)
@@ -358,10 +432,14 @@ def main():
 
         run(a.warmup)
         sync_all()
+        last_outputs = {} if a.dump_outputs else None
         t0 = time.perf_counter()
-        run(a.steps, first=a.warmup)
+        run(a.steps, first=a.warmup, last_step_outputs=last_outputs)
         sync_all()
         elapsed = time.perf_counter() - t0
+        if a.dump_outputs and rank == 0:
+            dump_outputs(a.dump_outputs, {"set%d" % k: o for k, o in sorted(last_outputs.items())})
+        last_outputs = None
 
         # single-stream latency: one reference view at a time on the current stream, the reference's own loop shape (test.py:238-252)
         n_lat = 4 * nsets

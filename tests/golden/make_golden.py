@@ -636,6 +636,105 @@ def f20_feature_heads():
     npz("f20_feature_heads.npz", **arrs)
 
 
+def _record_network(model, imgs, projs, dv):
+    """Run the reference's whole network with every ``fusions[i].forward`` wrapped (its cascade loop calls ``.forward`` directly, so
+    hooks would not fire): -> (network outputs, per-stage [(inputs, outputs)])."""
+    rec = []
+    for fu in model.fusions:
+        def wrapped(features, proj, depth_samples, tmp=None, position3d=None, _f=fu.forward):
+            o = _f(features, proj, depth_samples, tmp=tmp, position3d=position3d)
+            rec.append(({"features": features, "proj": proj, "hyp": depth_samples, "tmp": tmp, "pos": position3d}, o))
+            return o
+        fu.forward = wrapped
+    out = model(imgs, projs, dv)
+    for fu in model.fusions:
+        del fu.forward
+    return out, rec
+
+
+def _dropin_model(args, bn_seed, weight_seed, H=32, W=64):
+    """The reference network at H x W (V = 3): default initialisation, randomised BatchNorm statistics, then seeded weights in every
+    fusion (stored as manifest + seed like every other fixture; backbone and FMT keep the reference's own initialisation)."""
+    from models.networks.DINOv2_mvsformer_model import DINOv2MVSNet
+    torch.manual_seed(0)
+    model = DINOv2MVSNet(args).eval()
+    synth.randomize_bn_(model, seed=bn_seed)
+    arrs = {}
+    for i, fu in enumerate(model.fusions):
+        arrs.update(seed_weights(fu, weight_seed + i, "s%d.w." % (i + 1)))
+    V = 3
+    imgs = torch.rand(1, V, 3, H, W, generator=torch.Generator().manual_seed(1))
+    cams = synth.make_cameras(V, H, W, baseline=30.0, rot_deg=1.0, seed=2)
+    projs = synth.stage_proj_matrices(cams, 4)
+    dv = torch.arange(425.0, 2.65 * 191.5 + 425.0, 2.65)[None]
+    return model, imgs, projs, dv, arrs
+
+
+def _dropin_arrays(model, out, rec):
+    """The inputs the reference's cascade loop handed every fusion, every fusion's depth / confidence and the network's final outputs."""
+    arrs = {}
+    for i, (fu, (inp, o)) in enumerate(zip(model.fusions, rec)):
+        s = "s%d." % (i + 1)
+        arrs[s + "args"] = np.array(json.dumps(fu.args))
+        arrs[s + "ndepth"] = np.int64(fu.ndepth)
+        arrs[s + "stage_idx"] = np.int64(fu.stage_idx)
+        arrs[s + "features"] = inp["features"]
+        arrs[s + "proj"] = inp["proj"]
+        arrs[s + "hyp"] = inp["hyp"]
+        arrs[s + "tmp"] = np.float64(inp["tmp"])
+        if inp["pos"] is not None:
+            arrs[s + "pos"] = inp["pos"]
+        arrs[s + "out_names"] = np.array(sorted(o.keys()))
+        arrs[s + "depth"] = o["depth"]
+        arrs[s + "conf"] = o["photometric_confidence"]
+    arrs["refined_depth"] = out["refined_depth"]
+    arrs["photometric_confidence"] = out["photometric_confidence"]
+    arrs["net_names"] = np.array(sorted(out.keys()))
+    return arrs
+
+
+DROPIN_GRAD_SAMPLE = 256
+
+
+def _grad_sample(prefix, g, seed):
+    """A gradient tensor as its absolute maximum + DROPIN_GRAD_SAMPLE of its elements at fixed (seeded, sorted) flat indices."""
+    flat = g.detach().reshape(-1)
+    n = flat.numel()
+    idx = torch.arange(n) if n <= DROPIN_GRAD_SAMPLE else \
+        torch.randperm(n, generator=torch.Generator().manual_seed(seed))[:DROPIN_GRAD_SAMPLE].sort().values
+    return {prefix + "absmax": np.float32(flat.abs().max()), prefix + "idx": idx.to(torch.int32), prefix + "val": flat[idx]}
+
+
+def f21_dropin_network():
+    """The reference's whole top-level network (DINOv2MVSNet) - backbone, FMT and cascade loop the reference's own code - recorded at its
+    ``fusions[i]`` boundary: what tests/test_dropin_reference.py checks ``patch_model`` against.  f21_dropin_network.npz: the shipped
+    config in eval mode, plus its stage-1 fusion in train mode on the recorded stage-1 call with the test's loss (gradients of the
+    parameters and of the input features, sampled); f21_dropin_network_base_ch4.npz: base_ch = 4 with all-"Normal" regularisers at 64x64."""
+    args = json.load(open(os.path.join(REF, "config", "mvsformer++.json")))["arch"]["args"]
+    model, imgs, projs, dv, arrs = _dropin_model(args, 3, 210)
+    with torch.no_grad():
+        out, rec = _record_network(model, imgs, projs, dv)
+    arrs.update(_dropin_arrays(model, out, rec))
+    inp = rec[0][0]
+    st = model.fusions[0].train()
+    feat = inp["features"].clone().requires_grad_(True)
+    pre = st(feat, inp["proj"], inp["hyp"], tmp=inp["tmp"], position3d=inp["pos"])["prob_volume_pre"]
+    R = torch.randn(pre.shape, generator=torch.Generator().manual_seed(9))
+    (torch.softmax(pre, 1) * R).sum().backward()
+    arrs["train.R"] = R
+    grads = [("features", feat.grad)] + [(k, p.grad) for k, p in st.named_parameters() if p.grad is not None]
+    for i, (k, g) in enumerate(grads):
+        arrs.update(_grad_sample("train.grad.%s." % k, g, 1000 + i))
+    npz("f21_dropin_network.npz", **arrs)
+    args4 = json.loads(json.dumps(args))
+    args4["base_ch"] = [4, 4, 4, 4]
+    args4["cost_reg_type"] = ["Normal"] * 4
+    model, imgs, projs, dv, arrs = _dropin_model(args4, 4, 220, 64, 64)      # CostRegNet(4, 4) needs stage 1 >= 8 x 8
+    with torch.no_grad():
+        out, rec = _record_network(model, imgs, projs, dv)
+    arrs.update(_dropin_arrays(model, out, rec))
+    npz("f21_dropin_network_base_ch4.npz", **arrs)
+
 if __name__ == "__main__":
     only = sys.argv[1:]
     if only:
@@ -662,4 +761,5 @@ if __name__ == "__main__":
     f18_costregnet2d()
     f19_position_encoding()
     f20_feature_heads()
+    f21_dropin_network()
     pin_weights()
