@@ -481,6 +481,21 @@ int mvs_fusion_filter_fwd(int dynamic, const float* ref_depth, const float* ref_
 int mvs_fusion_ave_fwd(const float* ref_depth, const float* reproj_xyd, const float* masks, float* out, int n, int v, int h,
                        int w, void* stream);
 
+/* ==== point cloud: the filtered views of a scene as one binary PLY body =====================
+ * The per-view body after the filter in test.py filter_depth (:414-442) / dynamic_filter_depth (:485-517): keep the pixels of
+ * the final mask in row-major order (points_np[i, k][mask_np[i, 0]], :419 / :491), take the reference image's colours
+ * (:421-424 / :493-497), concatenate the views (:429 / :504) and pack the PLY vertex array (the tuple loop of :431-441 / :506-516).
+ * One view per call: mask [h,w] u8 and points [3,h,w] fp32 as mvs_fusion_filter_fwd writes them, rgb [h,w,3] u8.  The kept
+ * pixels land as packed 15-byte little-endian records {float x, y, z; uchar red, green, blue} in `records` (4-byte aligned,
+ * capacity records) starting at record *counter; *counter advances by the view's count, which is also written to
+ * view_counts[view_slot] (view_counts nullable).  Three launches on `stream`, no host synchronisation, bit-reproducible.
+ * The caller keeps *counter + h*w <= capacity (records past the capacity are dropped, the counter still advances).
+ * workspace: mvs_pointcloud_workspace_bytes(h, w) bytes, stream-ordered scratch.                                          */
+size_t mvs_pointcloud_workspace_bytes(int h, int w);
+int mvs_pointcloud_append(const uint8_t* mask, const float* points, const uint8_t* rgb, int h, int w, void* workspace,
+                          size_t workspace_bytes, unsigned* counter, unsigned* view_counts, int view_slot, uint8_t* records,
+                          long long capacity, void* stream);
+
 /* ---- layout helpers for the nn.Module-level API (NCDHW <-> channel-last) -------------------------*/
 int mvs_ncdhw_to_cl(const float* x, float* y_cl, int B, int C, int D, int H, int W, void* stream);
 int mvs_cl_to_ncdhw(const float* x_cl, float* y, int B, int C, int D, int H, int W, void* stream);

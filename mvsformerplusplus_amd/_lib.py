@@ -108,6 +108,8 @@ SIGNATURES = {
     "mvs_fusion_prepare_cams": (_i, [_vp, _i, _vp, _vp]),
     "mvs_fusion_filter_fwd": (_i, [_i] + [_vp] * 8 + [_f] * 4 + [_vp] * 7 + [_i] * 4 + [_vp]),
     "mvs_fusion_ave_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "mvs_pointcloud_workspace_bytes": (_sz, [_i, _i]),
+    "mvs_pointcloud_append": (_i, [_vp, _vp, _vp, _i, _i, _vp, _sz, _vp, _vp, _i, _vp, C.c_longlong, _vp]),
     "mvs_ncdhw_to_cl": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "mvs_cl_to_ncdhw": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
 }

@@ -75,10 +75,14 @@ __device__ __forceinline__ float world2img(const CamPack& c, const float* world,
     return cam[2];
 }
 
-// bilinear taps of grid_sample(align_corners=True, zeros padding) at normalised coordinates (gx, gy)
+// bilinear taps of grid_sample(align_corners=True, zeros padding) at normalised coordinates (gx, gy).
+// A coordinate far outside the image (a point near a camera's plane - a zero depth - projects to |uv| ~ 1e14) is pulled in to
+// just outside it first: every tap stays out of range as before, while v_cvt_i32_f32 would saturate to INT_MAX and the
+// x0 + 1 tap would wrap past the bounds check (the compiler tests x0 > -2 and w > x0 + 1).  NaN passes unchanged.
+__device__ __forceinline__ float pull_in(float i, int n) { return i < -2.0f ? -2.0f : (i > (float)n + 1.0f ? (float)n + 1.0f : i); }
 struct Bilin { int x0, y0; float wx1, wy1; };
 __device__ __forceinline__ Bilin bilin(float gx, float gy, int w, int h) {
-    const float ix = ((gx + 1.0f) / 2.0f) * (float)(w - 1), iy = ((gy + 1.0f) / 2.0f) * (float)(h - 1);
+    const float ix = pull_in(((gx + 1.0f) / 2.0f) * (float)(w - 1), w), iy = pull_in(((gy + 1.0f) / 2.0f) * (float)(h - 1), h);
     const float fx = floorf(ix), fy = floorf(iy);
     Bilin b;
     b.x0 = (int)fx; b.y0 = (int)fy; b.wx1 = ix - fx; b.wy1 = iy - fy;

@@ -6,6 +6,11 @@ with the reference so that either side can be swapped on its own:
     confidence ``confidence/<view>.npy``     uint8 = floor(photometric_confidence * 255)          (test.py:281-286)
     camera     ``cams/<view>_cam.txt``       "extrinsic" 4x4, blank line, "intrinsic" 3x3, blank line, the 4 values of the
                                              intrinsic slot's last row (depth range)             (test.py:149-166, :102-112)
+    image      ``images/<view>.jpg``         RGB, decoded with PIL                               (test.py:116-121)
+    pairs      ``pair.txt`` / ``new_pair.txt``  view count, then per view its id and "n id score id score ..."
+                                             (test.py:136-146, test_tt.py:142-156)
+    point cloud ``<scan>.ply``               binary little-endian PLY, vertex {float x, y, z; uchar red, green, blue}
+                                             (test.py:431-442, written there with plyfile)
 
 Host-side numpy only; nothing here touches the GPU.
 """
@@ -13,7 +18,7 @@ from __future__ import annotations
 
 import re
 import sys
-from typing import Tuple
+from typing import List, Tuple
 
 import numpy as np
 
@@ -81,3 +86,112 @@ def read_camera_parameters(filename: str) -> Tuple[np.ndarray, np.ndarray]:
     extrinsics = np.array(" ".join(lines[1:5]).split(), dtype=np.float32).reshape(4, 4)
     intrinsics = np.array(" ".join(lines[7:10]).split(), dtype=np.float32).reshape(3, 3)
     return intrinsics, extrinsics
+
+
+def read_img(filename: str) -> np.ndarray:
+    """-> [H,W,3] uint8, the decoded RGB bytes.  The reference (test.py:116-121) scales them to float32 / 255 and its drivers
+    multiply the kept colours by 255 again before the uint8 cast (:421-424); that round trip is the identity on all 256 values,
+    so the bytes are kept as they are."""
+    from PIL import Image
+    with Image.open(filename) as img:
+        if img.mode != "RGB":
+            img = img.convert("RGB")
+        return np.array(img, dtype=np.uint8)
+
+
+def read_pair_file(filename: str, convention: str = "dtu", nviews: int = 10) -> List[Tuple[int, List[int]]]:
+    """-> [(ref_view, [src_view, ...]), ...] in file order.  Lines with no source view are dropped (test.py:144).
+    convention "dtu" (test.py:136-146): the sources as listed (the dataset later keeps the first 10, test.py:337).
+    convention "tt" (test_tt.py:142-156): a list shorter than `nviews` (--fusion_view) is padded with its first source up to
+    `nviews`, then `nviews - 1` sources are kept."""
+    if convention not in ("dtu", "tt"):
+        raise ValueError("read_pair_file: convention must be 'dtu' or 'tt', not %r" % (convention,))
+    data = []
+    with open(filename) as f:
+        num_viewpoint = int(f.readline())
+        for _ in range(num_viewpoint):
+            ref_view = int(f.readline().rstrip())
+            src_views = [int(x) for x in f.readline().rstrip().split()[1::2]]
+            if len(src_views) == 0:
+                continue
+            if convention == "tt":
+                if len(src_views) < nviews:
+                    src_views += [src_views[0]] * (nviews - len(src_views))
+                src_views = src_views[:nviews - 1]
+            data.append((ref_view, src_views))
+    return data
+
+
+# the vertex layout of the reference's PLY (test.py:431-439): plyfile describes a structured array with these fields
+PLY_VERTEX_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1")])
+_PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "<i2", "int16": "<i2", "ushort": "<u2",
+              "uint16": "<u2", "int": "<i4", "int32": "<i4", "uint": "<u4", "uint32": "<u4", "float": "<f4", "float32": "<f4",
+              "double": "<f8", "float64": "<f8"}
+
+
+def ply_header(n: int) -> bytes:
+    """The header plyfile writes for the reference's vertex array (PlyElement.describe(vertex_all, 'vertex'), test.py:440-441).
+    The type names `float` / `uchar` are plyfile's names for numpy 'f4' / 'u1' (its type table); they have not been compared
+    with a file plyfile itself wrote."""
+    lines = ["ply", "format binary_little_endian 1.0", "element vertex %d" % n] + \
+        ["property float %s" % c for c in "xyz"] + ["property uchar %s" % c for c in ("red", "green", "blue")] + ["end_header"]
+    return ("\n".join(lines) + "\n").encode("ascii")
+
+
+def write_ply_records(filename: str, records) -> None:
+    """records: the packed PLY body, 15 bytes per vertex in PLY_VERTEX_DTYPE layout (bytes-like or uint8 / structured array)."""
+    body = memoryview(np.ascontiguousarray(records)).cast("B")
+    if body.nbytes % PLY_VERTEX_DTYPE.itemsize:
+        raise ValueError("write_ply_records: %d bytes is not a whole number of %d-byte vertices" % (body.nbytes, PLY_VERTEX_DTYPE.itemsize))
+    with open(filename, "wb") as f:
+        f.write(ply_header(body.nbytes // PLY_VERTEX_DTYPE.itemsize))
+        f.write(body)
+
+
+def write_ply(filename: str, xyz: np.ndarray, rgb: np.ndarray) -> None:
+    """xyz [N,3] float32, rgb [N,3] uint8 -> binary little-endian PLY, the file test.py:431-442 writes with plyfile."""
+    xyz, rgb = np.asarray(xyz), np.asarray(rgb)
+    if xyz.ndim != 2 or xyz.shape[1] != 3 or rgb.shape != xyz.shape:
+        raise ValueError("write_ply: want xyz [N,3] and rgb [N,3], got %s and %s" % (xyz.shape, rgb.shape))
+    v = np.empty(xyz.shape[0], PLY_VERTEX_DTYPE)
+    for i, c in enumerate("xyz"):
+        v[c] = xyz[:, i]
+    for i, c in enumerate(("red", "green", "blue")):
+        v[c] = rgb[:, i]
+    write_ply_records(filename, v)
+
+
+def read_ply(filename: str) -> Tuple[np.ndarray, np.ndarray]:
+    """-> (xyz [N,3] float32, rgb [N,3] uint8) of a binary little-endian PLY whose only element is `vertex` with (at least)
+    x, y, z and red, green, blue properties of fixed size."""
+    with open(filename, "rb") as f:
+        if f.readline().rstrip(b"\r\n") != b"ply":
+            raise ValueError("%s: not a PLY file" % filename)
+        n, fields, elements = None, [], []
+        while True:
+            line = f.readline()
+            if not line:
+                raise ValueError("%s: PLY header without end_header" % filename)
+            tok = line.decode("ascii").split()
+            if not tok or tok[0] in ("comment", "obj_info"):
+                continue
+            if tok[0] == "end_header":
+                break
+            if tok[0] == "format":
+                if tok[1] != "binary_little_endian":
+                    raise ValueError("%s: PLY format %s is not supported (binary_little_endian only)" % (filename, tok[1]))
+            elif tok[0] == "element":
+                elements.append(tok[1])
+                if tok[1] == "vertex":
+                    n = int(tok[2])
+            elif tok[0] == "property":
+                if tok[1] == "list" or tok[1] not in _PLY_TYPES:
+                    raise ValueError("%s: PLY property %r is not supported" % (filename, " ".join(tok[1:])))
+                if elements[-1:] == ["vertex"]:
+                    fields.append((tok[2], _PLY_TYPES[tok[1]]))
+        if elements != ["vertex"] or n is None:
+            raise ValueError("%s: want exactly one PLY element, vertex (got %s)" % (filename, elements))
+        v = np.frombuffer(f.read(), dtype=np.dtype(fields), count=n)
+    xyz = np.stack([v[c] for c in "xyz"], -1).astype(np.float32)
+    rgb = np.stack([v[c] for c in ("red", "green", "blue")], -1).astype(np.uint8)
+    return xyz, rgb

@@ -847,6 +847,25 @@ def fusion_ave(ref_depth, reproj_xyd, masks):
     return out
 
 
+PLY_RECORD_BYTES = 15
+
+
+def pointcloud_append(mask, points, rgb, records, counter, view_counts=None, view_slot: int = 0):
+    """Append one view's kept pixels as packed PLY vertex records: mask [h,w] (bool / uint8), points [3,h,w] fp32, rgb [h,w,3]
+    uint8 -> records (uint8, capacity * 15 bytes) from record counter[0] (int32 [1], advanced); view_counts (int32) [view_slot] =
+    the view's count.  Stream-ordered, no synchronisation; the caller keeps counter + h*w <= capacity."""
+    h, w = mask.shape[-2:]
+    m = mask.reshape(h, w).contiguous()
+    if m.dtype == torch.bool:
+        m = m.view(torch.uint8)
+    pts, col = _f32c(points).reshape(3, h, w), rgb.reshape(h, w, 3).contiguous()
+    assert m.dtype == torch.uint8 and col.dtype == torch.uint8 and records.dtype == torch.uint8 and counter.dtype == torch.int32
+    nbytes = lib().mvs_pointcloud_workspace_bytes(h, w)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=m.device)
+    check(lib().mvs_pointcloud_append(ptr(m), ptr(pts), ptr(col), h, w, ptr(ws), nbytes, ptr(counter), ptr(view_counts), int(view_slot),
+                                      ptr(records), records.numel() // PLY_RECORD_BYTES, stream_of(m)), "mvs_pointcloud_append")
+
+
 # ---- a13-a16 ------------------------------------------------------------------------------------
 def depth_regression(p: torch.Tensor, depth_values: torch.Tensor) -> torch.Tensor:
     pp, dv = _f32c(p), _f32c(depth_values)

@@ -228,3 +228,33 @@ def seeded_state_dict(shapes: Dict[str, Tuple[int, ...]], seed: int) -> Dict[str
 
 def state_dict_manifest(sd) -> Dict[str, Tuple[int, ...]]:
     return {k: tuple(v.shape) for k, v in sd.items()}
+
+
+def make_fusion_scene(V: int, H: int, W: int, *, seed: int = 0, baseline: float = 30.0) -> Dict[str, torch.Tensor]:
+    """The outputs of an inference run over V views, for the depth-map filtering and point-cloud step: depth maps of one tilted
+    plane seen from V translated cameras (closed form) with ~0.5 mm noise, 5 % outliers and a hole strip; uint8 confidences as
+    test.py saves them (a low-confidence band included); smooth RGB images with a sparse checker.
+    -> depth [V,H,W] fp32, conf [V,H,W] uint8, cams [V,2,4,4], rgb [V,H,W,3] uint8 (CPU)."""
+    g = torch.Generator().manual_seed(seed)
+    cams = make_cameras(V, H, W, baseline=baseline, rot_deg=0.0, seed=seed)[0]
+    a, b, z0 = 0.15, -0.1, 600.0
+    ys, xs = torch.meshgrid(torch.arange(H, dtype=torch.float32) + 0.5, torch.arange(W, dtype=torch.float32) + 0.5, indexing="ij")
+    depths = []
+    for v in range(V):
+        K, E = cams[v, 1, :3, :3], cams[v, 0]
+        C = -E[:3, 3]
+        rx, ry = (xs - K[0, 2]) / K[0, 0], (ys - K[1, 2]) / K[1, 1]
+        depths.append((z0 + a * C[0] + b * C[1] - C[2]) / (1 - a * rx - b * ry))
+    d = torch.stack(depths)
+    d = d * (1 + 0.0008 * torch.randn(d.shape, generator=g))
+    d = torch.where(torch.rand(d.shape, generator=g) < 0.05, d * (1 + 0.05 * torch.randn(d.shape, generator=g)), d)
+    d[:, :, :max(1, W // 20)] = 0.0
+    conf = torch.rand(d.shape, generator=g) * 0.5 + 0.5
+    conf[:, H // 5:H // 3, :] *= 0.6
+    conf = (conf * 255).to(torch.uint8)
+    xr = (torch.arange(W)[None, :] * 4) % 256
+    yr = (torch.arange(H)[:, None] * 5) % 256
+    rgb = torch.stack([torch.stack([(xr + 20 * v).expand(H, W) % 256, (yr + 30 * v).expand(H, W) % 256,
+                                    torch.full((H, W), (40 * v) % 256)], -1) for v in range(V)]).to(torch.uint8)
+    rgb[:, ::7, ::5] = 255 - rgb[:, ::7, ::5]
+    return {"depth": d.contiguous(), "conf": conf.contiguous(), "cams": cams.contiguous(), "rgb": rgb.contiguous()}
