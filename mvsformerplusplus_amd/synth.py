@@ -258,3 +258,41 @@ def make_fusion_scene(V: int, H: int, W: int, *, seed: int = 0, baseline: float 
                                     torch.full((H, W), (40 * v) % 256)], -1) for v in range(V)]).to(torch.uint8)
     rgb[:, ::7, ::5] = 255 - rgb[:, ::7, ::5]
     return {"depth": d.contiguous(), "conf": conf.contiguous(), "cams": cams.contiguous(), "rgb": rgb.contiguous()}
+
+
+def make_box_scene(V: int, H: int, W: int, *, seed: int = 0, metres: bool = False, rot_deg: float = 3.0,
+                   conf_thresh: float = 0.5) -> Dict[str, torch.Tensor]:
+    """A harder scene for the depth-map filters than make_fusion_scene: a box in front of a slanted plane (occlusion edges,
+    so bilinear taps straddle depth discontinuities) seen by V rotated cameras (make_cameras with ``rot_deg``).  DTU scale
+    (mm, depths ~400..870, 30 mm baseline) or, with ``metres``, a Tanks-and-Temples-like one (m, depths ~2.5..9, 0.4 m
+    baseline).  Depths are ray-cast in fp64, then get ~0.08 % noise and 2 % outliers; zero-depth holes (a strip and 0.1 %
+    scattered pixels).  Float confidences in [0.55, 1) with a low-confidence band below 0.5, and 0.2 % exactly ``conf_thresh``.
+    -> depth [V,H,W] fp32, conf [V,H,W] fp32, cams [V,2,4,4] (CPU)."""
+    g = torch.Generator().manual_seed(seed)
+    s = 0.01 if metres else 1.0
+    cams = make_cameras(V, H, W, baseline=40.0 * s if metres else 30.0, rot_deg=rot_deg, seed=seed)[0]
+    z0, a, b = (700.0 if metres else 650.0) * s, 0.2, -0.12                        # plane z = z0 + a x + b y (world = camera 0)
+    lo = torch.tensor([-90.0, -60.0, 440.0 if not metres else 270.0], dtype=torch.float64) * s   # the box
+    hi = torch.tensor([60.0, 80.0, 520.0 if not metres else 350.0], dtype=torch.float64) * s
+    ys, xs = torch.meshgrid(torch.arange(H, dtype=torch.float64) + 0.5, torch.arange(W, dtype=torch.float64) + 0.5, indexing="ij")
+    pix = torch.stack([xs, ys, torch.ones_like(xs)], -1)                           # [H,W,3]
+    depths = []
+    for v in range(V):
+        E, K = cams[v, 0].double(), cams[v, 1, :3, :3].double()
+        R, t = E[:3, :3], E[:3, 3]
+        C = -R.t() @ t
+        d = pix @ torch.linalg.inv(K).t() @ R                                      # world ray per pixel, camera depth = ray parameter
+        sp = (-z0 - a * C[0] - b * C[1] + C[2]) / (a * d[..., 0] + b * d[..., 1] - d[..., 2])
+        t1, t2 = (lo - C) / d, (hi - C) / d
+        tmin, tmax = torch.minimum(t1, t2).amax(-1), torch.maximum(t1, t2).amin(-1)
+        hit = (tmax >= tmin) & (tmin > 0)
+        depths.append(torch.where(hit & (tmin < sp), tmin, sp))
+    d = torch.stack(depths).float()
+    d = d * (1 + 0.0008 * torch.randn(d.shape, generator=g))
+    d = torch.where(torch.rand(d.shape, generator=g) < 0.02, d * (1 + 0.05 * torch.randn(d.shape, generator=g)), d)
+    d[:, :, W - max(1, W // 50):] = 0.0
+    d[torch.rand(d.shape, generator=g) < 0.001] = 0.0
+    conf = torch.rand(d.shape, generator=g) * 0.45 + 0.55
+    conf[:, H // 4:H // 4 + max(1, H // 40), :] *= 0.5
+    conf[torch.rand(d.shape, generator=g) < 0.002] = conf_thresh
+    return {"depth": d.contiguous(), "conf": conf.contiguous(), "cams": cams.contiguous()}

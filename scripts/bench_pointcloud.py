@@ -116,7 +116,7 @@ def reference_style(root, method, V, nsrc, device="cpu"):
     from oracle import fusion_ref as R
     dev = torch.device(device)
     grids = R.get_pixel_grids
-    R.get_pixel_grids = lambda h, w: grids(h, w).to(dev)                 # the reference builds its pixel grid with .cuda() (fusion.py:8-13)
+    R.get_pixel_grids = lambda h, w, dtype=torch.float32: grids(h, w, dtype).to(dev)   # the reference builds its pixel grid with .cuda() (fusion.py:8-13)
     t0 = time.perf_counter()
     t_load = t_filter = 0.0
     views = {}

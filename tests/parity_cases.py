@@ -1634,6 +1634,386 @@ def case_fusion_golden(device):
         assert ((cpu(out["points"]) - fx["d_points"]).abs().amax(1, keepdim=True)[same]).max() <= 5e-3
 
 
+# ---- the filters against an fp64 restatement at scene sizes: exact on decided pixels, bounded elsewhere ----
+_EPS32 = 2.0 ** -23
+
+
+def _fp32_delta(q64, q32, scale, sens, mult=16.0, sens_mult=4.0, floor_ulps=8.0):
+    """How close to a threshold an fp64 quantity must sit before fp32 rounding may flip the comparison; the largest of
+    - `mult` = 16 times the fp32 restatement's error at that entry (run beside the fp64 one: the rounding of the whole chain of
+      projections, ~1 ulp of `scale` - pixel coordinates for a distance, depths for a depth difference - on smooth surfaces);
+    - `sens_mult` = 4 times `sens`, what the quantity moves when the bilinear sample position moves by one fp32 ulp
+      (oracle/fusion_ref.tap_sensitivity).  Next to a zero-depth tap (its reprojection lies far away) the weight of that tap is
+      set by the last bit of the sample coordinate: the kernel and the fp32 restatement may round it to different sides of an
+      integer, and the restatement's own error then says nothing.  Without this term 1-2 of ~18 M comparisons per MI355X case
+      flipped on "decided" pixels, each one a sample within 2e-5 px of an integer next to a hole (e.g. ix = 886.99998942 with
+      the tap at 888 a hole: 6.6 px of x from one ulp);
+    - a floor of `floor_ulps` = 8 fp32 ulps of `scale`.
+    Entries where exactly one of q32 / q64 is finite get an infinite delta."""
+    both = torch.isfinite(q64) & torch.isfinite(q32) & torch.isfinite(scale) & (scale > 0)
+    sc = scale.abs().where(both, torch.ones_like(scale))
+    rel = torch.where(both, (q32 - q64).abs() / sc, torch.zeros_like(q64))
+    d = torch.maximum(mult * rel, torch.full_like(rel, floor_ulps * _EPS32)) * scale.abs()
+    d = torch.maximum(d, sens_mult * sens.nan_to_num(nan=float("inf")))
+    return torch.where(torch.isfinite(q64) != torch.isfinite(q32), torch.full_like(d, float("inf")), d)
+
+
+def _decide(conds):
+    """conds: [(holds (fp64 bool), borderline (bool))] of one AND-ed decision -> (value, borderline): decided when one condition
+    is clearly false or all are clearly true."""
+    val = conds[0][0].clone()
+    for c, _ in conds[1:]:
+        val &= c
+    clear_false = torch.zeros_like(val)
+    clear_true = torch.ones_like(val)
+    for c, b in conds:
+        clear_false |= ~c & ~b
+        clear_true &= c & ~b
+    return val, ~(clear_false | clear_true)
+
+
+def fusion_vs_fp64(got, rd, rconf, sd, sconf, rc, sc, *, dynamic, conf_thresh, p0, p1, vthresh=0.0, bounds=None):
+    """The comparison rule every fp64 case of the depth-map filters uses, for ONE batch element (all CPU tensors).
+    got: the kernel's outputs (any of reproj_xyd [v,3,h,w], in_range [v,h,w], vis_masks [v,h,w] / [v,v-1,h,w], depth, geo_mask,
+    mask [h,w], points [3,h,w]); inputs rd/rconf [h,w], sd/sconf [v,h,w] (sconf None = no gating), rc [2,4,4], sc [v,2,4,4];
+    p0/p1 = thres_disp / depth_thresh (static) or dist_base / rel_diff_base (dynamic).
+
+    Every (pixel, view, threshold) comparison is made in fp64 (oracle/fusion_ref.view_quantities) and is *borderline* when its
+    fp64 margin is below _fp32_delta.  On the pixels without a borderline comparison ("decided") vis_masks, in_range, geo_mask,
+    mask - and so the views that entered the averaged depth - must equal fp64's exactly.  The borderline share is capped at
+    3 % static, 12 % dynamic (v - 1 thresholds per view): measured 1.8 % / 8.5 % at 1152x1600 with 10 sources on
+    make_box_scene, whose outliers and holes put large tap differences under many samples.  Continuous outputs on decided
+    pixels: depth relative to fp64 and points relative to |camera centre| + depth, each within `bounds` plus 16x the fp32
+    restatement's own error of the same value (its conditioning); reproj_xyd relative on the entries fp64 holds below 1e4
+    (not a hole projection), with no zero-depth tap within two pixels of the sample (fusion_ref.near_zero: the linearised
+    tap_sensitivity does not hold there) and whose conditioning (16x the fp32 restatement's error, at least 4x the
+    tap_sensitivity) is below the bound - they must be the majority.  Bounds, from the MI355X at 1152x1600 / 1056x1920 / 517x743 and n = 2, 10 sources
+    (largest figures on the well-conditioned pixels): depth 1.4e-5 (bound 4e-5), points 1.4e-5 (4e-5), reproj_xyd 2.5e-4 (4e-4).
+    Non-finite values: the fp64 depth / points are finite everywhere here and so must the kernel's be.
+    -> dict of measured figures (keys with a leading "_": the fp64 mask, decided pixels and points)."""
+    from oracle import fusion_ref as R
+    b = dict({"depth": 4e-5, "points": 4e-5, "xyd": 4e-4, "xyd_cmp": 0.5, "borderline": 0.12 if dynamic else 0.03}, **(bounds or {}))
+    v, h, w = sd.shape
+    f64 = torch.float64
+    rd64 = rd.double()
+    sum_d = torch.zeros(h, w, dtype=f64)
+    sum_d32 = torch.zeros(h, w, dtype=f64)
+    cond_mult = 16.0
+    cnt = torch.zeros(h, w, dtype=f64)
+    counts = torch.zeros(max(v - 1, 1), h, w, dtype=f64)
+    border = torch.zeros(h, w, dtype=torch.bool)
+    vis, inr = [], []
+    xyd_stats = {"xyd_rel": 0.0, "xyd_cmp": 0.0}
+    for j in range(v):
+        s = sd[j]
+        if not dynamic and sconf is not None:
+            s = s * (sconf[j] > conf_thresh).float()
+        q = {}
+        for dt in (torch.float32, f64):
+            q[dt] = R.view_quantities(rd.to(dt)[None, None], s.to(dt)[None, None, None], rc.to(dt)[None], sc[j].to(dt)[None, None],
+                                      dynamic=dynamic, depth_thresh=float(p1))
+        a, f = q[f64], q[torch.float32]
+        px_scale = torch.maximum(a["x"].abs(), a["y"].abs()).clamp_min(float(max(h, w)))
+        dd = _fp32_delta(a["dist"], f["dist"], px_scale, a["sx"] + a["sy"])
+        if dynamic:
+            dr = _fp32_delta(a["ddiff"], f["ddiff"], (rd64.abs() + a["z"].abs()) / rd64.abs(), a["sz"] / rd64.abs())
+            ms = []
+            for k in range(v - 1):
+                td, tr = (k + 2) / float(p0), (k + 2) / float(p1)
+                m, bl = _decide([(a["dist"] < td, (a["dist"] - td).abs() < dd), (a["ddiff"] < tr, (a["ddiff"] - tr).abs() < dr)])
+                counts[k] += m
+                border |= bl
+                ms.append(m)
+            sel = ms[-1]
+            vis.append(torch.stack(ms))
+        else:
+            dgx = _fp32_delta(a["gx"], f["gx"], torch.ones_like(a["gx"]), torch.zeros_like(a["gx"]))
+            dgy = _fp32_delta(a["gy"], f["gy"], torch.ones_like(a["gy"]), torch.zeros_like(a["gy"]))
+            dm = _fp32_delta(a["dmargin"], f["dmargin"], torch.maximum(rd64.abs(), a["z"].abs()), (1 + float(p1)) * a["sz"])
+            ir, bx = _decide([(a["gx"] >= -1, (a["gx"] + 1).abs() < dgx), (a["gx"] <= 1, (a["gx"] - 1).abs() < dgx),
+                              (a["gy"] >= -1, (a["gy"] + 1).abs() < dgy), (a["gy"] <= 1, (a["gy"] - 1).abs() < dgy)])
+            sel, bl = _decide([(ir, bx), (a["dist"] < float(p0), (a["dist"] - float(p0)).abs() < dd), (a["dmargin"] < 0, a["dmargin"].abs() < dm)])
+            border |= bl | bx
+            vis.append(sel)
+            inr.append(ir)
+        sum_d += torch.where(sel, a["z"], torch.zeros_like(a["z"]))
+        sum_d32 += torch.where(sel, f["z"].double(), torch.zeros_like(a["z"]))
+        cnt += sel
+        if "reproj_xyd" in got:
+            # every entry fp64 holds below 1e4 (not a hole projection) is compared; the bound adds the entry's own conditioning
+            ref = torch.stack([a["x"], a["y"], a["z"]])
+            cond = torch.maximum((torch.stack([f["x"], f["y"], f["z"]]).double() - ref).abs(),
+                                 0.25 * torch.stack([a["sx"], a["sy"], a["sz"]]).nan_to_num(nan=float("inf")))   # 16 x 0.25 = 4 x the sample sensitivity
+            scale = ref.abs().clamp_min(1.0)
+            ok = ref.abs() < 1e4
+            err = (got["reproj_xyd"][j].double() - ref).abs()
+            well = ok & ~a["hole"][None] & (cond_mult * cond <= b["xyd"] * scale)   # well-conditioned: no hole tap, not on an edge
+            xyd_stats["xyd_rel"] = max(xyd_stats["xyd_rel"], float((err / scale)[well].max()) if well.any() else 0.0)
+            xyd_stats["xyd_cmp"] += float(well.double().mean()) / v
+    ave = (sum_d + rd64) / (cnt + 1)
+    ave_cond = ((sum_d32 + rd64) / (cnt + 1) - ave).abs()          # the fp32 restatement's error of the same average, same views
+    if dynamic:
+        geo = cnt >= v + 1
+        for k in range(v - 1):
+            geo |= counts[k] >= k + 2
+    else:
+        geo = cnt >= (vthresh - 1.1)
+    prob = rconf > conf_thresh
+    mask = geo & prob
+    dec = ~border
+    share = float(border.double().mean())
+    stats = dict(xyd_stats, borderline=share)
+    assert share <= b["borderline"], ("borderline share", share)
+    if "vis_masks" in got:
+        want = torch.stack(vis)
+        gv = got["vis_masks"].bool().reshape(want.shape)
+        bad = (gv != want) & dec.expand_as(want)
+        assert not bad.any(), ("vis_masks differ on decided pixels", int(bad.sum()), bad.nonzero()[:5].tolist())
+    if "in_range" in got and not dynamic:
+        want = torch.stack(inr)
+        bad = (got["in_range"].reshape(want.shape) > 0) != want
+        assert not (bad & dec).any(), ("in_range differs on decided pixels", int((bad & dec).sum()))
+    for k, want in (("geo_mask", geo), ("mask", mask)):
+        if k in got:
+            bad = (got[k].reshape(h, w).bool() != want) & dec
+            assert not bad.any(), ("%s differs on decided pixels" % k, int(bad.sum()), bad.nonzero()[:5].tolist())
+    if "depth" in got:
+        gd = got["depth"].reshape(h, w).double()
+        assert torch.isfinite(ave).all() and torch.isfinite(gd).all()
+        err, sc_ = (gd - ave).abs(), ave.abs().clamp_min(1e-6)
+        assert not ((err > b["depth"] * sc_ + cond_mult * ave_cond) & dec).any(), ("depth", float((err / sc_)[dec].max()))
+        well = dec & (cond_mult * ave_cond <= b["depth"] * sc_)
+        stats["depth_rel"] = float((err / sc_)[well].max())
+        stats["depth_rel_all"] = float((err / sc_)[dec].max())
+    if "points" in got:
+        p64 = R.backproject(ave[None, None], rc.double()[None])[0]
+        E = rc[0].double()
+        centre = (-E[:3, :3].t() @ E[:3, 3]).norm()
+        gp = got["points"].reshape(3, h, w).double()
+        assert torch.isfinite(gp).all()
+        err, sc_ = (gp - p64).abs().amax(0), (centre + ave.abs()).clamp_min(1e-6)
+        ray = (p64 - (-E[:3, :3].t() @ E[:3, 3])[:, None, None]).norm(dim=0) / ave.abs().clamp_min(1e-6)
+        assert not ((err > b["points"] * sc_ + cond_mult * ray * ave_cond) & dec).any(), ("points", float((err / sc_)[dec].max()))
+        well = dec & (cond_mult * ray * ave_cond <= b["points"] * sc_)
+        stats["points_rel"] = float((err / sc_)[well].max())
+        stats["_points64"] = p64
+    if "reproj_xyd" in got:
+        assert xyd_stats["xyd_cmp"] > b["xyd_cmp"], xyd_stats
+        assert xyd_stats["xyd_rel"] <= b["xyd"], ("reproj_xyd", xyd_stats)
+    stats["kept"] = float(mask.double().mean())
+    stats["_mask64"], stats["_decided"] = mask, dec
+    return stats
+
+
+def _box_inputs(H, W, v, seed=0, metres=False, rot_deg=3.0):
+    """Reference view 0 of a make_box_scene with views 1..v as its sources -> (rd, rconf [h,w], sd, sconf [v,h,w], rc, sc) CPU."""
+    s = synth.make_box_scene(v + 1, H, W, seed=seed, metres=metres, rot_deg=rot_deg)
+    d, c, cams = s["depth"], s["conf"], s["cams"]
+    return d[0], c[0], d[1:], c[1:], cams[0], cams[1:]
+
+
+def _fused(device, dynamic, inp, *, conf_thresh=0.5, p0, p1, vthresh=0.0, gate=True):
+    """One launch of the fused filter with every output requested, for n = 1 -> CPU dict shaped as fusion_vs_fp64 takes it."""
+    rd, rconf, sd, sconf, rc, sc = (dev(t, device) for t in inp)
+    v, h, w = sd.shape
+    out = ops.fusion_filter(dynamic, rd[None], sd[None], rc[None], sc[None], ref_conf=rconf[None],
+                            srcs_conf=sconf[None] if (gate and not dynamic) else None, conf_thresh=conf_thresh, p0=p0, p1=p1,
+                            vthresh=vthresh, want_xyd=True, want_masks=True)
+    return {k: cpu(t)[0] for k, t in out.items()}
+
+
+def case_fusion_scene_fp64(device, H, W, v, dynamic, *, seed=0, metres=False, rot_deg=3.0, thres_disp=1.0, thres_view=2,
+                           dist_base=4.0, rel_diff_base=1300.0, bounds=None):
+    """The fused filter (every output) on a box-and-plane scene against the fp64 restatement under fusion_vs_fp64's rule."""
+    inp = _box_inputs(H, W, v, seed=seed, metres=metres, rot_deg=rot_deg)
+    p0, p1 = (dist_base, rel_diff_base) if dynamic else (thres_disp, 0.01)
+    with torch.no_grad():
+        got = _fused(device, dynamic, inp, p0=p0, p1=p1, vthresh=thres_view)
+    rd, rconf, sd, sconf, rc, sc = inp
+    st = fusion_vs_fp64(got, rd, rconf, sd, None if dynamic else sconf, rc, sc, dynamic=dynamic, conf_thresh=0.5, p0=p0, p1=p1,
+                        vthresh=thres_view, bounds=bounds)
+    if not dynamic and thres_view <= 1:
+        assert got["geo_mask"].bool().all()                       # sum >= -0.1: every pixel, zero-depth holes included (fusion.py:108)
+    if not dynamic and thres_view >= v + 2:
+        assert not got["geo_mask"].bool().any()
+    if not dynamic:                                               # conf == conf_thresh is rejected: the test is strict (test.py:389-392)
+        at = rconf == 0.5
+        assert at.any() and not got["mask"].bool()[at].any()
+    return st
+
+
+def case_fusion_batch(device, H, W, v, bounds=None):
+    """n = 2 with different cameras and depths per element through every entry point of fusion.py: each element equals the
+    kernel's own n = 1 run of it bit for bit, and the fp64 restatement of it (run per element at n = 1: the reference's dynamic
+    driver only broadcasts correctly for n = 1, scripts/fuzz_fusion_gpu.py) under fusion_vs_fp64's rule."""
+    from mvsformerplusplus_amd import fusion as Fu
+    from oracle import fusion_ref as R
+    els = [_box_inputs(H, W, v, seed=11, rot_deg=3.0), _box_inputs(H, W, v, seed=12, metres=True, rot_deg=4.0)]
+    stack = lambda i: torch.stack([e[i] for e in els])
+    rd, rconf, sd, sconf, rc, sc = (dev(stack(i), device) for i in range(6))
+    sdg = sd * (sconf > 0.5).float()
+    kw = dict(conf_thresh=0.5, thres_disp=1.0, thres_view=2)
+
+    def run(sl):
+        r = {}
+        x, ir = Fu.get_reproj(rd[sl][:, None], sdg[sl][:, :, None], rc[sl], sc[sl])
+        r["s_xyd"], r["s_inr"] = x, ir
+        r["s_vis"], r["s_geo"] = Fu.vis_filter(rd[sl][:, None], x, ir, 1.0, 0.01, 2)
+        r["s_ave"] = Fu.ave_fusion(rd[sl][:, None], x, r["s_vis"])
+        for k, t in Fu.filter_depth(rd[sl][:, None], rconf[sl], sd[sl][:, :, None], sconf[sl], rc[sl], sc[sl], **kw).items():
+            r["s_" + k] = t
+        x = Fu.get_reproj_dynamic(rd[sl][:, None], sd[sl][:, :, None], rc[sl], sc[sl])
+        r["d_xyd"] = x
+        r["d_vis"], r["d_last"] = Fu.vis_filter_dynamic(rd[sl][:, None], x, 4, 1300)
+        for k, t in Fu.dynamic_filter_depth(rd[sl][:, None], rconf[sl], sd[sl][:, :, None], rc[sl], sc[sl], conf_thresh=0.5).items():
+            r["d_" + k] = t
+        return {k: cpu(t) for k, t in r.items()}
+
+    with torch.no_grad():
+        both = run(slice(0, 2))
+        stats = []
+        for b in range(2):
+            one = run(slice(b, b + 1))
+            for k in both:
+                assert torch.equal(both[k][b:b + 1], one[k]), ("element %d of the n = 2 run differs from its n = 1 run" % b, k)
+            g = lambda k: one[k][0]
+            e = [t[b].cpu() for t in (rd, rconf, sd, sconf, rc, sc)]
+            stats.append(fusion_vs_fp64({"reproj_xyd": g("s_xyd"), "in_range": g("s_inr"), "vis_masks": g("s_vis"), "geo_mask": g("s_geo"),
+                                         "depth": g("s_depth"), "mask": g("s_mask"), "points": g("s_points")}, *e,
+                                        dynamic=False, conf_thresh=0.5, p0=1.0, p1=0.01, vthresh=2, bounds=bounds))
+            # ave_fusion over vis_filter's masks: z * mask summed in view order, so the fused filter's average bit for bit (every z is
+            # finite here), and the restatement's within its summation order
+            assert torch.equal(g("s_ave"), g("s_depth"))
+            ave_ref = R.ave_fusion(e[0][None, None], g("s_xyd")[None], g("s_vis")[None])[0]
+            assert ((g("s_ave") - ave_ref).abs() <= 2e-6 * ave_ref.abs().clamp_min(1.0)).all()
+            stats.append(fusion_vs_fp64({"reproj_xyd": g("d_xyd"), "vis_masks": g("d_vis"), "geo_mask": g("d_geo_mask"), "depth": g("d_depth"),
+                                         "mask": g("d_mask"), "points": g("d_points")}, *e[:3], None, *e[4:],
+                                        dynamic=True, conf_thresh=0.5, p0=4.0, p1=1300.0, bounds=bounds))
+            assert torch.equal(g("d_last"), g("d_vis")[:, -1:])
+    return stats
+
+
+def case_fusion_view_limits(device):
+    """v = 16 is the kernel's limit (kMaxSrcViews): v = 17 is refused by both filters, v = 1 by the dynamic one."""
+    for v, dyn, ok in ((16, False, True), (16, True, True), (17, False, False), (17, True, False), (1, True, False), (1, False, True)):
+        rd = torch.full((1, 4, 6), 500.0, device=device)
+        sd = torch.full((1, v, 4, 6), 500.0, device=device)
+        cams = synth.make_cameras(v + 1, 4, 6)[0].to(device)
+        try:
+            ops.fusion_filter(dyn, rd, sd, cams[:1], cams[None, 1:])
+            raised = None
+        except _lib.MvsHipError as e:
+            raised = str(e)
+        assert (raised is None) == ok, (v, dyn, raised)
+
+
+def _on_threshold_static(h, w, v, thres_disp, g):
+    """reproj_xyd [1,v,3,h,w] whose distances and depth differences sit exactly on, one ulp inside and one ulp outside the
+    static thresholds in fp32, plus in_range from {0, 1}; ref depth [1,1,h,w]."""
+    f = torch.float32
+    px = (torch.arange(w, dtype=f) + 0.5).expand(h, w)
+    py = (torch.arange(h, dtype=f) + 0.5)[:, None].expand(h, w)
+    rd = (torch.rand(h, w, generator=g) * 500 + 400).to(f)
+    xs, ys, zs, inr = [], [], [], []
+    p1 = torch.tensor(0.01, dtype=f)
+    for _ in range(v):
+        along_x = torch.rand(h, w, generator=g) < 0.5
+        sign = torch.where(torch.rand(h, w, generator=g) < 0.5, -1.0, 1.0).to(f)
+        centre = torch.where(along_x, px, py)
+        on = centre + sign * thres_disp                                # exact: pixel centres and thresholds are multiples of 1/4
+        kind = torch.randint(0, 5, (h, w), generator=g)                # centre, on, one ulp inside, one ulp outside, twice as far
+        c = torch.where(kind == 0, centre, on)
+        c = torch.where(kind == 2, torch.nextafter(on, centre), c)
+        c = torch.where(kind == 3, torch.nextafter(on, on + sign), c)
+        c = torch.where(kind == 4, centre + sign * 2 * thres_disp, c)
+        xs.append(torch.where(along_x, c, px))
+        ys.append(torch.where(along_x, py, c))
+        # depth: |rd - z| == fl(max(rd, z) * 0.01) where a z below rd makes that hold in fp32, else one ulp off it either way
+        z = rd - rd * p1
+        z = torch.where((rd - z).abs() == torch.maximum(rd, z) * p1, z, rd * (1 - p1))
+        pick = torch.randint(0, 4, (h, w), generator=g)
+        z = torch.where(pick == 1, torch.nextafter(z, rd), torch.where(pick == 2, torch.nextafter(z, torch.zeros_like(z)), z))
+        z = torch.where(pick == 3, rd * 1.003, z)
+        zs.append(z)
+        inr.append((torch.rand(h, w, generator=g) < 0.9).to(f))
+    xyd = torch.stack([torch.stack(xs), torch.stack(ys), torch.stack(zs)], 1)[None]
+    return rd[None, None], xyd, torch.stack(inr)[None, :, None]
+
+
+def _on_threshold_dynamic(h, w, v, dist_base, rel_diff_base, g):
+    """reproj_xyd [1,v,3,h,w] whose distances / relative depth differences are the ladder values i / base (exact in fp32 for
+    the power-of-two bases used) and their fp32 neighbours, drawn per pixel and view so the threshold counts vary."""
+    f = torch.float32
+    px = (torch.arange(w, dtype=f) + 0.5).expand(h, w)
+    py = (torch.arange(h, dtype=f) + 0.5)[:, None].expand(h, w)
+    rd = torch.full((h, w), float(rel_diff_base), dtype=f)
+    lad = torch.arange(1, v + 2, dtype=f)
+    xs, ys, zs = [], [], []
+    for _ in range(v):
+        i = lad[torch.randint(0, v + 1, (h, w), generator=g)]
+        on = px + i / dist_base                                        # exact: the bases used are powers of two
+        nudge = torch.randint(0, 3, (h, w), generator=g)               # on the ladder value, one ulp inside, one ulp outside
+        xs.append(torch.where(nudge == 1, torch.nextafter(on, px), torch.where(nudge == 2, torch.nextafter(on, on + 1), on)))
+        ys.append(py.clone())
+        k = lad[torch.randint(0, v + 1, (h, w), generator=g)]
+        z = rd - k                                                     # |rd - z| / rd == k / rel_diff_base exactly
+        nudge = torch.randint(0, 3, (h, w), generator=g)
+        z = torch.where(nudge == 1, torch.nextafter(z, rd), torch.where(nudge == 2, torch.nextafter(z, torch.zeros_like(z)), z))
+        zs.append(z)
+    xyd = torch.stack([torch.stack(xs), torch.stack(ys), torch.stack(zs)], 1)[None]
+    return rd[None, None], xyd
+
+
+def case_fusion_thresholds_exact(device, h=9, w=37):
+    """The stand-alone entry points fed a constructed reproj_xyd whose values sit exactly on the thresholds (and one fp32 ulp to
+    either side): from the same fp32 input the decisions must equal the fp32 restatement's bit for bit.  Pins `<` against `<=`,
+    the `vthresh - 1.1` offset (thres_view = 3.05: sum >= 1.95; a `- 1.0` would need 3), the dynamic ladder's i = k + 2 and
+    the geo ladder.  Also ave_fusion on the same input, and its non-finite behaviour: it multiplies z * mask like the reference
+    (an infinite z behind a zero mask gives NaN), whereas the fused filter adds only the selected views (finite)."""
+    from mvsformerplusplus_amd import fusion as Fu
+    from oracle import fusion_ref as R
+    g = torch.Generator().manual_seed(5)
+    with torch.no_grad():
+        for v, thres_disp, thres_view in ((1, 1.0, 1), (2, 0.25, 2), (4, 4.0, 3.05), (10, 1.0, 3.05), (16, 0.25, 6)):
+            rd, xyd, inr = _on_threshold_static(h, w, v, thres_disp, g)
+            m_ref, geo_ref = R.vis_filter(rd, xyd, inr, thres_disp, 0.01, thres_view)
+            m, geo = Fu.vis_filter(dev(rd, device), dev(xyd, device), dev(inr, device), thres_disp, 0.01, thres_view)
+            assert torch.equal(cpu(m).bool(), m_ref.bool()) and torch.equal(cpu(geo).bool(), geo_ref.bool()), (v, thres_disp, thres_view)
+            assert 0 < float(m_ref.float().mean()) < 1
+            ave_ref = R.ave_fusion(rd, xyd, m_ref)
+            ave = cpu(Fu.ave_fusion(dev(rd, device), dev(xyd, device), dev(m_ref, device)))
+            assert ((ave - ave_ref).abs() <= 2e-6 * ave_ref.abs()).all()
+            out = ops.fusion_filter(False, dev(rd[:, 0], device), None, None, None, xyd_in=dev(xyd, device), in_range_in=dev(inr[:, :, 0], device),
+                                    p0=thres_disp, p1=0.01, vthresh=thres_view, want_masks=True, want_points=False)
+            assert ((cpu(out["depth"]) - ave_ref[:, 0]).abs() <= 2e-6 * ave_ref[:, 0].abs()).all()
+        for v, db, rdb in ((2, 4.0, 1024.0), (3, 4.0, 1024.0), (10, 2.0, 512.0), (16, 4.0, 1024.0)):
+            rd, xyd = _on_threshold_dynamic(h, w, v, db, rdb, g)
+            m_ref, last_ref = R.vis_filter_dynamic(rd, xyd, db, rdb)
+            m, last = Fu.vis_filter_dynamic(dev(rd, device), dev(xyd, device), db, rdb)
+            assert torch.equal(cpu(m), m_ref) and torch.equal(cpu(last), last_ref), (v, db, rdb)
+            assert 0.05 < float(m_ref.float().mean()) < 0.95
+            ave_ref, geo_ref = R.dynamic_fuse(rd, xyd, m_ref, last_ref)
+            out = ops.fusion_filter(True, dev(rd[:, 0], device), None, None, None, xyd_in=dev(xyd, device), p0=db, p1=rdb,
+                                    want_masks=True, want_points=False)
+            assert torch.equal(cpu(out["geo_mask"]).bool(), geo_ref[:, 0]), v
+            assert 0 < float(geo_ref.float().mean()) < 1
+            assert ((cpu(out["depth"]) - ave_ref[:, 0]).abs() <= 2e-6 * ave_ref[:, 0].abs()).all()
+        # non-finite z on a rejected view
+        rd, xyd, inr = _on_threshold_static(h, w, 3, 1.0, g)
+        xyd[:, 1, 2] = float("inf")
+        inr[:, 1] = 0.0
+        m_ref, _ = R.vis_filter(rd, xyd, inr, 1.0, 0.01, 2)
+        ave_ref = R.ave_fusion(rd, xyd, m_ref)
+        assert torch.isnan(ave_ref).all()
+        assert torch.isnan(cpu(Fu.ave_fusion(dev(rd, device), dev(xyd, device), dev(m_ref, device)))).all()
+        out = ops.fusion_filter(False, dev(rd[:, 0], device), None, None, None, xyd_in=dev(xyd, device), in_range_in=dev(inr[:, :, 0], device),
+                                p0=1.0, p1=0.01, vthresh=2, want_masks=True, want_points=False)
+        finite = xyd.clone()
+        finite[:, 1, 2] = 0.0
+        assert torch.equal(cpu(out["vis_masks"]).bool(), m_ref[:, :, 0].bool())
+        assert ((cpu(out["depth"]) - R.ave_fusion(rd, finite, m_ref)[:, 0]).abs() <= 2e-6 * rd[:, 0]).all()
+
+
 # ---------------------------------------------------------------- section 8f #2: backward of the aggregation, training path
 def case_aggregate_backward(device):
     """mvs_warp_corr_aggregate_bwd against torch autograd through the oracle's warp + correlation + aggregation, for C = G

@@ -231,3 +231,32 @@ def test_device_packing(emu):
 
 def test_train_fp32_configured_head(emu):
     P.case_train_fp32_configured_head(emu)
+
+
+# ---- the depth-map filters against the fp64 restatement (parity_cases.fusion_vs_fp64): reduced sizes, every branch ----
+@pytest.mark.parametrize("dynamic,v,kw", [
+    (False, 1, {}), (False, 2, {"thres_disp": 0.25}), (False, 4, {"thres_disp": 4.0}), (False, 10, {"metres": True}),
+    (False, 16, {"thres_view": 5}), (False, 10, {"thres_view": 1}), (False, 10, {"thres_view": 12}),
+    (True, 2, {}), (True, 3, {"metres": True}), (True, 10, {}), (True, 16, {"dist_base": 3.0, "rel_diff_base": 800.0}),
+    (True, 10, {"metres": True, "rot_deg": 5.0, "seed": 4})])
+def test_fusion_scene_fp64(emu, dynamic, v, kw):
+    P.case_fusion_scene_fp64(emu, 60, 90, v, dynamic, **kw)
+
+
+@pytest.mark.parametrize("dynamic", [False, True])
+def test_fusion_scene_fp64_tiny(emu, dynamic):
+    """7x5: 35 pixels, one partial workgroup.  Most samples there use a cell across the image border (excluded from the
+    reproj_xyd comparison), so the compared share is lower."""
+    P.case_fusion_scene_fp64(emu, 7, 5, 4, dynamic, bounds={"borderline": 0.03, "xyd_cmp": 0.3})
+
+
+def test_fusion_batch(emu):
+    P.case_fusion_batch(emu, 45, 61, 4)
+
+
+def test_fusion_view_limits(emu):
+    P.case_fusion_view_limits(emu)
+
+
+def test_fusion_thresholds_exact(emu):
+    P.case_fusion_thresholds_exact(emu)

@@ -292,6 +292,28 @@ def test_fusion_golden():
     P.case_fusion_golden(DEV)
 
 
+@pytest.mark.parametrize("dynamic", [False, True])
+@pytest.mark.parametrize("H,W,kw", [(1152, 1600, {}), (1056, 1920, {"metres": True, "rot_deg": 4.0, "seed": 2}), (517, 743, {"seed": 3})],
+                         ids=["dtu", "tt", "ragged"])
+def test_fusion_scene_fp64(H, W, kw, dynamic):
+    """The fused filter at the DTU / T&T output sizes and a size whose pixel count is not a multiple of 256 (517x743: the tail
+    workgroup), 10 sources, against the fp64 restatement (parity_cases.fusion_vs_fp64)."""
+    P.case_fusion_scene_fp64(DEV, H, W, 10, dynamic, **kw)
+
+
+def test_fusion_batch():
+    """n = 2 (blockIdx.y) through every entry point, per element against its own n = 1 run and the fp64 restatement."""
+    P.case_fusion_batch(DEV, 517, 743, 10)
+
+
+def test_fusion_view_limits():
+    P.case_fusion_view_limits(DEV)
+
+
+def test_fusion_thresholds_exact():
+    P.case_fusion_thresholds_exact(DEV)
+
+
 def test_attention_bf16p():
     """MVS_PREC_BF16P: bf16 softmax probabilities in p.v (optional fast mode of the transformer stage)."""
     P.case_attention_stress(DEV, n=4099, bf16p=True)

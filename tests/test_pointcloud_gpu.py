@@ -75,3 +75,36 @@ def test_f22_reproducible_files(tmp_path):
     run_f22(fx, tmp_path, "pcd", "tt", DEV, a)
     run_f22(fx, tmp_path, "pcd", "tt", DEV, b)
     assert open(a, "rb").read() == open(b, "rb").read() and os.path.getsize(a) > 1000
+
+
+@pytest.mark.parametrize("method", ["pcd", "dpcd"])
+def test_full_size_scene_fp64(method):
+    """Sibling of test_full_size_scene_bitwise against an independent reference: one 1152x1600 reference view with 10 rotated
+    sources (synth.make_box_scene) through PointCloudAccumulator.  Each record's colour carries its pixel index, so the records
+    name their pixels: every decided pixel the fp64 restatement keeps (parity_cases.fusion_vs_fp64) is a record, no decided
+    pixel it drops is, and each record's xyz is within the rule's point bound of the fp64 point."""
+    import parity_cases as P
+    H, W, v = 1152, 1600, 10
+    rd, rconf, sd, sconf, rc, sc = P._box_inputs(H, W, v, seed=5, rot_deg=3.0)
+    idx = torch.arange(H * W, dtype=torch.int64).reshape(H, W)
+    rgb = torch.stack([idx & 255, (idx >> 8) & 255, (idx >> 16) & 255], -1).to(torch.uint8)
+    dev = torch.device(DEV)
+    acc = PC.PointCloudAccumulator(dev, capacity=1 << 22)
+    with torch.no_grad():
+        out = acc.add_view(rd.to(dev), rconf.to(dev), sd.to(dev), sconf.to(dev) if method == "pcd" else None, rc.to(dev), sc.to(dev),
+                           rgb.to(dev), method, conf=0.5)
+    rec = acc.records().view(data_io.PLY_VERTEX_DTYPE)
+    got = {"mask": out["mask"][0].cpu(), "points": out["points"][0].cpu(), "depth": out["depth"][0].cpu(), "geo_mask": out["geo_mask"][0].cpu()}
+    dyn = method == "dpcd"
+    st = P.fusion_vs_fp64(got, rd, rconf, sd, None if dyn else sconf, rc, sc, dynamic=dyn, conf_thresh=0.5,
+                          p0=4.0 if dyn else 1.0, p1=1300.0 if dyn else 0.01, vthresh=2)
+    pix = torch.from_numpy(rec["red"].astype(np.int64) | (rec["green"].astype(np.int64) << 8) | (rec["blue"].astype(np.int64) << 16))
+    assert pix.numel() == int(got["mask"].sum()) and bool((pix[1:] > pix[:-1]).all())     # one record per kept pixel, row-major
+    in_ply = torch.zeros(H * W, dtype=torch.bool)
+    in_ply[pix] = True
+    dec, keep = st["_decided"].reshape(-1), st["_mask64"].reshape(-1)
+    assert torch.equal(in_ply[dec], keep[dec])
+    assert 0.3 < float(keep.double().mean()) < 0.95
+    # the records hold the filter's points bit for bit, and those met fusion_vs_fp64's point bound on every decided pixel above
+    xyz = torch.from_numpy(np.stack([rec["x"], rec["y"], rec["z"]]))
+    assert torch.equal(xyz, got["points"].reshape(3, -1)[:, pix])
