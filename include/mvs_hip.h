@@ -496,6 +496,28 @@ int mvs_pointcloud_append(const uint8_t* mask, const float* points, const uint8_
                           size_t workspace_bytes, unsigned* counter, unsigned* view_counts, int view_slot, uint8_t* records,
                           long long capacity, void* stream);
 
+/* ==== gipuma route: fusibile's cross-view consistency fusion as misc/gipuma.py drives it ===========
+ * The probability filter (misc/gipuma.py:160-181), the camera conversion (:72-92: P = [K 0; 0 1] E, first three rows) and the
+ * fusion fusibile performs on the converted folder (:184-205), restated from the project's contract.  N views of one size h x w,
+ * device-resident: depths fp32 [N,h,w] (filtered), colours u32 [N,h,w] (r | g << 8 | b << 16), used u8 [N,h,w] (zeroed once).
+ * mvs_gipuma_prepare_cams is HOST code (fp64): cams [N,2,4,4] fp32 as everywhere -> view_consts [N, view_floats] and
+ * pair_consts [N, N, pair_floats] (fp32, host memory; the caller uploads them).  Fails on a singular P[:, :3].              */
+size_t mvs_gipuma_view_floats(void);
+size_t mvs_gipuma_pair_floats(void);
+int mvs_gipuma_prepare_cams(const float* cams, int N, float* view_consts, float* pair_consts);
+/* one view's slot: depth_out = keep ? depth : 0 (keep u8 [h,w] nullable = keep all), color_out = packed rgb [h,w,3] u8     */
+int mvs_gipuma_prepare_view(const float* depth, const uint8_t* keep, const uint8_t* rgb, int h, int w, float* depth_out,
+                            uint32_t* color_out, void* stream);
+/* one launch per reference view r, in processing order on ONE stream (the marks of launch r are read by the later launches):
+ * mask [h,w] u8, points [3,h,w] fp32, rgb [h,w,3] u8 of view r, as mvs_pointcloud_append reads them (points / rgb are written
+ * for kept pixels only); used[c][v][u] = 1 for every pixel an emitted vertex used (c != r).  depth_min / depth_max are applied
+ * exactly as in fp64 to the fp32 map values; a vertex needs n >= num_consistent consistent views.  skipped (nullable,
+ * diagnostic) receives the used[r] the launch read.                                                                        */
+int mvs_gipuma_fuse_view(const float* depths, const uint32_t* colors, uint8_t* used, const float* view_consts,
+                         const float* pair_consts, int N, int h, int w, int r, double depth_min, double depth_max,
+                         float disp_thresh, double num_consistent, uint8_t* mask, float* points, uint8_t* rgb,
+                         uint8_t* skipped, void* stream);
+
 /* ---- layout helpers for the nn.Module-level API (NCDHW <-> channel-last) -------------------------*/
 int mvs_ncdhw_to_cl(const float* x, float* y_cl, int B, int C, int D, int H, int W, void* stream);
 int mvs_cl_to_ncdhw(const float* x_cl, float* y, int B, int C, int D, int H, int W, void* stream);

@@ -110,6 +110,11 @@ SIGNATURES = {
     "mvs_fusion_ave_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "mvs_pointcloud_workspace_bytes": (_sz, [_i, _i]),
     "mvs_pointcloud_append": (_i, [_vp, _vp, _vp, _i, _i, _vp, _sz, _vp, _vp, _i, _vp, C.c_longlong, _vp]),
+    "mvs_gipuma_view_floats": (_sz, []),
+    "mvs_gipuma_pair_floats": (_sz, []),
+    "mvs_gipuma_prepare_cams": (_i, [_vp, _i, _vp, _vp]),
+    "mvs_gipuma_prepare_view": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
+    "mvs_gipuma_fuse_view": (_i, [_vp] * 5 + [_i] * 4 + [C.c_double, C.c_double, _f, C.c_double] + [_vp] * 5),
     "mvs_ncdhw_to_cl": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "mvs_cl_to_ncdhw": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
 }

@@ -11,12 +11,17 @@ with the reference so that either side can be swapped on its own:
                                              (test.py:136-146, test_tt.py:142-156)
     point cloud ``<scan>.ply``               binary little-endian PLY, vertex {float x, y, z; uchar red, green, blue}
                                              (test.py:431-442, written there with plyfile)
+    Gipuma     ``points_mvsnet/``            fusibile's input folder: cams/<image>.P, images/, 2333__<view>/disp.dmb and
+                                             normals.dmb (misc/gipuma.py:25-157)
 
 Host-side numpy only; nothing here touches the GPU.
 """
 from __future__ import annotations
 
+import os
 import re
+import shutil
+import struct
 import sys
 from typing import List, Tuple
 
@@ -195,3 +200,88 @@ def read_ply(filename: str) -> Tuple[np.ndarray, np.ndarray]:
     xyz = np.stack([v[c] for c in "xyz"], -1).astype(np.float32)
     rgb = np.stack([v[c] for c in ("red", "green", "blue")], -1).astype(np.uint8)
     return xyz, rgb
+
+
+# ---------------------------------------------------------------- Gipuma / fusibile formats (misc/gipuma.py:25-157)
+def read_gipuma_dmb(path: str) -> np.ndarray:
+    """A Gipuma .dmb image: int32 type, height, width, channels, then the float32 samples, channel-planar -> [H,W] or [H,W,C]
+    (misc/gipuma.py:25-36)."""
+    with open(path, "rb") as f:
+        _, height, width, channels = struct.unpack("<4i", f.read(16))
+        data = np.fromfile(f, np.float32)
+    return np.transpose(data.reshape((width, height, channels), order="F"), (1, 0, 2)).squeeze()
+
+
+def write_gipuma_dmb(path: str, image: np.ndarray) -> None:
+    """[H,W] or [H,W,C] -> .dmb (misc/gipuma.py:39-60): the samples are written in the array's own dtype, [C,H,W] order."""
+    image = np.asarray(image)
+    height, width = image.shape[0], image.shape[1]
+    channels = image.shape[2] if image.ndim == 3 else 1
+    if image.ndim == 3:
+        image = np.transpose(image, (2, 0, 1)).squeeze()
+    with open(path, "wb") as f:
+        f.write(struct.pack("<4i", 1, height, width, channels))
+        image.tofile(f)
+
+
+def gipuma_projection(intrinsics: np.ndarray, extrinsics: np.ndarray) -> np.ndarray:
+    """P = [K 0; 0 0] E, first three rows, in float64 from the float32 file values (misc/gipuma.py:72-80) -> [3,4]."""
+    k4 = np.zeros((4, 4))
+    k4[:3, :3] = intrinsics
+    return np.matmul(k4, extrinsics)[0:3]
+
+
+def write_gipuma_cam(path: str, intrinsics: np.ndarray, extrinsics: np.ndarray) -> None:
+    """The .P file fusibile reads: P's 12 float64 values as str() writes them, each followed by a space, one row per line, then
+    an empty line (misc/gipuma.py:82-90)."""
+    P = gipuma_projection(intrinsics, extrinsics)
+    with open(path, "w") as f:
+        for i in range(3):
+            f.write("".join(str(P[i][j]) + " " for j in range(4)) + "\n")
+        f.write("\n")
+
+
+def gipuma_view_names(scan_folder: str) -> List[str]:
+    """The image file names of a scene (images/, hidden files skipped), sorted: the Gipuma route's view set and order."""
+    folder = os.path.join(scan_folder, "images")
+    if not os.path.isdir(folder):
+        raise ValueError("%s: no images/ folder" % scan_folder)
+    return sorted(n for n in os.listdir(folder) if not n.startswith("."))
+
+
+def gipuma_prob_filter(depth: np.ndarray, prob: np.ndarray, prob_threshold: float) -> np.ndarray:
+    """misc/gipuma.py:172-179: a uint8 map is divided by 255 (float64), any other is compared in its own dtype; depth is kept
+    where prob > prob_threshold and set to 0 elsewhere (a filtered copy is returned)."""
+    if prob.dtype == np.uint8:
+        prob = prob / 255
+    out = np.array(depth, copy=True)
+    out[~(prob > prob_threshold)] = 0
+    return out
+
+
+def export_gipuma_folder(scan_folder: str, point_folder: str, prob_threshold: float = 0.5, write_filtered: bool = False) -> List[str]:
+    """The probability filter and the conversion of misc/gipuma.py:116-181 (probability_filter + mvsnet_to_gipuma): write
+    fusibile's input folder `point_folder` (cams/<image>.P, images/ copied, 2333__<view>/disp.dmb and normals.dmb with the
+    reference's fake normals).  depth_est/<view>_prob_filtered.pfm is written next to the depth maps only with write_filtered.
+    -> the view names (sorted image names).  Running fusibile on the folder is left to the caller."""
+    names = gipuma_view_names(scan_folder)
+    for sub in ("", "cams", "images"):
+        os.makedirs(os.path.join(point_folder, sub), exist_ok=True)
+    for name in names:
+        prefix = os.path.splitext(name)[0]
+        K, E = read_camera_parameters(os.path.join(scan_folder, "cams", prefix + "_cam.txt"))
+        write_gipuma_cam(os.path.join(point_folder, "cams", name + ".P"), K, E)
+        shutil.copy(os.path.join(scan_folder, "images", name), os.path.join(point_folder, "images", name))
+        depth, _ = read_pfm(os.path.join(scan_folder, "depth_est", prefix + ".pfm"))
+        depth = gipuma_prob_filter(depth, np.load(os.path.join(scan_folder, "confidence", prefix + ".npy")), prob_threshold)
+        if write_filtered:
+            save_pfm(os.path.join(scan_folder, "depth_est", prefix + "_prob_filtered.pfm"), depth)
+        sub = os.path.join(point_folder, "2333__" + prefix)
+        os.makedirs(sub, exist_ok=True)
+        write_gipuma_dmb(os.path.join(sub, "disp.dmb"), depth)
+        # fake normals (misc/gipuma.py:95-113): (1, 1, 1) / 1.732050808 where the depth read back from disp.dmb is > 0
+        d = read_gipuma_dmb(os.path.join(sub, "disp.dmb"))
+        mask = np.tile(np.where(d > 0, 1, 0).reshape(d.shape[0], d.shape[1], 1), [1, 1, 3]).astype(np.float32)
+        normal = np.tile(np.ones_like(d).reshape(d.shape[0], d.shape[1], 1), [1, 1, 3]) / 1.732050808
+        write_gipuma_dmb(os.path.join(sub, "normals.dmb"), np.float32(np.multiply(normal, mask)))
+    return names

@@ -866,6 +866,53 @@ def pointcloud_append(mask, points, rgb, records, counter, view_counts=None, vie
                                       ptr(records), records.numel() // PLY_RECORD_BYTES, stream_of(m)), "mvs_pointcloud_append")
 
 
+# ---- gipuma route (misc/gipuma.py) -------------------------------------------
+def gipuma_prepare_cams(cams) -> Tuple[torch.Tensor, torch.Tensor]:
+    """cams [N,2,4,4] (host or device; float32 values) -> (view_consts [N, view_floats], pair_consts [N, N, pair_floats]), fp32
+    host tensors prepared in fp64 on the host.  Raises on a singular P[:, :3]."""
+    import numpy as np
+    c = np.ascontiguousarray(torch.as_tensor(cams).detach().cpu().numpy(), dtype=np.float32).reshape(-1, 2, 4, 4)
+    n = c.shape[0]
+    vf, pf = lib().mvs_gipuma_view_floats(), lib().mvs_gipuma_pair_floats()
+    views = np.zeros((n, vf), np.float32)
+    pairs = np.zeros((n, n, pf), np.float32)
+    check(lib().mvs_gipuma_prepare_cams(c.ctypes.data, n, views.ctypes.data, pairs.ctypes.data), "mvs_gipuma_prepare_cams")
+    return torch.from_numpy(views), torch.from_numpy(pairs)
+
+
+def gipuma_prepare_view(depth, keep, rgb, depth_out, color_out) -> None:
+    """One view's device slot: depth_out [h,w] fp32 = keep ? depth : 0 (keep [h,w] bool / uint8, None = keep all), color_out
+    [h,w] int32 = packed rgb [h,w,3] uint8.  Stream-ordered."""
+    h, w = depth.shape[-2:]
+    d = _f32c(depth).reshape(h, w)
+    k = None if keep is None else keep.reshape(h, w).contiguous()
+    if k is not None and k.dtype == torch.bool:
+        k = k.view(torch.uint8)
+    col = rgb.reshape(h, w, 3).contiguous()
+    assert col.dtype == torch.uint8 and depth_out.dtype == torch.float32 and color_out.dtype == torch.int32
+    assert depth_out.is_contiguous() and color_out.is_contiguous() and depth_out.numel() == h * w == color_out.numel()
+    check(lib().mvs_gipuma_prepare_view(ptr(d), ptr(k), ptr(col), h, w, ptr(depth_out), ptr(color_out), stream_of(d)),
+          "mvs_gipuma_prepare_view")
+
+
+def gipuma_fuse_view(depths, colors, used, view_consts, pair_consts, r: int, *, depth_min: float, depth_max: float, disp_thresh: float,
+                     num_consistent: float, mask, points, rgb, skipped=None) -> None:
+    """Fusion launch of reference view r: depths [N,h,w] fp32, colors [N,h,w] int32, used [N,h,w] uint8 (read at r, marked
+    elsewhere), constants from gipuma_prepare_cams on the same device -> mask [h,w] uint8, points [3,h,w] fp32, rgb [h,w,3] uint8
+    (kept pixels only), skipped [h,w] uint8 (optional).  Stream-ordered, no synchronisation."""
+    n, h, w = depths.shape
+    for t, dt in ((depths, torch.float32), (colors, torch.int32), (used, torch.uint8), (view_consts, torch.float32),
+                  (pair_consts, torch.float32), (mask, torch.uint8), (points, torch.float32), (rgb, torch.uint8)):
+        assert t.dtype == dt and t.is_contiguous(), "gipuma_fuse_view: bad tensor"
+    assert colors.shape == used.shape == depths.shape and mask.numel() == h * w and points.numel() == 3 * h * w and rgb.numel() == 3 * h * w
+    assert view_consts.shape[0] == n and pair_consts.shape[:2] == (n, n)
+    if skipped is not None:
+        assert skipped.dtype == torch.uint8 and skipped.is_contiguous() and skipped.numel() == h * w
+    check(lib().mvs_gipuma_fuse_view(ptr(depths), ptr(colors), ptr(used), ptr(view_consts), ptr(pair_consts), n, h, w, int(r),
+                                     float(depth_min), float(depth_max), float(disp_thresh), float(num_consistent), ptr(mask), ptr(points),
+                                     ptr(rgb), ptr(skipped), stream_of(depths)), "mvs_gipuma_fuse_view")
+
+
 # ---- a13-a16 ------------------------------------------------------------------------------------
 def depth_regression(p: torch.Tensor, depth_values: torch.Tensor) -> torch.Tensor:
     pp, dv = _f32c(p), _f32c(depth_values)
