@@ -4,7 +4,14 @@ achieved HBM GB/s vs peak").
 
     python bench.py --gpus 1 --steps 20 --warmup 3          # 20 steps x 96 reference views
     python bench.py --gpus 1 --steps 20 --warmup 3 --dump-outputs DIR   # + the last timed step's outputs as DIR/<name>.npy
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full   # + every extra object below (several minutes)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port P bench.py --gpus 8 ...
+
+A plain run does only what the headline needs: it sets up, warms up, times the steps, writes the outputs if --dump-outputs is given
+and prints the JSON line (`value`, `ms_per_step`, `dtype`, `config`, `whole_path`).  `--full` adds everything else this file measures
+or checks, each outside the timed region: the single-stream `latency`, the per-kernel profile behind `roofline`, the other precisions,
+hand-offs and regulariser mix, the feature emitter, the training step, the view-sharded leg (N > 1), the torch-ROCm composite and CPU
+baselines with the `parity` read-out.  The `--no-*` switches leave single legs out of a --full run.
 
 One "step" = one batch of `--views-per-step` (default 96) reference views, each pushed through the whole 4-stage cascade with
 batch 1 per forward call like the reference's test.py loop (features in HBM -> refined depth + confidence): hypothesis
@@ -28,17 +35,17 @@ same inputs (bar 1e-3).
 The reference views of a step are issued round-robin on `--streams` HIP streams (default 4 since round 5 - graph replay and the default
 policy's launch-bound coarse stages moved the optimum from 3: 606 vs 595 ref-views/s, three alternations on one box): views are independent, so the small
 latency-bound launches of one view's coarse stages overlap the large launches of another's fine stages; the single-stream
-figure (one view at a time, the reference's loop) is reported in `latency`, the per-kernel profile behind `roofline` is
+figure (one view at a time, the reference's loop) is reported in `latency` by --full, the per-kernel profile behind `roofline` is
 single-stream too.  Issue (round 5): one hipGraph replay per reference view (`CascadeDepthHead.capture`, one graph per (stream,
 input set); `--issue eager` = the ~60 launches of a view issued from Python) - the same device work; the host needs ~1.1 ms per view to
 issue it eagerly, which a device path below ~1.3 ms per view no longer hides.
 
 N > 1: one process per GPU; reference views are independent, so every rank runs its own stream of reference views
 (data parallel over reference views, no data-path collective; "scaling": "weak").  The view-sharded latency mode
-(source views over ranks, partial cost volumes combined per stage over RCCL) is timed afterwards on
+(source views over ranks, partial cost volumes combined per stage over RCCL) is timed afterwards by --full on
 BASELINE configs[2]'s shape (V = 10) and reported in the extra `view_sharded` object.
 
-Rank 0 prints ONE JSON line.  Extra objects: `training_step` (N = 1: forward + backward of each cascade stage through the native
+Rank 0 prints ONE JSON line.  Extra objects (--full only): `latency`, `training_step` (N = 1: forward + backward of each cascade stage through the native
 training kernels at DTU-training-like sizes, outside the timed region), `roofline` (dominant kernel, HIP-event timing on the launch stream) and
 `cpu_baseline` (the oracle - a CPU restatement of the reference path - timed on this host's cores, N=1 only), `fp32_equivalent_mode`
 (N = 1: the same weights, inputs and loop with the regularisers in "bf16x3", outside the timed headline: both modes in one line),
@@ -228,7 +235,7 @@ def dump_outputs(dirname, outputs):
     print("bench.py: wrote %d arrays (%.1f MB) to %s" % (len(arrays), written / 1e6, dirname), file=sys.stderr)
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
@@ -249,6 +256,10 @@ def main():
                     help="graph (default): replay one captured hipGraph per (stream, input set) (CascadeDepthHead.capture) - one launch per "
                          "reference view from the host's side; eager: issue the ~60 launches of a reference view from Python.  The same device work")
     ap.add_argument("--graph", action="store_true", help="= --issue graph (kept for the round-3/4 scripts)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run every extra leg (single-stream latency, per-kernel profile and roofline, other precisions, "
+                         "hand-offs and regulariser mix, feature emitter, training step, view-sharded leg, torch-ROCm composite and CPU "
+                         "baselines with parity); the headline and its timed steps are the same with or without it")
     ap.add_argument("--no-shipped-leg", action="store_true", help="skip the extra `shipped` object (stage-1 transformer mix: value + parity)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-composite-baseline", action="store_true", help="skip the torch-ROCm composite baseline leg (the oracle's tensors on cuda:0)")
@@ -291,10 +302,17 @@ def main():
                     help="after the timed steps, write what the timed path returned in its last step - for every input set, the outputs of its last "
                          "reference view of that step - as DIR/<name>.npy (float32 / float64, at most 64 MB in all: larger tensors as a fixed "
                          "seeded sample, see DIR/manifest.json).  Inputs depend only on the arguments, so two builds compare output for output")
-    a = ap.parse_args()
+    a = ap.parse_args(argv)
     if a.steps < 1:
         ap.error("--steps must be >= 1")
+    if a.profile_table and not a.full:
+        ap.error("--profile-table prints the per-kernel profile, which only --full runs")
     a.graph = a.graph or a.issue == "graph"
+    return a
+
+
+def main():
+    a = parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -441,18 +459,19 @@ def main():
             dump_outputs(a.dump_outputs, {"set%d" % k: o for k, o in sorted(last_outputs.items())})
         last_outputs = None
 
-        # single-stream latency: one reference view at a time on the current stream, the reference's own loop shape (test.py:238-252)
-        n_lat = 4 * nsets
-        for j in range(nsets):
-            head(*sets[j], tmp=TMP)
-        torch.cuda.synchronize()
-        tl0 = time.perf_counter()
-        for j in range(n_lat):
-            head(*sets[j % nsets], tmp=TMP)
-        torch.cuda.synchronize()
-        latency_ms = (time.perf_counter() - tl0) / (n_lat * BATCH) * 1e3
-        out = head(feats, projs, dv, tmp=TMP)
-        torch.cuda.synchronize()
+        if a.full:
+            # single-stream latency: one reference view at a time on the current stream, the reference's own loop shape (test.py:238-252)
+            n_lat = 4 * nsets
+            for j in range(nsets):
+                head(*sets[j], tmp=TMP)
+            torch.cuda.synchronize()
+            tl0 = time.perf_counter()
+            for j in range(n_lat):
+                head(*sets[j % nsets], tmp=TMP)
+            torch.cuda.synchronize()
+            latency_ms = (time.perf_counter() - tl0) / (n_lat * BATCH) * 1e3
+            out = head(feats, projs, dv, tmp=TMP)
+            torch.cuda.synchronize()
     t = torch.tensor([elapsed], dtype=torch.float64, device=device)
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -476,16 +495,15 @@ def main():
                    "features": "%s %s resident in HBM" % (a.feat_dtype, {"tiled": "octet-tiled [B,V,C/8,H,W,8]", "planar": "planar [B,V,C,H,W]",
                                                                            "emitted": "planar stage 1 + %s octet tiles written by the producer-side emitter (stages 2-4)" % a.emit_dtype}[a.feat_layout])},
         "ms_per_ref_view": ms_per_step / R,
-        "latency": {"single_stream_ms_per_ref_view": latency_ms, "single_stream_ref_views_per_s": 1e3 / latency_ms,
-                    "note": "one reference view at a time on one stream (the reference's loop, test.py:238-252), same rotating inputs"},
     }
     if is_cfg2:
         gbs = ALGO_BYTES_PER_VIEW * value / world / 1e9
         result["whole_path"] = {"algorithmic_bytes_per_ref_view": ALGO_BYTES_PER_VIEW, "achieved_gbs_per_gpu": gbs, "peak_gbs": 8000.0,
-                                "frac": gbs / 8000.0, "frac_single_stream": ALGO_BYTES_PER_VIEW / (latency_ms * 1e-3) / 8.0e12,
+                                "frac": gbs / 8000.0,
                                 "note": "frac: SURVEY.md section 8d layer-wise byte model (fp32 tensors, 5.03 GB per reference view at cfg2) x ref-views/s / "
-                                        "8 TB/s; frac_as_built / frac_pmc (added by the profile leg): the bytes the tensors of the as-built format "
-                                        "really have / the PMC-counted HBM bytes, same views/s, same peak"}
+                                        "8 TB/s; frac_single_stream (--full): the same at the single-stream latency; frac_as_built / frac_pmc (added by "
+                                        "the profile leg): the bytes the tensors of the as-built format really have / the PMC-counted HBM bytes, same "
+                                        "views/s, same peak"}
 
     result["config"]["cost_reg_type"] = SHIPPED["cost_reg_type"] if a.cost_reg == "shipped" else ["Normal"] * 4
     prec0 = head.fusions[0].precision_policy
@@ -517,6 +535,15 @@ def main():
         result["config"]["gather_pass2"] = ("second gather on every stage (--no-keep-correlations)" if a.no_keep_correlations else
                                             "stream of the per-view correlations kept by pass 1 (fp32 on the exact coarse stages from D = 16 on, fp16 "
                                             "on the fp16-format stages with D > 4); otherwise a second gather")
+
+    if not a.full:
+        print_and_close(result, rank, world)
+        return
+
+    result["latency"] = {"single_stream_ms_per_ref_view": latency_ms, "single_stream_ref_views_per_s": 1e3 / latency_ms,
+                         "note": "one reference view at a time on one stream (the reference's loop, test.py:238-252), same rotating inputs"}
+    if "whole_path" in result:
+        result["whole_path"]["frac_single_stream"] = ALGO_BYTES_PER_VIEW / (latency_ms * 1e-3) / 8.0e12
 
     # ---- per-kernel HIP-event profile -> roofline of the dominant kernel ----
     if not a.no_profile:
@@ -849,11 +876,17 @@ def main():
                             "confidence_max_abs_vs_oracle": float((out["photometric_confidence"].cpu() - ref["photometric_confidence"]).abs().max()),
                             "bar": 1e-3}
 
+    print_and_close(result, rank, world)
+
+
+def print_and_close(result, rank, world):
+    """Rank 0 prints the JSON line; N > 1 then leaves the process group."""
     if rank == 0:
         print(json.dumps(result), flush=True)
     if world > 1:
         # the line is out; a rank whose peers left through their watchdog must not wait in the closing barrier for ever
         import threading
+        import torch.distributed as dist
         bye = threading.Timer(60.0, lambda: os._exit(0))
         bye.daemon = True
         bye.start()

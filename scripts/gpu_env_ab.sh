@@ -12,7 +12,7 @@ for setting in "$@"; do
     i=$((i+1))
     echo "== bench: $setting =="
     ( [ "$setting" != "-" ] && export "$setting"
-      timeout 600 python bench.py --steps 10 --warmup 3 --profile-table --no-cpu-baseline --no-train-leg ${BENCH_ARGS:-} > $OUT/bench_env$i.json 2> $OUT/bench_env$i.err )
+      timeout 600 python bench.py --full --steps 10 --warmup 3 --profile-table --no-cpu-baseline --no-train-leg ${BENCH_ARGS:-} > $OUT/bench_env$i.json 2> $OUT/bench_env$i.err )
     grep -v "amdgpu.ids" $OUT/bench_env$i.err | grep -E "${TABLE_GREP:-conv|deconv|sum of|kernel  }" | head -${TABLE_ROWS:-30}
     python - "$OUT/bench_env$i.json" <<'PY'
 import json, sys

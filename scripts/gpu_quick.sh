@@ -7,7 +7,7 @@ export PYTHONDONTWRITEBYTECODE=1
 echo "== pytest -m gpu =="
 timeout 600 python -m pytest tests -m gpu -x -q 2>&1 | tail -6 | tee $OUT/pytest_gpu.log
 echo "== bench =="
-timeout 600 python bench.py --steps 10 --warmup 2 --profile-table ${BENCH_ARGS:-} > $OUT/bench.json 2> $OUT/bench.err
+timeout 600 python bench.py --full --steps 10 --warmup 2 --profile-table ${BENCH_ARGS:-} > $OUT/bench.json 2> $OUT/bench.err
 grep -v "amdgpu.ids" $OUT/bench.err | tail -45
 python - <<'PY'
 import json

@@ -9,7 +9,7 @@ timeout 900 python -m pytest tests -m gpu -x -q 2>&1 | tail -6 | tee $OUT/pytest
 echo "== per-stage gather A/B =="
 timeout 300 python scripts/prof_gather.py 2>&1 | grep -v amdgpu.ids | tee $OUT/prof_gather.log
 echo "== bench (LDS-staged gather) =="
-timeout 600 python bench.py --steps 20 --warmup 3 --profile-table --no-cpu-baseline > $OUT/bench_lds.json 2> $OUT/bench_lds.err
+timeout 600 python bench.py --full --steps 20 --warmup 3 --profile-table --no-cpu-baseline > $OUT/bench_lds.json 2> $OUT/bench_lds.err
 grep -v "amdgpu.ids" $OUT/bench_lds.err | tail -40
 python - <<'PY'
 import json

@@ -8,7 +8,7 @@ export PYTHONDONTWRITEBYTECODE=1
 echo "== pytest -m gpu =="
 timeout 900 python -m pytest tests -m gpu -x -q 2>&1 | tail -6 | tee $OUT/pytest_gpu.log
 echo "== bench (driver's command) =="
-timeout 900 python bench.py --steps 20 --warmup 5 --profile-table > $OUT/bench.json 2> $OUT/bench.err
+timeout 900 python bench.py --full --steps 20 --warmup 5 --profile-table > $OUT/bench.json 2> $OUT/bench.err
 grep -v "amdgpu.ids" $OUT/bench.err | tail -48
 python - <<'PY'
 import json
@@ -24,7 +24,7 @@ except Exception as e:
 PY
 for args in "--conv-precision f16mix" "--issue eager" ""; do
   echo "== A/B: bench.py --steps 10 $args =="
-  timeout 600 python bench.py --steps 10 --warmup 3 --no-profile --no-cpu-baseline --no-train-leg --no-shipped-leg $args > $OUT/ab.json 2>/dev/null
+  timeout 600 python bench.py --full --steps 10 --warmup 3 --no-profile --no-cpu-baseline --no-train-leg --no-shipped-leg $args > $OUT/ab.json 2>/dev/null
   python -c "
 import json; r = json.loads(open('gpurun_out/ab.json').read().strip().splitlines()[-1]); print('$args', round(r['value'],1), 'ref-views/s', round(r['ms_per_ref_view'],3), 'ms; single', round(r['latency']['single_stream_ms_per_ref_view'],3), r['config']['issue'])"
 done

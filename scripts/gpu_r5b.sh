@@ -8,7 +8,7 @@ export PYTHONDONTWRITEBYTECODE=1
 echo "== pytest -m gpu (new / touched cases) =="
 timeout 900 python -m pytest tests -m gpu -x -q -k "track_s or fused_small or feature_heads or regnet_golden or single_layers or f16_layers or cascade_golden or gather_variants or cfg1 or hip_graph" 2>&1 | tail -4 | tee $OUT/pytest_gpu.log
 echo "== bench (driver's command) =="
-timeout 900 python bench.py --steps 20 --warmup 5 --profile-table > $OUT/bench.json 2> $OUT/bench.err
+timeout 900 python bench.py --full --steps 20 --warmup 5 --profile-table > $OUT/bench.json 2> $OUT/bench.err
 grep -v "amdgpu.ids" $OUT/bench.err | tail -44
 python - <<'PY'
 import json
@@ -22,7 +22,7 @@ except Exception as e:
     print('bench.json unreadable', e)
 PY
 for args in "--streams 3" "--streams 4" "--streams 5" "--streams 6" "--streams 3 --keep-exact-min-depth 32" "--streams 3 --keep-exact-min-depth 1000" "--streams 3 --conv-precision f16mix" "--streams 3"; do
-  timeout 600 python bench.py --steps 10 --warmup 3 --no-profile --no-cpu-baseline --no-train-leg --no-shipped-leg $args > $OUT/ab.json 2>/dev/null
+  timeout 600 python bench.py --full --steps 10 --warmup 3 --no-profile --no-cpu-baseline --no-train-leg --no-shipped-leg $args > $OUT/ab.json 2>/dev/null
   python -c "
 import json; r = json.loads(open('gpurun_out/ab.json').read().strip().splitlines()[-1]); print('%-48s' % '$args', round(r['value'],1), 'ref-views/s', round(r['ms_per_ref_view'],3), 'ms; single', round(r['latency']['single_stream_ms_per_ref_view'],3))"
 done

@@ -8,7 +8,7 @@ export PYTHONDONTWRITEBYTECODE=1
 timeout 300 python scripts/diag_stage_time.py 2>&1 | grep -v amdgpu.ids
 cd /tmp && export TMPDIR=/tmp
 for pol in stagemix f16mix; do
-  timeout 600 rocprofv3 --kernel-trace --stats -d $ROOT/$OUT/prof_$pol -o $pol -- python $ROOT/bench.py --steps 2 --warmup 1 --views-per-step 8 --streams 1 --issue eager \
+  timeout 600 rocprofv3 --kernel-trace --stats -d $ROOT/$OUT/prof_$pol -o $pol -- python $ROOT/bench.py --full --steps 2 --warmup 1 --views-per-step 8 --streams 1 --issue eager \
       --no-profile --no-cpu-baseline --no-train-leg --no-shipped-leg --conv-precision $pol > $ROOT/$OUT/rocprof_$pol.log 2>&1
   DB=$(find $ROOT/$OUT/prof_$pol -name '*.db' | head -1)
   python $ROOT/scripts/rocpd_stats.py $DB "mvs::" > $ROOT/$OUT/kernel_stats_$pol.csv

@@ -10,7 +10,7 @@ for lib in mvsformerplusplus_amd/csrc/libmvs_hip.so mvsformerplusplus_amd/csrc/l
   tag=$(basename $lib .so)
   echo "== $tag =="
   MVS_HIP_LIB=$PWD/$lib timeout 200 python scripts/diag_stage_time.py stagemix 2>&1 | grep -v amdgpu.ids
-  MVS_HIP_LIB=$PWD/$lib timeout 200 python bench.py --steps 10 --warmup 3 --no-profile --no-cpu-baseline --no-train-leg --no-shipped-leg > $OUT/ab.json 2>/dev/null
+  MVS_HIP_LIB=$PWD/$lib timeout 200 python bench.py --full --steps 10 --warmup 3 --no-profile --no-cpu-baseline --no-train-leg --no-shipped-leg > $OUT/ab.json 2>/dev/null
   python -c "
 import json; r = json.loads(open('gpurun_out/ab.json').read().strip().splitlines()[-1]); print('$tag', round(r['value'],1), 'ref-views/s', round(r['ms_per_ref_view'],3), 'ms; single', round(r['latency']['single_stream_ms_per_ref_view'],3))"
 done

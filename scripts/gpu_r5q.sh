@@ -9,7 +9,7 @@ for v in "" 4 "" 4; do
     lib=""; [ -n "$v" ] && lib=$L/libmvs_hip_direct$v.so
     MVS_HIP_LIB="$lib" timeout 200 python scripts/prof_gather_direct.py 2>&1 | tail -3
 done
-B="--steps 10 --warmup 3 --no-cpu-baseline --no-train-leg --no-shipped-leg"
+B="--full --steps 10 --warmup 3 --no-cpu-baseline --no-train-leg --no-shipped-leg"
 for v in "" 4; do
     lib=""; [ -n "$v" ] && lib=$L/libmvs_hip_direct$v.so
     MVS_HIP_LIB="$lib" timeout 300 python bench.py $B > gpurun_out/ab_q$v.json 2>gpurun_out/ab_q$v.err || tail -5 gpurun_out/ab_q$v.err

@@ -3,7 +3,7 @@
 set -u
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 export PYTHONDONTWRITEBYTECODE=1
-B="--steps 8 --warmup 2 --no-profile --no-cpu-baseline --no-train-leg --no-shipped-leg"
+B="--full --steps 8 --warmup 2 --no-profile --no-cpu-baseline --no-train-leg --no-shipped-leg"
 for cfg in "1 4" "1 6" "2 2" "2 3" "4 1" "4 2" "2 4" "1 4"; do
   set -- $cfg
   echo "== batch $1 streams $2 =="

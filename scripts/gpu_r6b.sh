@@ -5,7 +5,7 @@ cd "${GRAFT_REPO_ROOT:-/root/repo}"
 export PYTHONDONTWRITEBYTECODE=1
 L=$PWD/mvsformerplusplus_amd/csrc
 timeout 900 python -m pytest tests/test_gpu_parity.py -x -q -k "gather or stage_golden or lowp or cascade_golden or cfg2" 2>&1 | tail -5
-B="--steps 8 --warmup 2 --no-cpu-baseline --no-train-leg --no-shipped-leg --profile-table"
+B="--full --steps 8 --warmup 2 --no-cpu-baseline --no-train-leg --no-shipped-leg --profile-table"
 for v in "" glopt0 "" glopt0; do
     lib=""; [ -n "$v" ] && lib=$L/libmvs_hip_$v.so
     echo "=== variant [$v]"

@@ -4,7 +4,7 @@ set -u
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 export PYTHONDONTWRITEBYTECODE=1
 timeout 900 python -m pytest tests/test_gpu_parity.py -x -q -k "vis or stage_golden or cascade_golden or cfg2" 2>&1 | tail -5
-B="--steps 8 --warmup 2 --no-cpu-baseline --no-train-leg --no-shipped-leg --profile-table"
+B="--full --steps 8 --warmup 2 --no-cpu-baseline --no-train-leg --no-shipped-leg --profile-table"
 for v in "" 1 "" 1; do
     echo "=== MVS_VIS_BLOCK=[$v]"
     if [ -n "$v" ]; then export MVS_VIS_BLOCK=1; else unset MVS_VIS_BLOCK; fi

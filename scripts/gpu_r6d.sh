@@ -11,7 +11,7 @@ for v in "" zskip0 "" zskip0; do
     echo "=== variant [$v]"
     MVS_HIP_LIB="$lib" timeout 300 python scripts/bench_unet_layers.py 2>&1 | tail -22
 done
-B="--steps 8 --warmup 2 --no-cpu-baseline --no-train-leg --no-shipped-leg --profile-table"
+B="--full --steps 8 --warmup 2 --no-cpu-baseline --no-train-leg --no-shipped-leg --profile-table"
 for v in "" zskip0 ""; do
     lib=""; [ -n "$v" ] && lib=$L/libmvs_hip_$v.so
     echo "=== bench variant [$v]"

@@ -8,7 +8,7 @@ timeout 900 python -m pytest tests/test_gpu_parity.py -x -q -k "gather or stage_
 timeout 300 python scripts/gather_ablate.py 2>&1 | grep -v amdgpu.ids | tail -1
 for v in glsb1 glsb3; do MVS_HIP_LIB=$L/libmvs_hip_$v.so timeout 300 python scripts/gather_ablate.py 2>&1 | grep -v amdgpu.ids | tail -1; done
 timeout 300 python scripts/gather_ablate.py 2>&1 | grep -v amdgpu.ids | tail -1
-B="--steps 8 --warmup 2 --no-cpu-baseline --no-train-leg --no-shipped-leg --no-profile"
+B="--full --steps 8 --warmup 2 --no-cpu-baseline --no-train-leg --no-shipped-leg --no-profile"
 for v in "" glsb1 glsb3 "" glsb1 glsb3; do
     lib=""; [ -n "$v" ] && lib=$L/libmvs_hip_$v.so
     MVS_HIP_LIB="$lib" timeout 400 python bench.py $B > gpurun_out/r6h_$v.json 2> gpurun_out/r6h_$v.err || tail -5 gpurun_out/r6h_$v.err

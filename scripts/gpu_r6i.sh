@@ -10,7 +10,7 @@ for v in "" dus0 "" dus0; do
     echo "=== variant [$v]"
     MVS_HIP_LIB="$lib" timeout 300 python scripts/bench_unet_layers.py 2>&1 | grep -E "deconv|sum"
 done
-B="--steps 8 --warmup 2 --no-cpu-baseline --no-train-leg --no-shipped-leg --no-profile"
+B="--full --steps 8 --warmup 2 --no-cpu-baseline --no-train-leg --no-shipped-leg --no-profile"
 for v in "" dus0 "" dus0; do
     lib=""; [ -n "$v" ] && lib=$L/libmvs_hip_$v.so
     MVS_HIP_LIB="$lib" timeout 400 python bench.py $B > gpurun_out/r6i_$v.json 2> gpurun_out/r6i_$v.err || tail -5 gpurun_out/r6i_$v.err

@@ -13,14 +13,14 @@ timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2 | 
 # PMC first: bench.py's roofline.traffic / whole_path.frac_pmc read profiles/pmc_traffic.json, which must describe THIS build's kernels
 (cd /tmp && export TMPDIR=/tmp
 echo "== PMC: HBM traffic of every kernel (separate passes) =="
-timeout 600 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $ROOT/$OUT/pmc_$TAG/f -o f -- python $ROOT/bench.py --steps 1 --warmup 1 --views-per-step 4 --issue eager --no-shipped-leg --no-cpu-baseline --no-profile --no-train-leg > $ROOT/$OUT/pmc_f.log 2>&1
-timeout 600 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $ROOT/$OUT/pmc_$TAG/w -o w -- python $ROOT/bench.py --steps 1 --warmup 1 --views-per-step 4 --issue eager --no-shipped-leg --no-cpu-baseline --no-profile --no-train-leg > $ROOT/$OUT/pmc_w.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $ROOT/$OUT/pmc_$TAG/f -o f -- python $ROOT/bench.py --full --steps 1 --warmup 1 --views-per-step 4 --issue eager --no-shipped-leg --no-cpu-baseline --no-profile --no-train-leg > $ROOT/$OUT/pmc_f.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $ROOT/$OUT/pmc_$TAG/w -o w -- python $ROOT/bench.py --full --steps 1 --warmup 1 --views-per-step 4 --issue eager --no-shipped-leg --no-cpu-baseline --no-profile --no-train-leg > $ROOT/$OUT/pmc_w.log 2>&1
 )
 mkdir -p $OUT/profiles_$TAG
 python scripts/pmc_traffic.py $OUT/pmc_$TAG $OUT/profiles_$TAG/pmc_traffic.json $OUT/profiles_$TAG/${TAG}_pmc_fetch_write_raw.json
 cp $OUT/profiles_$TAG/pmc_traffic.json profiles/pmc_traffic.json
 echo "== bench (driver's command) =="
-timeout 1500 python bench.py --steps 20 --warmup 5 --profile-table > $OUT/bench.json 2> $OUT/bench.err
+timeout 1500 python bench.py --full --steps 20 --warmup 5 --profile-table > $OUT/bench.json 2> $OUT/bench.err
 grep -v "amdgpu.ids" $OUT/bench.err | tail -45
 python - <<'PY'
 import json
@@ -33,7 +33,7 @@ PY
 echo "== randomised cascades in the product default vs the oracle (scripts/fuzz_cascade_gpu.py 60 0) =="
 timeout 600 python scripts/fuzz_cascade_gpu.py 60 0 2>&1 | grep -v amdgpu.ids > $OUT/fuzz_cascade.log; tail -3 $OUT/fuzz_cascade.log
 echo "== bench, shipped regulariser mix (stage-1 transformer + PE3D) =="
-timeout 900 python bench.py --steps 6 --warmup 2 --profile-table --cost-reg shipped --issue eager > $OUT/bench_shipped.json 2> $OUT/bench_shipped.err
+timeout 900 python bench.py --full --steps 6 --warmup 2 --profile-table --cost-reg shipped --issue eager > $OUT/bench_shipped.json 2> $OUT/bench_shipped.err
 grep -v "amdgpu.ids" $OUT/bench_shipped.err | grep -E "tr_|pos3d|softmax_regress|sum of"
 python - <<'PY'
 import json
@@ -41,20 +41,20 @@ r = json.loads(open('gpurun_out/bench_shipped.json').read().strip().splitlines()
 print('shipped', {k: r[k] for k in ('value', 'ms_per_ref_view') if k in r}, 'parity', r.get('parity'))
 PY
 echo "== bench, fp32-equivalent regulariser format (--conv-precision bf16x3: split bf16 pairs, three MFMA terms) =="
-timeout 600 python bench.py --steps 10 --warmup 3 --profile-table --no-train-leg --no-cpu-baseline --conv-precision bf16x3 > $OUT/bench_bf16x3.json 2> $OUT/bench_bf16x3.err
+timeout 600 python bench.py --full --steps 10 --warmup 3 --profile-table --no-train-leg --no-cpu-baseline --conv-precision bf16x3 > $OUT/bench_bf16x3.json 2> $OUT/bench_bf16x3.err
 python -c "
 import json; r = json.loads(open('gpurun_out/bench_bf16x3.json').read().strip().splitlines()[-1]); print('bf16x3', r['value'], r['ms_per_ref_view'], r['latency']['single_stream_ms_per_ref_view'])"
 echo "== bench, bf16 features in the octet-tiled hand-off layout =="
-timeout 600 python bench.py --steps 6 --warmup 2 --no-profile --no-cpu-baseline --feat-layout tiled --feat-dtype bf16 > $OUT/bench_tiled_bf16.json 2>/dev/null
+timeout 600 python bench.py --full --steps 6 --warmup 2 --no-profile --no-cpu-baseline --feat-layout tiled --feat-dtype bf16 > $OUT/bench_tiled_bf16.json 2>/dev/null
 python -c "
 import json; r = json.loads(open('gpurun_out/bench_tiled_bf16.json').read().strip().splitlines()[-1]); print('tiled bf16', r['value'], r['ms_per_ref_view'])"
 echo "== bench, stages 2-4 fed by the producer-side emitter's fp16 octet tiles (no pack pass in the process; direct gather at stages 3-4) =="
-timeout 600 python bench.py --steps 10 --warmup 3 --no-profile --no-train-leg --no-shipped-leg --feat-layout emitted --emit-dtype fp16 > $OUT/bench_emitted.json 2>/dev/null
+timeout 600 python bench.py --full --steps 10 --warmup 3 --no-profile --no-train-leg --no-shipped-leg --feat-layout emitted --emit-dtype fp16 > $OUT/bench_emitted.json 2>/dev/null
 python -c "
 import json; r = json.loads(open('gpurun_out/bench_emitted.json').read().strip().splitlines()[-1]); print('emitted fp16 tiles', r['value'], r['ms_per_ref_view'], r.get('parity'))"
 echo "== N = 2 flow of bench.py on this one-GPU box (both ranks on the device, gloo): code path check, not a measurement =="
 MVS_BENCH_ONE_DEVICE=1 MVS_BENCH_BACKEND=gloo timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
-  --master-port 29511 bench.py --gpus 2 --steps 2 --warmup 1 --views-per-step 4 --no-profile > $OUT/bench_n2.raw 2> $OUT/bench_n2.err
+  --master-port 29511 bench.py --full --gpus 2 --steps 2 --warmup 1 --views-per-step 4 --no-profile > $OUT/bench_n2.raw 2> $OUT/bench_n2.err
 grep '^{' $OUT/bench_n2.raw | tail -1 > $OUT/bench_n2.json          # gloo prints "[Gloo] Rank ..." lines on stdout: keep the JSON line only
 python - <<'PY'
 import json
@@ -66,11 +66,11 @@ except Exception as e:
 PY
 echo "== rocprofv3 kernel trace (same bench command, 5 steps) =="
 cd /tmp && export TMPDIR=/tmp
-timeout 900 rocprofv3 --kernel-trace --stats -d $ROOT/$OUT/prof_$TAG -o $TAG -- python $ROOT/bench.py --steps 5 --warmup 1 --issue eager --no-shipped-leg --no-train-leg --no-cpu-baseline --no-profile > $ROOT/$OUT/rocprof.log 2>&1
+timeout 900 rocprofv3 --kernel-trace --stats -d $ROOT/$OUT/prof_$TAG -o $TAG -- python $ROOT/bench.py --full --steps 5 --warmup 1 --issue eager --no-shipped-leg --no-train-leg --no-cpu-baseline --no-profile > $ROOT/$OUT/rocprof.log 2>&1
 tail -2 $ROOT/$OUT/rocprof.log
 # the same with ONE stream: kernels of different reference views do not overlap, so the average durations are the launches' own
 # (what bench.py's HIP-event table and its `roofline` object measure); with 3 streams co-running kernels stretch each other
-timeout 900 rocprofv3 --kernel-trace --stats -d $ROOT/$OUT/prof1_$TAG -o $TAG -- python $ROOT/bench.py --steps 5 --warmup 1 --streams 1 --issue eager --no-shipped-leg --no-train-leg --no-cpu-baseline --no-profile > $ROOT/$OUT/rocprof1.log 2>&1
+timeout 900 rocprofv3 --kernel-trace --stats -d $ROOT/$OUT/prof1_$TAG -o $TAG -- python $ROOT/bench.py --full --steps 5 --warmup 1 --streams 1 --issue eager --no-shipped-leg --no-train-leg --no-cpu-baseline --no-profile > $ROOT/$OUT/rocprof1.log 2>&1
 cd $ROOT
 DB=$(find $OUT/prof_$TAG -name '*.db' | head -1)
 if [ -n "$DB" ]; then
@@ -96,7 +96,7 @@ grep -v "amdgpu.ids" $OUT/bench.err > $OUT/profiles_$TAG/${TAG}_bench_kernel_tab
 grep -v "amdgpu.ids" $OUT/bench_shipped.err > $OUT/profiles_$TAG/${TAG}_bench_kernel_table_shipped.txt
 rm -rf $OUT/prof_$TAG $OUT/prof1_$TAG $OUT/pmc_$TAG
 echo "== bench, the exact-coarse branch of the default policy (--conv-precision stagemix) =="
-timeout 600 python bench.py --steps 10 --warmup 3 --profile-table --no-train-leg --no-cpu-baseline --no-shipped-leg --conv-precision stagemix > $OUT/bench_stagemix.json 2> $OUT/bench_stagemix.err
+timeout 600 python bench.py --full --steps 10 --warmup 3 --profile-table --no-train-leg --no-cpu-baseline --no-shipped-leg --conv-precision stagemix > $OUT/bench_stagemix.json 2> $OUT/bench_stagemix.err
 python -c "
 import json; r = json.loads(open('gpurun_out/bench_stagemix.json').read().strip().splitlines()[-1]); print('stagemix', r['value'], r['ms_per_ref_view'], r['latency']['single_stream_ms_per_ref_view'])"
 cp $OUT/bench_stagemix.json $OUT/profiles_$TAG/${TAG}_bench_1gpu_stagemix.json

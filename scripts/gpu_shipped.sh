@@ -5,7 +5,7 @@ cd "${GRAFT_REPO_ROOT:-/root/repo}"
 OUT=gpurun_out; mkdir -p $OUT
 export PYTHONDONTWRITEBYTECODE=1
 timeout 600 python -m pytest tests -m gpu -x -q -k "transformer or shipped" 2>&1 | tail -6 | tee $OUT/pytest_gpu_tr.log
-timeout 900 python bench.py --steps 5 --warmup 2 --profile-table --cost-reg shipped ${BENCH_ARGS:-} > $OUT/bench_shipped.json 2> $OUT/bench_shipped.err
+timeout 900 python bench.py --full --steps 5 --warmup 2 --profile-table --cost-reg shipped ${BENCH_ARGS:-} > $OUT/bench_shipped.json 2> $OUT/bench_shipped.err
 grep -v "amdgpu.ids" $OUT/bench_shipped.err | tail -50
 python - <<'PY'
 import json

@@ -11,7 +11,7 @@ timeout 600 python scripts/prof_attn.py 2>&1 | grep -v amdgpu.ids | tee $OUT/r04
 echo "== pytest subset =="
 timeout 900 python -m pytest tests -m gpu -x -q -k "attention or transformer or shipped" 2>&1 | tail -5 | tee $OUT/pytest_gpu_subset.log
 echo "== bench (all-Normal) =="
-timeout 900 python bench.py --steps 10 --warmup 3 --profile-table --no-cpu-baseline --no-train-leg > $OUT/bench.json 2> $OUT/bench.err
+timeout 900 python bench.py --full --steps 10 --warmup 3 --profile-table --no-cpu-baseline --no-train-leg > $OUT/bench.json 2> $OUT/bench.err
 grep -v "amdgpu.ids" $OUT/bench.err | tail -40
 python - <<'PY'
 import json
@@ -21,7 +21,7 @@ for k in ('latency', 'whole_path', 'roofline'):
     print(k, r.get(k))
 PY
 echo "== bench (shipped mix) =="
-timeout 900 python bench.py --steps 4 --warmup 1 --views-per-step 32 --profile-table --cost-reg shipped > $OUT/bench_shipped.json 2> $OUT/bench_shipped.err
+timeout 900 python bench.py --full --steps 4 --warmup 1 --views-per-step 32 --profile-table --cost-reg shipped > $OUT/bench_shipped.json 2> $OUT/bench_shipped.err
 grep -v "amdgpu.ids" $OUT/bench_shipped.err | grep -E "tr_|pos3d|softmax_regress|sum of"
 python - <<'PY'
 import json

@@ -7,7 +7,7 @@ export PYTHONDONTWRITEBYTECODE=1
 echo "== pytest subset =="
 timeout 900 python -m pytest tests -m gpu -x -q -k "vis_cnn or stage_golden or cascade_golden or wide_range or fullsize_properties" 2>&1 | tail -3
 echo "== bench =="
-timeout 600 python bench.py --steps 8 --warmup 3 --profile-table --no-cpu-baseline --no-train-leg > $OUT/bench_v10.json 2> $OUT/bench_v10.err
+timeout 600 python bench.py --full --steps 8 --warmup 3 --profile-table --no-cpu-baseline --no-train-leg > $OUT/bench_v10.json 2> $OUT/bench_v10.err
 grep -v "amdgpu.ids" $OUT/bench_v10.err | grep -E "vis_cnn|sum of" | head
 python - $OUT/bench_v10.json <<'PY'
 import json, sys

@@ -6,7 +6,7 @@ OUT=gpurun_out; mkdir -p $OUT
 export PYTHONDONTWRITEBYTECODE=1
 for cfg in "1 3" "2 3" "2 2" "4 2" "3 3" "1 5"; do
   set -- $cfg
-  timeout 600 python bench.py --steps 6 --warmup 3 --no-profile --no-cpu-baseline --no-train-leg --batch $1 --streams $2 > $OUT/bench_b$1s$2.json 2> $OUT/bench_b$1s$2.err
+  timeout 600 python bench.py --full --steps 6 --warmup 3 --no-profile --no-cpu-baseline --no-train-leg --batch $1 --streams $2 > $OUT/bench_b$1s$2.json 2> $OUT/bench_b$1s$2.err
   python - $OUT/bench_b$1s$2.json "$cfg" <<'PY'
 import json, sys
 try:

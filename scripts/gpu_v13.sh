@@ -7,7 +7,7 @@ OUT=gpurun_out; mkdir -p $OUT
 export PYTHONDONTWRITEBYTECODE=1
 : > $OUT/streams_ab_v13.txt
 for cfg in "--streams 3" "--streams 2" "--streams 4" "--streams 6" "--streams 3 --batch 2" "--streams 3"; do
-  timeout 100 python bench.py --steps 10 --warmup 3 --no-profile --no-cpu-baseline --no-train-leg $cfg > $OUT/b13.json 2> $OUT/b13.err
+  timeout 100 python bench.py --full --steps 10 --warmup 3 --no-profile --no-cpu-baseline --no-train-leg $cfg > $OUT/b13.json 2> $OUT/b13.err
   python - "$cfg" <<'PY' | tee -a $OUT/streams_ab_v13.txt
 import json, sys
 try:

@@ -10,7 +10,7 @@ export PYTHONDONTWRITEBYTECODE=1
 for lib in mvsformerplusplus_amd/csrc/libmvs_hip.so mvsformerplusplus_amd/csrc/libmvs_hip_*.so mvsformerplusplus_amd/csrc/libmvs_hip.so; do
   [ -f "$lib" ] || continue
   tag=$(basename $lib .so)
-  MVS_HIP_LIB=$PWD/$lib timeout 100 python bench.py --steps 10 --warmup 3 --no-profile --no-cpu-baseline --no-train-leg > $OUT/b14.json 2> $OUT/b14.err
+  MVS_HIP_LIB=$PWD/$lib timeout 100 python bench.py --full --steps 10 --warmup 3 --no-profile --no-cpu-baseline --no-train-leg > $OUT/b14.json 2> $OUT/b14.err
   python - "$tag" <<'PY' | tee -a $OUT/tiles_ab_v14.txt
 import json, sys
 try:

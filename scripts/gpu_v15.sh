@@ -8,7 +8,7 @@ export PYTHONDONTWRITEBYTECODE=1
 : > $OUT/graph_ab_v15.txt
 nproc | sed 's/^/host threads: /' | tee -a $OUT/graph_ab_v15.txt
 for cfg in "--streams 3" "--streams 3 --graph" "--streams 4 --graph" "--streams 6 --graph" "--streams 3 --graph --input-sets 2" "--streams 3"; do
-  timeout 120 python bench.py --steps 10 --warmup 3 --no-profile --no-cpu-baseline --no-train-leg $cfg > $OUT/b15.json 2> $OUT/b15.err
+  timeout 120 python bench.py --full --steps 10 --warmup 3 --no-profile --no-cpu-baseline --no-train-leg $cfg > $OUT/b15.json 2> $OUT/b15.err
   python - "$cfg" <<'PY' | tee -a $OUT/graph_ab_v15.txt
 import json, sys
 try:

@@ -10,7 +10,7 @@ echo "== pytest subset =="
 timeout 900 python -m pytest tests -m gpu -x -q -k "attention or golden or saturation or single_layers or midsize or cfg1" 2>&1 | tail -5 | tee $OUT/pytest_gpu_subset.log
 for prec in f16mix f16 f16x2; do
   echo "== bench $prec =="
-  timeout 600 python bench.py --steps 10 --warmup 3 --profile-table --no-cpu-baseline --no-train-leg --conv-precision $prec > $OUT/bench_$prec.json 2> $OUT/bench_$prec.err
+  timeout 600 python bench.py --full --steps 10 --warmup 3 --profile-table --no-cpu-baseline --no-train-leg --conv-precision $prec > $OUT/bench_$prec.json 2> $OUT/bench_$prec.err
   grep -v "amdgpu.ids" $OUT/bench_$prec.err | grep -E "conv3d|deconv|sum of" | head -24
   python - $OUT/bench_$prec.json <<'PY'
 import json, sys

@@ -13,7 +13,7 @@ timeout 900 python -m pytest tests -m gpu -x -q -k "golden or single_layers or f
 for off in 0 1; do
   echo "== bench (MVS_CONV_LOADER_OFF=$off) ==" | tee -a $OUT/r04_conv_loader_ab.txt
   if [ $off = 1 ]; then export MVS_CONV_LOADER_OFF=1; fi
-  timeout 600 python bench.py --steps 10 --warmup 3 --profile-table --no-cpu-baseline --no-train-leg > $OUT/bench_l$off.json 2> $OUT/bench_l$off.err
+  timeout 600 python bench.py --full --steps 10 --warmup 3 --profile-table --no-cpu-baseline --no-train-leg > $OUT/bench_l$off.json 2> $OUT/bench_l$off.err
   grep -v "amdgpu.ids" $OUT/bench_l$off.err | grep -E "conv3d|deconv|sum of" | head -24 | tee -a $OUT/r04_conv_loader_ab.txt
   python - $OUT/bench_l$off.json <<'PY' | tee -a $OUT/r04_conv_loader_ab.txt
 import json, sys

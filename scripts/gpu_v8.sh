@@ -9,7 +9,7 @@ timeout 900 python -m pytest tests -m gpu -x -q -k "gather or stage_golden or ca
 for mode in keep nokeep; do
   flag=""; [ $mode = nokeep ] && flag="--no-keep-correlations"
   echo "== bench $mode =="
-  timeout 600 python bench.py --steps 8 --warmup 3 --profile-table --no-cpu-baseline --no-train-leg $flag > $OUT/bench_$mode.json 2> $OUT/bench_$mode.err
+  timeout 600 python bench.py --full --steps 8 --warmup 3 --profile-table --no-cpu-baseline --no-train-leg $flag > $OUT/bench_$mode.json 2> $OUT/bench_$mode.err
   grep -v "amdgpu.ids" $OUT/bench_$mode.err | grep -E "gl_|corr_agg|sum of" | head -14
   python - $OUT/bench_$mode.json <<'PY'
 import json, sys
@@ -18,7 +18,7 @@ print({k: r[k] for k in ('value', 'ms_per_ref_view') if k in r}, 'latency', r['l
 PY
 done
 echo "== bench keep, tiled fp16 features =="
-timeout 600 python bench.py --steps 8 --warmup 3 --no-cpu-baseline --no-train-leg --feat-layout tiled --feat-dtype fp16 > $OUT/bench_keep_tiled.json 2> $OUT/bench_keep_tiled.err
+timeout 600 python bench.py --full --steps 8 --warmup 3 --no-cpu-baseline --no-train-leg --feat-layout tiled --feat-dtype fp16 > $OUT/bench_keep_tiled.json 2> $OUT/bench_keep_tiled.err
 python - $OUT/bench_keep_tiled.json <<'PY'
 import json, sys
 r = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

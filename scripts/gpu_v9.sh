@@ -9,7 +9,7 @@ timeout 900 python -m pytest tests -m gpu -x -q -k "gather or stage_golden or ca
 for mode in w16 w32; do
   [ $mode = w32 ] && export MVS_GATHER_WINDOW=f32
   echo "== bench $mode =="
-  timeout 600 python bench.py --steps 8 --warmup 3 --profile-table --no-cpu-baseline --no-train-leg > $OUT/bench_$mode.json 2> $OUT/bench_$mode.err
+  timeout 600 python bench.py --full --steps 8 --warmup 3 --profile-table --no-cpu-baseline --no-train-leg > $OUT/bench_$mode.json 2> $OUT/bench_$mode.err
   grep -v "amdgpu.ids" $OUT/bench_$mode.err | grep -E "gl_|corr_agg|sum of" | head -14
   python - $OUT/bench_$mode.json <<'PY'
 import json, sys

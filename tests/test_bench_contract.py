@@ -1,5 +1,6 @@
 """CPU: the bench line committed under profiles/ (produced by bench.py on an MI355X) carries every field of the driver's
-contract, with consistent arithmetic.  Guards the JSON schema without needing a GPU."""
+contract, with consistent arithmetic.  Guards the JSON schema without needing a GPU.  The GPU cases run bench.py itself at a small size,
+plain (the headline alone) and with --full (the extra legs)."""
 import json
 import os
 
@@ -62,3 +63,53 @@ def test_committed_bench_line(name):
         if not wp["pmc_symbols_without_counters"]:          # every launch counted: the counter bytes cannot be below the bytes the tensors have
             assert wp["frac_as_built"] <= wp["frac_pmc"]
         assert r["kernels"] and all(v.get("gbs", 0) <= 8000.0 for v in r["kernels"].values())
+
+
+# ---- plain run vs --full: the plain run prints the headline alone, --full adds the extra legs ----
+HEADLINE_KEYS = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
+                 "data", "config", "ms_per_ref_view")
+EXTRA_KEYS = ("latency", "roofline", "gather_roofline", "kernels", "families", "attention_bf16p", "fp32_equivalent_mode", "exact_coarse_mode",
+              "uniform_f16mix_mode", "fp16_tiles_handoff_mode", "shipped", "feature_emitter", "training_step", "view_sharded",
+              "torch_rocm_composite", "cpu_baseline", "parity")
+
+
+def test_full_is_opt_in():
+    import bench
+    assert bench.parse_args([]).full is False
+    a = bench.parse_args(["--full", "--profile-table", "--no-train-leg"])
+    assert a.full and a.profile_table and a.no_train_leg
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--profile-table"])          # the per-kernel table belongs to the profile leg, which only --full runs
+
+
+def _bench_line(args, timeout):
+    import subprocess
+    import sys
+    small = ["--steps", "1", "--warmup", "1", "--height", "128", "--width", "192", "--views", "3", "--views-per-step", "4",
+             "--input-sets", "2", "--streams", "2"]
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + small + args, cwd=ROOT, capture_output=True, text=True,
+                       timeout=timeout)
+    assert p.returncode == 0, p.stderr[-3000:]
+    return json.loads(p.stdout.strip().splitlines()[-1])
+
+
+@pytest.mark.gpu
+def test_plain_run_prints_the_headline_alone(tmp_path):
+    r = _bench_line(["--dump-outputs", str(tmp_path)], timeout=300)
+    for k in HEADLINE_KEYS:
+        assert k in r, k
+    assert r["unit"] == "ref-views/s" and r["higher_is_better"] is True and r["value"] > 0 and r["ms_per_step"] > 0
+    assert abs(r["value"] - r["config"]["global_batch"] * 1e3 / r["ms_per_step"]) <= 1e-6 * r["value"]
+    assert r["dtype"].startswith("fp16 operands/storage, fp32 accumulate")
+    assert not [k for k in EXTRA_KEYS if k in r]
+    assert os.path.exists(os.path.join(str(tmp_path), "manifest.json"))
+
+
+@pytest.mark.gpu
+def test_full_run_adds_the_extra_legs():
+    r = _bench_line(["--full", "--no-train-leg", "--no-composite-baseline"], timeout=600)
+    for k in HEADLINE_KEYS + ("latency", "roofline", "families", "kernels", "fp32_equivalent_mode", "fp16_tiles_handoff_mode", "cpu_baseline", "parity"):
+        assert k in r, k
+    assert "error" not in r["fp32_equivalent_mode"] and "error" not in r["fp16_tiles_handoff_mode"]
+    assert r["latency"]["single_stream_ms_per_ref_view"] > 0
+    assert r["parity"]["refined_depth_rel_l1_vs_oracle"] <= r["parity"]["bar"]
