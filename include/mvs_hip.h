@@ -518,6 +518,19 @@ int mvs_gipuma_fuse_view(const float* depths, const uint32_t* colors, uint8_t* u
                          float disp_thresh, double num_consistent, uint8_t* mask, float* points, uint8_t* rgb,
                          uint8_t* skipped, void* stream);
 
+/* ==== colmap2mvsnet: view-selection scores and depth values of a COLMAP model =====================
+ * fp64 throughout, device-resident.  mvs_colmap_depths: z[k] = erow[obs_img[k]] . [xyz[obs_pt[k]], 1] for n observations
+ * (erow = row 2 of each image's [R|t; 0 1], [N, 4]; xyz [P, 3]).  mvs_colmap_scores: score [N, N] (zeroed here) for N <= 16384
+ * images from a per-image CSR (img_ptr [N+1], img_pts sorted unique dense point indices, img_mult their multiplicities) and a
+ * per-point CSR of ascending unique images (pt_ptr [P+1], pt_imgs); centres [N, 3] = -R^T t; den1 / den2 = 2 sigma1^2,
+ * 2 sigma2^2.  max_pairs >= the number of co-visible pairs i < j sizes `pairs` (u32); flags u8 [N, N] scratch (zeroed here);
+ * workspace of mvs_colmap_workspace_bytes(N) (0 = N out of range).  Deterministic: no atomics, fixed reduction order.     */
+size_t mvs_colmap_workspace_bytes(int N);
+int mvs_colmap_depths(const int* obs_img, const int* obs_pt, long long n, const double* xyz, const double* erow, double* z, void* stream);
+int mvs_colmap_scores(const int* img_ptr, const int* img_pts, const int* img_mult, int N, const int* pt_ptr, const int* pt_imgs, int P,
+                      const double* xyz, const double* centres, double theta0, double den1, double den2, long long max_pairs,
+                      uint8_t* flags, unsigned* pairs, void* workspace, size_t workspace_bytes, double* score, void* stream);
+
 /* ---- layout helpers for the nn.Module-level API (NCDHW <-> channel-last) -------------------------*/
 int mvs_ncdhw_to_cl(const float* x, float* y_cl, int B, int C, int D, int H, int W, void* stream);
 int mvs_cl_to_ncdhw(const float* x_cl, float* y, int B, int C, int D, int H, int W, void* stream);

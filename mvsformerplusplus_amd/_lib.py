@@ -115,6 +115,10 @@ SIGNATURES = {
     "mvs_gipuma_prepare_cams": (_i, [_vp, _i, _vp, _vp]),
     "mvs_gipuma_prepare_view": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
     "mvs_gipuma_fuse_view": (_i, [_vp] * 5 + [_i] * 4 + [C.c_double, C.c_double, _f, C.c_double] + [_vp] * 5),
+    "mvs_colmap_workspace_bytes": (_sz, [_i]),
+    "mvs_colmap_depths": (_i, [_vp, _vp, C.c_longlong, _vp, _vp, _vp, _vp]),
+    "mvs_colmap_scores": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, C.c_double, C.c_double, C.c_double, C.c_longlong]
+                          + [_vp] * 3 + [_sz, _vp, _vp]),
     "mvs_ncdhw_to_cl": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "mvs_cl_to_ncdhw": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
 }

@@ -913,6 +913,51 @@ def gipuma_fuse_view(depths, colors, used, view_consts, pair_consts, r: int, *, 
                                      ptr(rgb), ptr(skipped), stream_of(depths)), "mvs_gipuma_fuse_view")
 
 
+# ---- colmap2mvsnet (colmap2mvsnet.py) ----------------------------------------
+COLMAP_MAX_IMAGES = 16384
+
+
+def _i32c(t: torch.Tensor) -> torch.Tensor:
+    assert t.dtype == torch.int32, "expected int32, got %s" % t.dtype
+    return t.contiguous()
+
+
+def _f64c(t: torch.Tensor) -> torch.Tensor:
+    assert t.dtype == torch.float64, "expected float64, got %s" % t.dtype
+    return t.contiguous()
+
+
+def colmap_depths(obs_img, obs_pt, xyz, erow) -> torch.Tensor:
+    """z [n] fp64 of n observations: obs_img / obs_pt int32 [n] (image, dense point index), xyz fp64 [P,3], erow fp64 [N,4] (row 2 of
+    each image's extrinsic).  Stream-ordered."""
+    oi, op, x, e = _i32c(obs_img), _i32c(obs_pt), _f64c(xyz), _f64c(erow)
+    z = torch.empty(oi.numel(), dtype=torch.float64, device=oi.device)
+    check(lib().mvs_colmap_depths(ptr(oi), ptr(op), oi.numel(), ptr(x), ptr(e), ptr(z), stream_of(oi)), "mvs_colmap_depths")
+    return z
+
+
+def colmap_scores(img_ptr, img_pts, img_mult, pt_ptr, pt_imgs, xyz, centres, *, theta0: float, den1: float, den2: float,
+                  max_pairs: int) -> torch.Tensor:
+    """score [N,N] fp64 of the view selection: the per-image CSR (img_ptr int32 [N+1], img_pts / img_mult int32: sorted unique dense
+    point indices and their multiplicity), the per-point CSR of ascending images (pt_ptr int32 [P+1], pt_imgs int32), xyz fp64 [P,3],
+    centres fp64 [N,3]; den = 2 sigma^2; max_pairs >= the number of co-visible pairs.  Stream-ordered, no synchronisation."""
+    ip, ipt, im, pp, pim = (_i32c(t) for t in (img_ptr, img_pts, img_mult, pt_ptr, pt_imgs))
+    x, c = _f64c(xyz), _f64c(centres)
+    n, p = ip.numel() - 1, pp.numel() - 1
+    dev = ip.device
+    nbytes = lib().mvs_colmap_workspace_bytes(n)
+    if nbytes == 0:
+        raise ValueError("colmap_scores: %d images (1..%d)" % (n, COLMAP_MAX_IMAGES))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    flags = torch.empty(n * n, dtype=torch.uint8, device=dev)
+    pairs = torch.empty(max(int(max_pairs), 1), dtype=torch.int32, device=dev)
+    score = torch.empty(n, n, dtype=torch.float64, device=dev)
+    check(lib().mvs_colmap_scores(ptr(ip), ptr(ipt), ptr(im), n, ptr(pp), ptr(pim), p, ptr(x), ptr(c), float(theta0), float(den1),
+                                  float(den2), int(max_pairs), ptr(flags), ptr(pairs), ptr(ws), nbytes, ptr(score), stream_of(ip)),
+          "mvs_colmap_scores")
+    return score
+
+
 # ---- a13-a16 ------------------------------------------------------------------------------------
 def depth_regression(p: torch.Tensor, depth_values: torch.Tensor) -> torch.Tensor:
     pp, dv = _f32c(p), _f32c(depth_values)

@@ -296,3 +296,117 @@ def make_box_scene(V: int, H: int, W: int, *, seed: int = 0, metres: bool = Fals
     conf[:, H // 4:H // 4 + max(1, H // 40), :] *= 0.5
     conf[torch.rand(d.shape, generator=g) < 0.002] = conf_thresh
     return {"depth": d.contiguous(), "conf": conf.contiguous(), "cams": cams.contiguous()}
+
+
+def _rotmat2qvec(R):
+    """Unit quaternion (w, x, y, z) of rotation matrices [..., 3, 3] (w >= 0)."""
+    import numpy as np
+    R = np.asarray(R, np.float64)
+    w = np.sqrt(np.maximum(0.0, 1 + R[..., 0, 0] + R[..., 1, 1] + R[..., 2, 2])) / 2
+    x = np.copysign(np.sqrt(np.maximum(0.0, 1 + R[..., 0, 0] - R[..., 1, 1] - R[..., 2, 2])) / 2, R[..., 2, 1] - R[..., 1, 2])
+    y = np.copysign(np.sqrt(np.maximum(0.0, 1 - R[..., 0, 0] + R[..., 1, 1] - R[..., 2, 2])) / 2, R[..., 0, 2] - R[..., 2, 0])
+    z = np.copysign(np.sqrt(np.maximum(0.0, 1 - R[..., 0, 0] - R[..., 1, 1] + R[..., 2, 2])) / 2, R[..., 1, 0] - R[..., 0, 1])
+    q = np.stack([w, x, y, z], -1)
+    return q / np.linalg.norm(q, axis=-1, keepdims=True)
+
+
+def make_colmap_model(n_images: int, n_points: int, *, seed: int = 0, layout: str = "ring", window: Optional[int] = None,
+                      min_track: int = 2, max_track: int = 60, tail: float = 1.3, duplicates: float = 0.0, invalid: float = 0.0,
+                      camera_models: Tuple[str, ...] = ("PINHOLE",), width: int = 640, height: int = 480, shared_camera: bool = False):
+    """A seeded synthetic COLMAP model (mvsformerplusplus_amd.colmap.Model) for tests and measurements.
+
+    Cameras sit on a ring (`layout="ring"`, looking at the origin) or a 2-D grid (`"grid"`, looking down); points lie on a wavy
+    surface around the origin.  Track lengths are heavy-tailed: min_track + floor(Lomax(tail) * 2), clipped to
+    [min_track, min(max_track, n_images)].  A track is a run of consecutive images along the camera order starting at a random
+    image (`window=None`: any start; else the start lies within `window` images of the point's nearest camera; runs wrap
+    around), so far-apart images share nothing; point k < n_images starts at image k.  `duplicates` / `invalid`: fractions of extra observations that repeat one of the image's
+    points / carry point id -1.  Image and point ids are unique but not consecutive; names are not in id order."""
+    import numpy as np
+    from . import colmap
+    g = np.random.default_rng(seed)
+    n, p = int(n_images), int(n_points)
+    # cameras
+    if layout == "ring":
+        a = 2 * np.pi * np.arange(n) / n + g.uniform(-0.2, 0.2, n) * (2 * np.pi / max(n, 1))
+        C = np.stack([6 * np.cos(a), g.uniform(-0.5, 0.5, n), 6 * np.sin(a)], 1)
+        up = np.array([0.0, 1.0, 0.0])
+    elif layout == "grid":
+        side = int(np.ceil(np.sqrt(n)))
+        gx, gy = np.arange(n) % side, np.arange(n) // side
+        C = np.stack([(gx - side / 2) * 0.8, (gy - side / 2) * 0.8, np.full(n, -6.0)], 1) + g.uniform(-0.1, 0.1, (n, 3))
+        up = np.array([0.0, 1.0, 0.0])
+    else:
+        raise ValueError("layout must be 'ring' or 'grid'")
+    target = g.uniform(-0.3, 0.3, (n, 3))
+    if layout == "grid":
+        target[:, :2] += C[:, :2]
+        target[:, 2] = 0.0
+    zax = target - C
+    zax /= np.linalg.norm(zax, axis=1, keepdims=True)
+    xax = np.cross(np.broadcast_to(up, zax.shape), zax)
+    xax /= np.linalg.norm(xax, axis=1, keepdims=True)
+    yax = np.cross(zax, xax)
+    q = _rotmat2qvec(np.stack([xax, yax, zax], 1))
+    R = colmap.qvec2rotmat(q)
+    t = -np.einsum("nij,nj->ni", R, C)
+    # points on a wavy surface
+    u, v = g.uniform(-1, 1, p), g.uniform(-1, 1, p)
+    if layout == "ring":
+        xyz = np.stack([2 * u, 1.5 * v, 0.3 * np.sin(3 * u) * np.cos(2 * v)], 1)
+    else:
+        side = int(np.ceil(np.sqrt(n)))
+        xyz = np.stack([u * side * 0.45, v * side * 0.45, 0.5 * np.sin(2 * u) * np.cos(3 * v)], 1)
+    # tracks: runs of consecutive images
+    L = min_track + np.floor(g.pareto(tail, p) * 2).astype(np.int64)
+    L = np.clip(L, min_track, min(max_track, n))
+    if window is None:
+        start = g.integers(0, n, p)
+    else:
+        near = np.argmin(((xyz[:, None, :] - C[None, :, :]) ** 2).sum(-1), 1) if p * n <= 5e7 else g.integers(0, n, p)
+        start = near + g.integers(-window, window + 1, p)
+    start[:min(n, p)] = np.arange(min(n, p))                       # every image starts one track
+    tptr = np.zeros(p + 1, np.int64)
+    np.cumsum(L, out=tptr[1:])
+    t_pt = np.repeat(np.arange(p), L)
+    t_img = (np.repeat(start, L) + np.arange(tptr[-1]) - np.repeat(tptr[:-1], L)) % n
+    # observations per image: the track entries, plus duplicates and -1 entries, shuffled within each image
+    extra_d = int(round(duplicates * len(t_pt)))
+    if extra_d:
+        k = g.integers(0, len(t_pt), extra_d)
+        t_pt, t_img = np.concatenate([t_pt, t_pt[k]]), np.concatenate([t_img, t_img[k]])
+    pid_dense = t_pt.astype(np.int64)
+    o_img = t_img.astype(np.int64)
+    extra_i = int(round(invalid * len(o_img)))
+    if extra_i:
+        pid_dense = np.concatenate([pid_dense, np.full(extra_i, -1)])
+        o_img = np.concatenate([o_img, g.integers(0, n, extra_i)])
+    order = np.lexsort((g.random(len(o_img)), o_img))
+    o_img, pid_dense = o_img[order], pid_dense[order]
+    counts = np.bincount(o_img, minlength=n)
+    optr = np.zeros(n + 1, np.int64)
+    np.cumsum(counts, out=optr[1:])
+    p2d = np.arange(len(o_img)) - optr[o_img]                    # POINT2D_IDX within its image
+    img_ids = g.permutation(np.arange(1, 3 * n + 1))[:n].astype(np.int64)
+    pt_ids = g.permutation(np.arange(1, 3 * p + 1))[:p].astype(np.int64)
+    names = ["view_%05d.jpg" % k for k in g.permutation(n)]
+    cams, cam_ids = {}, np.zeros(n, np.int64)
+    for k in range(1 if shared_camera else n):
+        mname = camera_models[k % len(camera_models)]
+        spec = colmap.PARAM_TYPE[mname]
+        f = 500.0 + g.uniform(-20, 20)
+        vals = {"f": f, "fx": f, "fy": f * (1 + g.uniform(-0.02, 0.02)), "cx": width / 2 + g.uniform(-5, 5),
+                "cy": height / 2 + g.uniform(-5, 5)}
+        params = np.array([vals.get(s, g.uniform(-0.05, 0.05)) for s in spec], np.float64)
+        cams[k + 1] = colmap.Camera(k + 1, mname, width, height, params)
+    cam_ids[:] = 1 if shared_camera else np.arange(1, n + 1)
+    xys = np.stack([g.uniform(0, width, len(o_img)), g.uniform(0, height, len(o_img))], 1)
+    images = colmap.Images(img_ids, q, t, cam_ids, names, optr, xys, np.where(pid_dense >= 0, pt_ids[np.maximum(pid_dense, 0)], -1))
+    # points3D tracks: every observation of the point (duplicates included), grouped by point
+    valid = np.nonzero(pid_dense >= 0)[0]
+    by_pt = valid[np.argsort(pid_dense[valid], kind="stable")]
+    tl = np.bincount(pid_dense[valid], minlength=p)
+    pptr = np.zeros(p + 1, np.int64)
+    np.cumsum(tl, out=pptr[1:])
+    points = colmap.Points3D(pt_ids, xyz, g.integers(0, 256, (p, 3)).astype(np.uint8), g.uniform(0, 2, p), pptr,
+                             img_ids[o_img[by_pt]].astype(np.int32), p2d[by_pt].astype(np.int32))
+    return colmap.Model(cams, images, points)
