@@ -531,6 +531,27 @@ int mvs_colmap_scores(const int* img_ptr, const int* img_pts, const int* img_mul
                       const double* xyz, const double* centres, double theta0, double den1, double den2, long long max_pairs,
                       uint8_t* flags, unsigned* pairs, void* workspace, size_t workspace_bytes, double* score, void* stream);
 
+/* ==== FPN feature encoder and decoder at full image resolution ========================================
+ * models/module.py:47-86 (Conv2d: conv without bias + BatchNorm2d + leaky_relu 0.1), models/module.py:200-270 (FPNEncoder,
+ * FPNDecoder) with feat_chs = [8, 16, 32, 64] (DINOv2_mvsformer_model.py:34-35, casmvs_model.py:33-34).  All tensors planar fp32,
+ * contiguous [N, C, H, W].  Split-bf16 three-term MFMA contraction (fp32-equivalent); BatchNorm folded on the host.
+ * mvs_fpn_conv_fwd: Conv2d(Cin, Cout, k, stride, padding k/2) + bias [Cout] (nullable) + act (0 none, 1 Swish, 2 LeakyReLU 0.1);
+ *   x [N,Cin,H,W] -> y [N,Cout,(H-1)/stride+1,(W-1)/stride+1]; w_packed = packing.pack_conv_weights_bf16x3(w (Cin padded to a
+ *   multiple of 8)[:, :, None], packing.fpn_chunk(Cin, stride)).  mvs_fpn_conv_is_built lists the (Cin, Cout, k, stride) that exist.
+ * mvs_fpn_merge_fwd (module.py:262-266): intra [N,64,H,W] = up2(prev [N,64,H/2,W/2]) + b_inner + w_inner [64,Clat] . lateral
+ *   [N,Clat,H,W]; up2 = bilinear x2, align_corners=True, source index dst * (in - 1) / (out - 1) in fp32.
+ * mvs_fpn_merge_conv_fwd (module.py:267-268): y = act(conv3x3(intra) + bias) with intra as above computed inside the convolution's
+ *   staging - the 64-channel full-resolution intra is never written.  mvs_fpn_merge_is_built(Clat, 0) = the merge alone,
+ *   (Clat, Cout) = the fused last level.  H and W even.                                                                              */
+int mvs_fpn_conv_is_built(int Cin, int Cout, int k, int stride);
+int mvs_fpn_merge_is_built(int Clat, int Cout);
+int mvs_fpn_conv_fwd(const float* x, const void* w_packed, const float* bias, int act, float* y, int N, int Cin, int Cout, int k, int stride,
+                     int H, int W, void* stream);
+int mvs_fpn_merge_fwd(const float* prev, const float* lateral, const float* w_inner, const float* b_inner, float* intra, int N, int Clat,
+                      int H, int W, void* stream);
+int mvs_fpn_merge_conv_fwd(const float* prev, const float* lateral, const float* w_inner, const float* b_inner, const void* w_packed,
+                           const float* bias, int act, float* y, int N, int Clat, int Cout, int H, int W, void* stream);
+
 /* ---- layout helpers for the nn.Module-level API (NCDHW <-> channel-last) -------------------------*/
 int mvs_ncdhw_to_cl(const float* x, float* y_cl, int B, int C, int D, int H, int W, void* stream);
 int mvs_cl_to_ncdhw(const float* x_cl, float* y, int B, int C, int D, int H, int W, void* stream);

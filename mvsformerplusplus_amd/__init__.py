@@ -13,10 +13,11 @@ from .module import (Conv3d, ConvBnReLU, CostRegNet, CostRegNet2D, CostRegNet3D,
 from . import fusion
 from .ops import PackedFeatures, pack_features
 from .handoff import TiledFeatureHead
+from .features import FPNDecoder, FPNEncoder, patch_fpn
 from .position_encoding import PositionEncoding3D, get_position_3d
 from .warping import diff_homo_warping_3D_with_mask, homo_warping_3D, homo_warping_3D_with_mask
 
 __all__ = ["CascadeDepthHead", "patch_model", "StageNet", "Conv3d", "Deconv3d", "ConvBnReLU", "CostRegNet", "CostRegNet3D", "CostRegNet2D",
-           "PureTransformerCostReg", "get_position_3d", "PositionEncoding3D", "fusion", "PackedFeatures", "pack_features", "TiledFeatureHead",
+           "PureTransformerCostReg", "get_position_3d", "PositionEncoding3D", "fusion", "PackedFeatures", "pack_features", "TiledFeatureHead", "FPNEncoder", "FPNDecoder", "patch_fpn",
            "depth_regression", "conf_regression", "init_range", "init_inverse_range", "schedule_inverse_range", "schedule_range",
            "homo_warping_3D_with_mask", "homo_warping_3D", "diff_homo_warping_3D_with_mask"]

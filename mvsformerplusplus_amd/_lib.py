@@ -119,6 +119,11 @@ SIGNATURES = {
     "mvs_colmap_depths": (_i, [_vp, _vp, C.c_longlong, _vp, _vp, _vp, _vp]),
     "mvs_colmap_scores": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, C.c_double, C.c_double, C.c_double, C.c_longlong]
                           + [_vp] * 3 + [_sz, _vp, _vp]),
+    "mvs_fpn_conv_is_built": (_i, [_i] * 4),
+    "mvs_fpn_merge_is_built": (_i, [_i, _i]),
+    "mvs_fpn_conv_fwd": (_i, [_vp, _vp, _vp, _i, _vp] + [_i] * 7 + [_vp]),
+    "mvs_fpn_merge_fwd": (_i, [_vp] * 5 + [_i] * 4 + [_vp]),
+    "mvs_fpn_merge_conv_fwd": (_i, [_vp] * 6 + [_i, _vp] + [_i] * 5 + [_vp]),
     "mvs_ncdhw_to_cl": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "mvs_cl_to_ncdhw": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
 }

@@ -90,6 +90,58 @@ def conv2d3x3_tiles(x: torch.Tensor, w_packed: torch.Tensor, bias: Optional[torc
     return out
 
 
+FPN_ACT_NONE, FPN_ACT_SWISH, FPN_ACT_LEAKY = 0, 1, 2
+
+
+def fpn_conv_is_built(cin: int, cout: int, k: int, stride: int) -> bool:
+    return bool(lib().mvs_fpn_conv_is_built(int(cin), int(cout), int(k), int(stride)))
+
+
+def fpn_merge_is_built(clat: int, cout: int = 0) -> bool:
+    return bool(lib().mvs_fpn_merge_is_built(int(clat), int(cout)))
+
+
+def _planar32(t: torch.Tensor) -> torch.Tensor:
+    return t.contiguous() if t.dtype == torch.float32 else t.float().contiguous()
+
+
+def fpn_conv(x: torch.Tensor, w_packed: torch.Tensor, bias: Optional[torch.Tensor], cout: int, k: int, stride: int = 1,
+             act: int = FPN_ACT_NONE) -> torch.Tensor:
+    """FPN layer (DESIGN.md section 4.10): x [N,Cin,H,W] -> act(Conv2d(Cin, cout, k, stride, padding k//2)(x) + bias) fp32
+    [N, cout, (H-1)//stride+1, (W-1)//stride+1].  w_packed = packing.pack_fpn_conv_weights(w, stride) (BN folded); act = FPN_ACT_*."""
+    x = _planar32(x)
+    N, cin, H, W = x.shape
+    out = torch.empty(N, cout, (H - 1) // stride + 1, (W - 1) // stride + 1, dtype=torch.float32, device=x.device)
+    check(lib().mvs_fpn_conv_fwd(ptr(x), ptr(w_packed), ptr(bias), int(act), ptr(out), N, cin, int(cout), int(k), int(stride), H, W,
+                                 stream_of(x)), "mvs_fpn_conv_fwd")
+    return out
+
+
+def fpn_merge(prev: torch.Tensor, lateral: torch.Tensor, w_inner: torch.Tensor, b_inner: torch.Tensor) -> torch.Tensor:
+    """FPNDecoder lateral merge (module.py:262-266): up2(prev [N,64,h,w]) + inner(lateral [N,Clat,2h,2w]) -> fp32 [N,64,2h,2w];
+    inner = Conv2d(Clat, 64, 1) given as w_inner [64, Clat] fp32, b_inner [64]; up2 = bilinear x2, align_corners=True."""
+    prev, lateral = _planar32(prev), _planar32(lateral)
+    N, clat, H, W = lateral.shape
+    assert prev.shape == (N, 64, H // 2, W // 2) and H % 2 == 0 and W % 2 == 0, (tuple(prev.shape), tuple(lateral.shape))
+    out = torch.empty(N, 64, H, W, dtype=torch.float32, device=lateral.device)
+    check(lib().mvs_fpn_merge_fwd(ptr(prev), ptr(lateral), ptr(_planar32(w_inner)), ptr(_planar32(b_inner)), ptr(out), N, clat, H, W,
+                                  stream_of(lateral)), "mvs_fpn_merge_fwd")
+    return out
+
+
+def fpn_merge_conv(prev: torch.Tensor, lateral: torch.Tensor, w_inner: torch.Tensor, b_inner: torch.Tensor, w_packed: torch.Tensor,
+                   bias: Optional[torch.Tensor], cout: int, act: int = FPN_ACT_SWISH) -> torch.Tensor:
+    """The decoder's last level fused (module.py:267-268): act(Conv2d(64, cout, 3, padding=1)(fpn_merge(prev, lateral, ...)) + bias)
+    with the merged 64-channel map computed inside the convolution's staging (never written)."""
+    prev, lateral = _planar32(prev), _planar32(lateral)
+    N, clat, H, W = lateral.shape
+    assert prev.shape == (N, 64, H // 2, W // 2) and H % 2 == 0 and W % 2 == 0, (tuple(prev.shape), tuple(lateral.shape))
+    out = torch.empty(N, cout, H, W, dtype=torch.float32, device=lateral.device)
+    check(lib().mvs_fpn_merge_conv_fwd(ptr(prev), ptr(lateral), ptr(_planar32(w_inner)), ptr(_planar32(b_inner)), ptr(w_packed), ptr(bias),
+                                       int(act), ptr(out), N, clat, int(cout), H, W, stream_of(lateral)), "mvs_fpn_merge_conv_fwd")
+    return out
+
+
 def _feat(t) -> Tuple[torch.Tensor, int]:
     if isinstance(t, PackedFeatures):
         return t, _lib.DTYPE_CODE[t.dtype]

@@ -106,6 +106,23 @@ def pack_conv_weights_bf16x3(w: torch.Tensor, ch: int, split=None) -> torch.Tens
     return (split or _split_bf16)(full).permute(1, 2, 3, 0, 4, 5, 6).contiguous().reshape(-1)                           # [pass, step, mb, 2, g, j, e]
 
 
+def fpn_chunk(cin: int, stride: int) -> int:
+    """Input channels staged per LDS pass by ``fpn_conv_kernel`` (csrc/fpn_kernels.hip FpnShape::CH): all of them up to 32 at stride 1,
+    one octet at stride 2 (the 2x wider staged tile).  Cin is first padded to a multiple of 8."""
+    cinp = (cin + 7) // 8 * 8
+    return min(cinp, 32) if stride == 1 else 8
+
+
+def pack_fpn_conv_weights(w: torch.Tensor, stride: int) -> torch.Tensor:
+    """Conv2d weight [Cout, Cin, k, k] (BN folded) -> the bf16x3 packing of ``fpn_conv_kernel``: Cin zero-padded to a multiple of 8,
+    taps (ky*k + kx) enumerated like the 3-D packer's with kd = 1."""
+    cout, cin = w.shape[:2]
+    cinp = (cin + 7) // 8 * 8
+    if cinp != cin:
+        w = torch.cat([w.float(), w.new_zeros(cout, cinp - cin, *w.shape[2:]).float()], 1)
+    return pack_conv_weights_bf16x3(w.float().unsqueeze(2), fpn_chunk(cin, stride))
+
+
 def pack_linear_bf16x3(w: torch.Tensor, split=None) -> torch.Tensor:
     """w [N, K] (y = x @ w.T; N % 16 == 0, K % 32 == 0) -> bf16 1-D tensor for ``tr_gemm_kernel``:
 
