@@ -552,6 +552,36 @@ int mvs_fpn_merge_fwd(const float* prev, const float* lateral, const float* w_in
 int mvs_fpn_merge_conv_fwd(const float* prev, const float* lateral, const float* w_inner, const float* b_inner, const void* w_packed,
                            const float* bias, int act, float* y, int N, int Clat, int Cout, int H, int W, void* stream);
 
+/* ==== FMT_with_pathway: stage-1 linear attention + pathway ============================================
+ * models/FMT.py:35-206 with the shipped FMT_config (Linear attention, d_model 64, 4 heads, ffn, pre-norm, LayerScale).  Token
+ * tensors are the feature maps themselves: planar fp32 [N, 64, n], n = h w.  Split-bf16 three-term MFMA GEMMs (fp32-equivalent);
+ * LayerNorm, elu, the normaliser, GELU (erf) and the residuals in fp32.  w_packed (mvs_fmt_weights_bytes) and vectors
+ * (mvs_fmt_vectors_bytes) of one block come from packing.pack_fmt_block.
+ * mvs_fmt_kv_fwd: key/value summary of kv = LN1(x [+ pe]) per view: k = elu(Wk kv) + 1, v = Wv kv, KV_h = sum_s k_s (x) v_s (exact
+ *   fp32 products), ksum_h = sum_s k_s -> kv_operand [N] of mvs_fmt_kv_operand_bytes each (a packed split-bf16 GEMM operand).
+ *   Per-workgroup partials in `workspace` (mvs_fmt_kv_workspace_bytes(N, n); 0 = out of range) are added in a fixed order: no
+ *   atomics, bit-identical run to run.  pe (nullable) [64, n] is added to x first.
+ * mvs_fmt_block_fwd: y = block(x [+ pe]) for N views; view i attends to kv_operand[i / kv_div] (self attention: its own, kv_div 1;
+ *   cross attention: the reference view's of its batch element, kv_div = V - 1).  One launch; q, the attention output and the 256-wide
+ *   hidden activation stay in registers.
+ * mvs_fmt_path_fwd: y [N,C,H,W] = conv3x3(bilinear(w_reduce [C,2C] . prev [N,2C,h,w], size (H,W), align_corners=False) + lateral
+ *   [N,C,H,W]), zero padding, no biases, C = 32 | 16 | 8, any h, w, H, W >= 1; the merged map is computed inside the convolution's
+ *   staging and never written.  w_packed = packing.pack_fpn_conv_weights(w, 1).
+ * mvs_fmt_merge_fwd + mvs_fmt_smooth_fwd: the same level unfused (the merged map written, then the convolution alone).            */
+size_t mvs_fmt_weights_bytes(void);
+size_t mvs_fmt_vectors_bytes(void);
+size_t mvs_fmt_kv_operand_bytes(void);
+size_t mvs_fmt_kv_workspace_bytes(int N, int n);
+int mvs_fmt_kv_fwd(const float* x, const float* pe, const void* w_packed, const float* vectors, void* workspace, size_t workspace_bytes,
+                   void* kv_operand, int N, int n, void* stream);
+int mvs_fmt_block_fwd(const float* x, const float* pe, const void* kv_operand, const void* w_packed, const float* vectors, float* y, int N,
+                      int n, int kv_div, void* stream);
+int mvs_fmt_path_fwd(const float* prev, const float* lateral, const float* w_reduce, const void* w_packed, float* y, int N, int C, int h, int w,
+                     int H, int W, void* stream);
+int mvs_fmt_merge_fwd(const float* prev, const float* lateral, const float* w_reduce, float* merged, int N, int C, int h, int w, int H, int W,
+                      void* stream);
+int mvs_fmt_smooth_fwd(const float* x, const void* w_packed, float* y, int N, int C, int H, int W, void* stream);
+
 /* ---- layout helpers for the nn.Module-level API (NCDHW <-> channel-last) -------------------------*/
 int mvs_ncdhw_to_cl(const float* x, float* y_cl, int B, int C, int D, int H, int W, void* stream);
 int mvs_cl_to_ncdhw(const float* x_cl, float* y, int B, int C, int D, int H, int W, void* stream);

@@ -124,6 +124,15 @@ SIGNATURES = {
     "mvs_fpn_conv_fwd": (_i, [_vp, _vp, _vp, _i, _vp] + [_i] * 7 + [_vp]),
     "mvs_fpn_merge_fwd": (_i, [_vp] * 5 + [_i] * 4 + [_vp]),
     "mvs_fpn_merge_conv_fwd": (_i, [_vp] * 6 + [_i, _vp] + [_i] * 5 + [_vp]),
+    "mvs_fmt_weights_bytes": (_sz, []),
+    "mvs_fmt_vectors_bytes": (_sz, []),
+    "mvs_fmt_kv_operand_bytes": (_sz, []),
+    "mvs_fmt_kv_workspace_bytes": (_sz, [_i, _i]),
+    "mvs_fmt_kv_fwd": (_i, [_vp] * 5 + [_sz, _vp, _i, _i, _vp]),
+    "mvs_fmt_block_fwd": (_i, [_vp] * 6 + [_i, _i, _i, _vp]),
+    "mvs_fmt_path_fwd": (_i, [_vp] * 5 + [_i] * 6 + [_vp]),
+    "mvs_fmt_merge_fwd": (_i, [_vp] * 4 + [_i] * 6 + [_vp]),
+    "mvs_fmt_smooth_fwd": (_i, [_vp] * 3 + [_i] * 4 + [_vp]),
     "mvs_ncdhw_to_cl": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "mvs_cl_to_ncdhw": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
 }

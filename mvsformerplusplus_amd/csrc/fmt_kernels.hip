@@ -1,0 +1,646 @@
+// FMT_with_pathway: the stage-1 linear-attention transformer and the three-level pathway of the shipped
+// network, fp32-equivalent.
+//
+// Reference (restated, never copied): models/FMT.py:35-206 (FMT, FMT_with_pathway), models/dino/layers/block.py (CrossBlock, pre-norm,
+// LayerScale), models/dino/layers/attention.py (CrossLinearAttention: q = elu(Wq x) + 1, k = elu(Wk kv) + 1, v = Wv kv,
+// KV_h = sum_s k_s (x) v_s, a = (q . KV_h) / (q . sum_s k_s + 1e-6)), models/dino/layers/mlp.py (fc1, GELU (erf), fc2).
+//
+// Layout.  Tokens stay PLANAR: a token tensor is [N, 64, n] fp32 (n = h w), i.e. the feature map itself, so there is no transpose on
+// the way in or out.  Every GEMM puts the tokens on the MFMA's column (or row) index = the lane: lane (li = lane & 15, g = lane >> 4)
+// of a wave owns token t0 + 16 nb + li (nb < FT_NREP) and, in the ACCUMULATOR LAYOUT, its channels 16 mb + 4 g + k (mb = 16-channel
+// block, k < 4).  A v_mfma_f32_16x16x32_bf16 result (rows = output channels, columns = tokens) is already in that layout, and it is the
+// next GEMM's B operand with no data movement: the 8 elements of k-step s are the registers of blocks 2s and 2s+1, i.e. k-slot
+// (s, g, e) holds channel 32 s + 16 (e >> 2) + 4 g + (e & 3).  The weights are packed with the same permutation of their input
+// channels (packing.pack_fmt_linear), so a whole block - LayerNorm, q, the per-head apply, proj, LayerNorm, fc1, GELU, fc2, both
+// residuals - runs in registers; neither q, a nor the 256-wide hidden activation touches LDS or HBM.  Every product is the three-term
+// split-bf16 one (hi*hi + hi*lo + lo*hi, fp32 accumulate); LayerNorm statistics, elu, the normaliser, GELU and the residuals are fp32.
+//
+// Kernels:
+//   1. fmt_kv_partial_kernel + fmt_kv_reduce_kernel: LN1 -> k, v (tokens on the MFMA ROW index, so that a lane group holds four
+//      tokens of one channel) -> KV_h += k^T v over the tokens on the exact-fp32 v_mfma_f32_16x16x4_f32; per-workgroup partials, added in a
+//      fixed order by the second launch (no atomics: bit-identical run to run), which also writes the result as a packed split-bf16
+//      operand: a [80 x 64] matrix = block-diagonal KV_h^T plus four rows of sum_s k_s per lane group, so that the apply and the
+//      normaliser are one more GEMM of the block kernel.
+//   2. fmt_block_kernel: one CrossBlock for 32 tokens per wave; packed weights stream from L2 in lane order (164 KB for the four
+//      matrices + the 20 KB key/value operand exceed the LDS; each wave reads them once per 32 tokens).
+//   3. fmt_path_kernel<C>: smooth_k(bilinear(dim_reduction_k(prev)) + lateral), an implicit-GEMM 3x3 in the form of fpn_conv_kernel
+//      whose staging evaluates the merged map for the tile and its halo (align_corners=False, any size ratio, no biases); the merged
+//      map is never written.  fmt_merge_kernel + the same convolution on a planar source are the unfused form.
+// Staged positions are clamped to the image explicitly (zero padding from a branch, never from an out-of-range load).
+#include "mvs_common.h"
+#include "split_format.h"
+
+namespace mvs {
+
+constexpr int FT_NREP = 2;                    // 16-token column blocks per wave
+constexpr int FT_TOK = 16 * FT_NREP;          // tokens per wave
+// packed weights, in bf16x8 (16-byte) units: linear [step][mb][hi|lo][64 lanes] (packing.pack_fmt_block)
+constexpr int FT_W_Q = 0, FT_W_P = 1024, FT_W_1 = 2048, FT_W_2 = 6144, FT_W_KV = 10240, FT_W_END = 12288;
+// fp32 vectors (packing.pack_fmt_block)
+constexpr int FT_V_LN1W = 0, FT_V_LN1B = 64, FT_V_BP = 128, FT_V_G1 = 192, FT_V_LN2W = 256, FT_V_LN2B = 320, FT_V_B1 = 384, FT_V_B2 = 640,
+              FT_V_G2 = 704, FT_V_END = 768;
+constexpr int FT_KVOP = 2 * 5 * 2 * 64;       // bf16x8 units of one key/value operand ([2 steps][5 row blocks][hi|lo][64 lanes])
+constexpr int FT_PART = 1280;                 // floats of one partial: KV [4][16][16] | per-lane-group sums of k [4][4][16]
+constexpr int FT_MAX_SLABS = 64;      // partials per view: the second launch adds them one after the other (a dependent load each)
+
+__device__ __forceinline__ void ft_operand(const f32x4& a, const f32x4& b, bf16x8& hi, bf16x8& lo) {
+    split8(make_float4(a[0], a[1], a[2], a[3]), make_float4(b[0], b[1], b[2], b[3]), hi, lo);
+}
+
+// the wave's tokens in the accumulator layout (+ the position encoding table [64, n]); tokens past the end read as zero
+__device__ __forceinline__ void ft_load(const float* __restrict__ xn, const float* __restrict__ pe, int ntok, int t0, int li, int g,
+                                        f32x4 (&x)[4][FT_NREP]) {
+#pragma unroll
+    for (int nb = 0; nb < FT_NREP; ++nb) {
+        const int tok = t0 + nb * 16 + li;
+        const bool ok = tok < ntok;
+#pragma unroll
+        for (int mb = 0; mb < 4; ++mb)
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const size_t o = (size_t)(16 * mb + 4 * g + k) * ntok + tok;
+                float v = 0.0f;
+                if (ok) {
+                    v = xn[o];
+                    if (pe) v += pe[o];
+                }
+                x[mb][nb][k] = v;
+            }
+    }
+}
+
+// LayerNorm(64, eps 1e-5) of every token (its 64 channels sit in the four lanes li, li + 16, li + 32, li + 48) -> split operands
+__device__ __forceinline__ void ft_layernorm(const f32x4 (&x)[4][FT_NREP], const float* __restrict__ w, const float* __restrict__ b, int g,
+                                             bf16x8 (&oh)[2][FT_NREP], bf16x8 (&ol)[2][FT_NREP]) {
+    float4 wv[4], bv[4];
+#pragma unroll
+    for (int mb = 0; mb < 4; ++mb) {
+        wv[mb] = *reinterpret_cast<const float4*>(w + 16 * mb + 4 * g);
+        bv[mb] = *reinterpret_cast<const float4*>(b + 16 * mb + 4 * g);
+    }
+#pragma unroll
+    for (int nb = 0; nb < FT_NREP; ++nb) {
+        float s = 0.0f;
+#pragma unroll
+        for (int mb = 0; mb < 4; ++mb) s += (x[mb][nb][0] + x[mb][nb][1]) + (x[mb][nb][2] + x[mb][nb][3]);
+        s += __shfl_xor(s, 16);
+        s += __shfl_xor(s, 32);
+        const float mean = s * (1.0f / 64.0f);
+        float q = 0.0f;
+#pragma unroll
+        for (int mb = 0; mb < 4; ++mb)
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const float d = x[mb][nb][k] - mean;
+                q = fmaf(d, d, q);
+            }
+        q += __shfl_xor(q, 16);
+        q += __shfl_xor(q, 32);
+        const float rstd = 1.0f / sqrtf(q * (1.0f / 64.0f) + 1e-5f);
+        f32x4 y[4];
+#pragma unroll
+        for (int mb = 0; mb < 4; ++mb) {
+            const float ww[4] = {wv[mb].x, wv[mb].y, wv[mb].z, wv[mb].w}, bb[4] = {bv[mb].x, bv[mb].y, bv[mb].z, bv[mb].w};
+#pragma unroll
+            for (int k = 0; k < 4; ++k) y[mb][k] = fmaf((x[mb][nb][k] - mean) * rstd, ww[k], bb[k]);
+        }
+        ft_operand(y[0], y[1], oh[0][nb], ol[0][nb]);
+        ft_operand(y[2], y[3], oh[1][nb], ol[1][nb]);
+    }
+}
+
+// acc[mb][nb] += W[rows 16 (mb0 + mb) ..][k-steps s0 .. s0 + NSTEP) . operand; wl = packed linear + lane, MTOT = its row blocks
+template <int MREP, int NSTEP, int MTOT>
+__device__ __forceinline__ void ft_gemm(const bf16x8* __restrict__ wl, int s0, int mb0, const bf16x8 (&bh)[NSTEP][FT_NREP],
+                                        const bf16x8 (&bl)[NSTEP][FT_NREP], f32x4 (&acc)[MREP][FT_NREP]) {
+#pragma unroll
+    for (int s = 0; s < NSTEP; ++s)
+#pragma unroll
+        for (int mb = 0; mb < MREP; ++mb) {
+            const bf16x8 ah = wl[(size_t)((((s0 + s) * MTOT + mb0 + mb) * 2 + 0) * 64)];
+            const bf16x8 al = wl[(size_t)((((s0 + s) * MTOT + mb0 + mb) * 2 + 1) * 64)];
+#pragma unroll
+            for (int nb = 0; nb < FT_NREP; ++nb) {
+                acc[mb][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bh[s][nb], acc[mb][nb], 0, 0, 0);
+                acc[mb][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bl[s][nb], acc[mb][nb], 0, 0, 0);
+                acc[mb][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bh[s][nb], acc[mb][nb], 0, 0, 0);
+            }
+        }
+}
+
+template <int MREP>
+__device__ __forceinline__ void ft_zero(f32x4 (&acc)[MREP][FT_NREP]) {
+#pragma unroll
+    for (int mb = 0; mb < MREP; ++mb)
+#pragma unroll
+        for (int nb = 0; nb < FT_NREP; ++nb) acc[mb][nb] = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
+}
+
+__device__ __forceinline__ float ft_elu1(float t) { return t > 0.0f ? t + 1.0f : expf(t); }                      // elu(t) + 1
+__device__ __forceinline__ float ft_gelu(float t) { return 0.5f * t * (1.0f + erff(t * 0.70710678118654752440f)); }
+
+struct FmtBlockArgs {
+    const float* x;          // [N, 64, n]
+    const float* pe;         // [64, n] added to x first (nullable)
+    const bf16x8* kvop;      // [N / kv_div] key/value operands
+    const bf16x8* w;         // packed weights
+    const float* vec;        // LayerNorm / bias / layer-scale vectors
+    float* out;              // [N, 64, n]
+    int ntok, kv_div;
+};
+
+__global__ __launch_bounds__(256) void fmt_block_kernel(FmtBlockArgs a) {
+    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, g = lane >> 4;
+    const int n = (int)blockIdx.y, ntok = a.ntok;
+    const int t0 = ((int)blockIdx.x * 4 + wave) * FT_TOK;
+    if (t0 >= ntok) return;                                       // wave-uniform; the kernel has no workgroup barrier
+    const bf16x8* wl = a.w + lane;
+    const float* vec = a.vec;
+
+    f32x4 x[4][FT_NREP];
+    ft_load(a.x + (size_t)n * 64 * ntok, a.pe, ntok, t0, li, g, x);
+    bf16x8 bh[2][FT_NREP], bl[2][FT_NREP];
+    f32x4 acc[4][FT_NREP];
+
+    // ---- attention: q = elu(Wq LN1(x)) + 1 ----
+    ft_layernorm(x, vec + FT_V_LN1W, vec + FT_V_LN1B, g, bh, bl);
+    ft_zero<4>(acc);
+    ft_gemm<4, 2, 4>(wl + FT_W_Q, 0, 0, bh, bl, acc);
+#pragma unroll
+    for (int nb = 0; nb < FT_NREP; ++nb) {
+#pragma unroll
+        for (int mb = 0; mb < 4; ++mb)
+#pragma unroll
+            for (int k = 0; k < 4; ++k) acc[mb][nb][k] = ft_elu1(acc[mb][nb][k]);
+        ft_operand(acc[0][nb], acc[1][nb], bh[0][nb], bl[0][nb]);
+        ft_operand(acc[2][nb], acc[3][nb], bh[1][nb], bl[1][nb]);
+    }
+    // ---- a = (q . KV_h) / (q . ksum_h + 1e-6): rows 0..63 of the operand are the heads' KV_h^T, row 64 + 4 g' + h is ksum_h ----
+    {
+        f32x4 ap[5][FT_NREP];
+        ft_zero<5>(ap);
+        ft_gemm<5, 2, 5>(a.kvop + (size_t)(n / a.kv_div) * FT_KVOP + lane, 0, 0, bh, bl, ap);
+#pragma unroll
+        for (int nb = 0; nb < FT_NREP; ++nb) {
+#pragma unroll
+            for (int mb = 0; mb < 4; ++mb) {
+                const float den = ap[4][nb][mb] + 1e-6f;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) ap[mb][nb][k] = ap[mb][nb][k] / den;
+            }
+            ft_operand(ap[0][nb], ap[1][nb], bh[0][nb], bl[0][nb]);
+            ft_operand(ap[2][nb], ap[3][nb], bh[1][nb], bl[1][nb]);
+        }
+    }
+    // ---- x += ls1 * (Wp a + bp) ----
+    ft_zero<4>(acc);
+    ft_gemm<4, 2, 4>(wl + FT_W_P, 0, 0, bh, bl, acc);
+#pragma unroll
+    for (int mb = 0; mb < 4; ++mb) {
+        const float4 bp = *reinterpret_cast<const float4*>(vec + FT_V_BP + 16 * mb + 4 * g);
+        const float4 g1 = *reinterpret_cast<const float4*>(vec + FT_V_G1 + 16 * mb + 4 * g);
+        const float bb[4] = {bp.x, bp.y, bp.z, bp.w}, gg[4] = {g1.x, g1.y, g1.z, g1.w};
+#pragma unroll
+        for (int nb = 0; nb < FT_NREP; ++nb)
+#pragma unroll
+            for (int k = 0; k < 4; ++k) x[mb][nb][k] = fmaf(gg[k], acc[mb][nb][k] + bb[k], x[mb][nb][k]);
+    }
+    // ---- x += ls2 * (W2 gelu(W1 LN2(x) + b1) + b2): 64 hidden channels at a time, each chunk is two k-steps of fc2 ----
+    ft_layernorm(x, vec + FT_V_LN2W, vec + FT_V_LN2B, g, bh, bl);
+    ft_zero<4>(acc);
+#pragma unroll 1
+    for (int c = 0; c < 4; ++c) {
+        f32x4 hd[4][FT_NREP];
+        bf16x8 hh[2][FT_NREP], hl[2][FT_NREP];
+        ft_zero<4>(hd);
+        ft_gemm<4, 2, 16>(wl + FT_W_1, 0, 4 * c, bh, bl, hd);
+#pragma unroll
+        for (int mb = 0; mb < 4; ++mb) {
+            const float4 b1 = *reinterpret_cast<const float4*>(vec + FT_V_B1 + 64 * c + 16 * mb + 4 * g);
+            const float bb[4] = {b1.x, b1.y, b1.z, b1.w};
+#pragma unroll
+            for (int nb = 0; nb < FT_NREP; ++nb)
+#pragma unroll
+                for (int k = 0; k < 4; ++k) hd[mb][nb][k] = ft_gelu(hd[mb][nb][k] + bb[k]);
+        }
+#pragma unroll
+        for (int nb = 0; nb < FT_NREP; ++nb) {
+            ft_operand(hd[0][nb], hd[1][nb], hh[0][nb], hl[0][nb]);
+            ft_operand(hd[2][nb], hd[3][nb], hh[1][nb], hl[1][nb]);
+        }
+        ft_gemm<4, 2, 4>(wl + FT_W_2, 2 * c, 0, hh, hl, acc);
+    }
+    float* on = a.out + (size_t)n * 64 * ntok;
+#pragma unroll
+    for (int mb = 0; mb < 4; ++mb) {
+        const float4 b2 = *reinterpret_cast<const float4*>(vec + FT_V_B2 + 16 * mb + 4 * g);
+        const float4 g2 = *reinterpret_cast<const float4*>(vec + FT_V_G2 + 16 * mb + 4 * g);
+        const float bb[4] = {b2.x, b2.y, b2.z, b2.w}, gg[4] = {g2.x, g2.y, g2.z, g2.w};
+#pragma unroll
+        for (int nb = 0; nb < FT_NREP; ++nb) {
+            const int tok = t0 + nb * 16 + li;
+            if (tok >= ntok) continue;
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                on[(size_t)(16 * mb + 4 * g + k) * ntok + tok] = fmaf(gg[k], acc[mb][nb][k] + bb[k], x[mb][nb][k]);
+        }
+    }
+}
+
+// Key/value summary, first launch: workgroup `slab` of view n takes the 32-token tiles slab * 4 + wave + i * (4 * slabs) and writes
+// part[n][slab] = its four waves' sums, added in wave order.
+__global__ __launch_bounds__(256) void fmt_kv_partial_kernel(const float* __restrict__ x, const float* __restrict__ pe, const bf16x8* __restrict__ w,
+                                                             const float* __restrict__ vec, float* __restrict__ part, int ntok, int ntile) {
+    HIP_DYNAMIC_SHARED(float4, lds4)
+    float* lds = reinterpret_cast<float*>(lds4);                  // [4 waves][FT_PART]
+    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, g = lane >> 4;
+    const int n = (int)blockIdx.y, nslot = (int)gridDim.x * 4;
+    const bf16x8* wl = w + FT_W_KV + lane;
+    f32x4 kv[4];
+    float ks[4];
+#pragma unroll
+    for (int h = 0; h < 4; ++h) {
+        kv[h] = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
+        ks[h] = 0.0f;
+    }
+#pragma unroll 1
+    for (int tile = (int)blockIdx.x * 4 + wave; tile < ntile; tile += nslot) {
+        const int t0 = tile * FT_TOK;
+        f32x4 xx[4][FT_NREP];
+        ft_load(x + (size_t)n * 64 * ntok, pe, ntok, t0, li, g, xx);
+        bf16x8 th[2][FT_NREP], tl[2][FT_NREP];
+        ft_layernorm(xx, vec + FT_V_LN1W, vec + FT_V_LN1B, g, th, tl);
+        // tokens on the row index: lane (li, g) gets [token 4 g + kk of block nb][output channel 16 cb + li]; cb < 4 = k, else v
+        f32x4 kacc[4][FT_NREP], vacc[4][FT_NREP];
+        ft_zero<4>(kacc);
+        ft_zero<4>(vacc);
+#pragma unroll
+        for (int s = 0; s < 2; ++s)
+#pragma unroll
+            for (int cb = 0; cb < 8; ++cb) {
+                const bf16x8 wh = wl[(size_t)(((s * 8 + cb) * 2 + 0) * 64)];
+                const bf16x8 wo = wl[(size_t)(((s * 8 + cb) * 2 + 1) * 64)];
+#pragma unroll
+                for (int nb = 0; nb < FT_NREP; ++nb) {
+                    f32x4& d = cb < 4 ? kacc[cb & 3][nb] : vacc[cb & 3][nb];
+                    d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(tl[s][nb], wh, d, 0, 0, 0);
+                    d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(th[s][nb], wo, d, 0, 0, 0);
+                    d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(th[s][nb], wh, d, 0, 0, 0);
+                }
+            }
+        // KV_h[d][m] += sum over four tokens (one per lane group) of k[token][d] v[token][m], exact fp32 products
+#pragma unroll
+        for (int nb = 0; nb < FT_NREP; ++nb)
+#pragma unroll
+            for (int kk = 0; kk < 4; ++kk) {
+                const bool ok = t0 + nb * 16 + 4 * g + kk < ntok;
+#pragma unroll
+                for (int h = 0; h < 4; ++h) {
+                    const float kval = ok ? ft_elu1(kacc[h][nb][kk]) : 0.0f;
+                    ks[h] += kval;
+                    kv[h] = __builtin_amdgcn_mfma_f32_16x16x4f32(kval, vacc[h][nb][kk], kv[h], 0, 0, 0);
+                }
+            }
+    }
+    // lane (li = m, g) holds KV_h[d = 4 g + r][m] and the sum of k_h[.][d = li] over its lane group's tokens
+    float* mine = lds + wave * FT_PART;
+#pragma unroll
+    for (int h = 0; h < 4; ++h) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) mine[h * 256 + (4 * g + r) * 16 + li] = kv[h][r];
+        mine[1024 + (h * 4 + g) * 16 + li] = ks[h];
+    }
+    __syncthreads();
+    float* dst = part + ((size_t)n * gridDim.x + blockIdx.x) * FT_PART;
+    for (int e = tid; e < FT_PART; e += 256) dst[e] = ((lds[e] + lds[FT_PART + e]) + lds[2 * FT_PART + e]) + lds[3 * FT_PART + e];
+}
+
+// Second launch: block (mb, n) adds the slabs' partials of row block mb in slab order and writes that row block's 64-lane hi | lo pairs
+// of both k-steps of the operand: M[16 mb + j][col] = KV_mb[col & 15][j] where col >> 4 == mb (mb < 4); M[64 + j][col] = ksum_{col >> 4}[col & 15] where
+// (j & 3) == col >> 4; k-slot (step, g, e) = column 32 step + 16 (e >> 2) + 4 g + (e & 3).
+__global__ __launch_bounds__(256) void fmt_kv_reduce_kernel(const float* __restrict__ part, bf16x8* __restrict__ kvop, int nslab) {
+    HIP_DYNAMIC_SHARED(float4, lds4)
+    float* lds = reinterpret_cast<float*>(lds4);                  // [256]
+    const int tid = (int)threadIdx.x, mb = (int)blockIdx.x, n = (int)blockIdx.y;
+    const float* p = part + (size_t)n * nslab * FT_PART;
+    float sum = 0.0f;
+    if (mb < 4) {
+        for (int sl = 0; sl < nslab; ++sl) sum += p[(size_t)sl * FT_PART + mb * 256 + tid];                      // [d][m]
+    } else if (tid < 64) {
+        const int hc = tid >> 4, d = tid & 15;
+        for (int sl = 0; sl < nslab; ++sl)
+            for (int gg = 0; gg < 4; ++gg) sum += p[(size_t)sl * FT_PART + 1024 + (hc * 4 + gg) * 16 + d];      // [head][d]
+    }
+    lds[tid] = sum;
+    __syncthreads();
+    if (tid >= 128) return;
+    const int s = tid >> 6, lane = tid & 63, j = lane & 15, g = lane >> 4;
+    float v[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const int col = 32 * s + 16 * (e >> 2) + 4 * g + (e & 3), hc = col >> 4, d = col & 15;
+        if (mb < 4) v[e] = hc == mb ? lds[d * 16 + j] : 0.0f;
+        else v[e] = (j & 3) == hc ? lds[hc * 16 + d] : 0.0f;
+    }
+    bf16x8 hi, lo;
+    split8(make_float4(v[0], v[1], v[2], v[3]), make_float4(v[4], v[5], v[6], v[7]), hi, lo);
+    bf16x8* o = kvop + (size_t)n * FT_KVOP + (size_t)(s * 5 + mb) * 2 * 64 + lane;
+    o[0] = hi;
+    o[64] = lo;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// pathway: smooth_k(bilinear(dim_reduction_k(prev), size of lateral, align_corners=False) + lateral)
+// ---------------------------------------------------------------------------------------------------------------------------------
+constexpr int FT_TH = 4, FT_TW = 64;
+
+template <int C>
+struct FtPlanarSrc {
+    const float* x;
+    int H, W;
+    const float* p;
+    __device__ __forceinline__ void at(int n, int gy, int gx) { p = x + ((size_t)n * C * H + gy) * W + gx; }
+    __device__ __forceinline__ void load8(int c0, float* v) const {
+        const size_t hw = (size_t)H * W;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) v[k] = p[(size_t)(c0 + k) * hw];
+    }
+};
+
+// merged[c] at a pixel of the lateral = lateral[c] + sum_ci w[c][ci] * bilinear(prev[ci]); prev [N, 2C, h, w], lateral [N, C, H, W].
+// The 1x1 and the interpolation are both linear and bias-free: the 2C coarse channels are interpolated once per pixel, then reduced.
+template <int C>
+struct FtMergeSrc {
+    static constexpr int CP = 2 * C;
+    const float* prev;
+    const float* lat;
+    const float* wr;         // dim_reduction weight [C][2C]
+    int H, W, h, w;
+    float sy, sx;            // (float)h / H, (float)w / W as F.interpolate(size=...) computes them
+    float p[CP];
+    const float* lp;
+    __device__ __forceinline__ void at(int n, int gy, int gx) {
+        lp = lat + ((size_t)n * C * H + gy) * W + gx;
+        const float fy = fmaxf(((float)gy + 0.5f) * sy - 0.5f, 0.0f), fx = fmaxf(((float)gx + 0.5f) * sx - 0.5f, 0.0f);
+        const int yi = (int)fy, xi = (int)fx;
+        const int y0 = yi < h - 1 ? yi : h - 1, x0 = xi < w - 1 ? xi : w - 1;
+        const float ly = fminf(fy - (float)y0, 1.0f), lx = fminf(fx - (float)x0, 1.0f);
+        const int dy = y0 < h - 1 ? w : 0, dx = x0 < w - 1 ? 1 : 0;
+        const float* q = prev + (size_t)n * CP * h * w + (size_t)y0 * w + x0;
+        const size_t hw = (size_t)h * w;
+#pragma unroll
+        for (int ci = 0; ci < CP; ++ci) {
+            const float* qc = q + (size_t)ci * hw;
+            p[ci] = (1.0f - ly) * ((1.0f - lx) * qc[0] + lx * qc[dx]) + ly * ((1.0f - lx) * qc[dy] + lx * qc[dy + dx]);
+        }
+    }
+    __device__ __forceinline__ void load8(int c0, float* v) const {
+        const size_t HW = (size_t)H * W;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            float s = 0.0f;
+#pragma unroll
+            for (int ci = 0; ci < CP; ++ci) s = fmaf(wr[(c0 + k) * CP + ci], p[ci], s);
+            v[k] = s + lp[(size_t)(c0 + k) * HW];
+        }
+    }
+};
+
+template <int C>
+struct FtShape {
+    static constexpr int OPT = C / 8, NOCT = 9 * OPT, NSTEP = (NOCT + 3) / 4, MREP = (C + 15) / 16, NREP = FT_TW / 16;
+    static constexpr int IH = FT_TH + 2, IW = FT_TW + 2, NPIX = IH * IW;
+    static constexpr int PLANE = NPIX * 32 + 32;                  // bytes of one octet plane (+ one slot: bank rows differ)
+    static constexpr size_t LDS = (size_t)OPT * PLANE;
+};
+
+// Conv2d(C, C, 3, padding=1, bias=False) on Src; weights = packing.pack_fpn_conv_weights(w, 1) (one pass: C <= 32).  A workgroup owns
+// 4 output rows x 64 columns (one row per wave); the contraction is fpn_conv_kernel's.
+template <int C, class Src>
+__global__ __launch_bounds__(256) void fmt_path_kernel(Src src, const void* __restrict__ wp, float* __restrict__ out, int H, int W, int tiles_x,
+                                                       int ntiles) {
+    typedef FtShape<C> F;
+    constexpr int OPT = F::OPT, NOCT = F::NOCT, NSTEP = F::NSTEP, IW = F::IW, NPIX = F::NPIX, MREP = F::MREP, NREP = F::NREP;
+    HIP_DYNAMIC_SHARED(float4, lds4)
+    char* ldsb = reinterpret_cast<char*>(lds4);
+    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, g = lane >> 4;
+    const int tile = (int)xcd_remap(blockIdx.x, (unsigned)ntiles), n = (int)blockIdx.y;
+    const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
+    const int y0 = ty * FT_TH, x0 = tx * FT_TW;
+
+    // ---- stage: one work-item = one staged pixel, every channel octet; outside the image = zero padding from a branch ----
+    for (int pix = tid; pix < NPIX; pix += 256) {
+        const int iy = pix / IW, ix = pix - iy * IW;
+        const int gy = y0 - 1 + iy, gx = x0 - 1 + ix;
+        const bool inside = gy >= 0 && gy < H && gx >= 0 && gx < W;
+        Src s = src;
+        if (inside) s.at(n, gy, gx);
+#pragma unroll
+        for (int oc = 0; oc < OPT; ++oc) {
+            float v[8];
+            if (inside) {
+                s.load8(oc * 8, v);
+            } else {
+#pragma unroll
+                for (int k = 0; k < 8; ++k) v[k] = 0.0f;
+            }
+            bf16x8 hi, lo;
+            split8(make_float4(v[0], v[1], v[2], v[3]), make_float4(v[4], v[5], v[6], v[7]), hi, lo);
+            char* dst = ldsb + oc * F::PLANE + pix * 32;
+            *reinterpret_cast<bf16x8*>(dst) = hi;
+            *reinterpret_cast<bf16x8*>(dst + 16) = lo;
+        }
+    }
+    __syncthreads();
+
+    f32x4 acc[MREP][NREP];
+#pragma unroll
+    for (int mb = 0; mb < MREP; ++mb)
+#pragma unroll
+        for (int nb = 0; nb < NREP; ++nb) acc[mb][nb] = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
+    // ---- contract: step = four channel octets (one per lane group), octet q = 4 step + g -> (tap, oc) = divmod(q, OPT) ----
+    const bf16x8* wq = reinterpret_cast<const bf16x8*>(wp) + lane;
+#pragma unroll
+    for (int step = 0; step < NSTEP; ++step) {
+        const int q = 4 * step + g;
+        const bool live = q < NOCT;                               // the last step may run past the 9 x OPT octets: zero operand
+        const int tap = live ? q / OPT : 0, oc = live ? q - tap * OPT : 0;
+        const int ky = tap / 3, kx = tap - ky * 3;
+        const char* srcp = ldsb + oc * F::PLANE + ((wave + ky) * IW + li + kx) * 32;
+        bf16x8 ah[MREP], al[MREP], bh[NREP], bl[NREP];
+#pragma unroll
+        for (int mb = 0; mb < MREP; ++mb) {
+            ah[mb] = wq[(size_t)((step * MREP + mb) * 2 + 0) * 64];
+            al[mb] = wq[(size_t)((step * MREP + mb) * 2 + 1) * 64];
+        }
+#pragma unroll
+        for (int nb = 0; nb < NREP; ++nb) {
+            bf16x8 hv = *reinterpret_cast<const bf16x8*>(srcp + nb * 16 * 32);
+            bf16x8 lv = *reinterpret_cast<const bf16x8*>(srcp + nb * 16 * 32 + 16);
+            if (!live) {
+#pragma unroll
+                for (int k = 0; k < 8; ++k) { hv[k] = (__bf16)0.0f; lv[k] = (__bf16)0.0f; }
+            }
+            bh[nb] = hv;
+            bl[nb] = lv;
+        }
+#pragma unroll
+        for (int mb = 0; mb < MREP; ++mb)
+#pragma unroll
+            for (int nb = 0; nb < NREP; ++nb) {
+                acc[mb][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[mb], bh[nb], acc[mb][nb], 0, 0, 0);
+                acc[mb][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[mb], bl[nb], acc[mb][nb], 0, 0, 0);
+                acc[mb][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[mb], bh[nb], acc[mb][nb], 0, 0, 0);
+            }
+    }
+    // ---- epilogue: lane (pixel li, group g) holds output channels 16 mb + 4 g .. + 3 of its pixel; planar fp32 stores ----
+    const int y = y0 + wave;
+    if (y >= H) return;
+    const size_t hw = (size_t)H * W;
+    float* ob = out + (size_t)n * C * hw + (size_t)y * W;
+#pragma unroll
+    for (int nb = 0; nb < NREP; ++nb) {
+        const int xx = x0 + nb * 16 + li;
+        if (xx >= W) continue;
+#pragma unroll
+        for (int mb = 0; mb < MREP; ++mb) {
+            const int co = 16 * mb + 4 * g;
+            if (co >= C) continue;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) ob[(size_t)(co + k) * hw + xx] = acc[mb][nb][k];
+        }
+    }
+}
+
+template <int C>
+__global__ __launch_bounds__(256) void fmt_merge_kernel(FtMergeSrc<C> src, float* __restrict__ out) {
+    const int x = (int)blockIdx.x * 64 + ((int)threadIdx.x & 63), y = (int)blockIdx.y * 4 + ((int)threadIdx.x >> 6), n = (int)blockIdx.z;
+    if (x >= src.W || y >= src.H) return;
+    FtMergeSrc<C> s = src;
+    s.at(n, y, x);
+    const size_t HW = (size_t)src.H * src.W;
+    float* o = out + (size_t)n * C * HW + (size_t)y * src.W + x;
+#pragma unroll
+    for (int c0 = 0; c0 < C; c0 += 8) {
+        float v[8];
+        s.load8(c0, v);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) o[(size_t)(c0 + k) * HW] = v[k];
+    }
+}
+
+template <int C, class Src>
+static int launch_fmt_path(const Src& src, const void* wp, float* out, int N, int H, int W, hipStream_t st, const char* what) {
+    typedef FtShape<C> F;
+    const int tiles_x = (int)ceil_div(W, FT_TW), tiles_y = (int)ceil_div(H, FT_TH);
+    if (F::LDS > 48 * 1024)
+        hipFuncSetAttribute(reinterpret_cast<const void*>(&fmt_path_kernel<C, Src>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)F::LDS);
+    hipLaunchKernelGGL((fmt_path_kernel<C, Src>), dim3(tiles_x * tiles_y, N), dim3(256), F::LDS, st, src, wp, out, H, W, tiles_x, tiles_x * tiles_y);
+    return check_launch(what);
+}
+
+template <int C>
+static FtMergeSrc<C> ft_merge_src(const float* prev, const float* lat, const float* wr, int h, int w, int H, int W) {
+    FtMergeSrc<C> s{};
+    s.prev = prev; s.lat = lat; s.wr = wr;
+    s.H = H; s.W = W; s.h = h; s.w = w;
+    s.sy = (float)h / (float)H;
+    s.sx = (float)w / (float)W;
+    return s;
+}
+
+static int ft_slabs(int ntok) {
+    const int ntile = (int)ceil_div(ntok, FT_TOK), s = (int)ceil_div(ntile, 4);
+    return s < FT_MAX_SLABS ? s : FT_MAX_SLABS;
+}
+
+static bool ft_path_args(const char* what, int N, int C, int H, int W) {
+    if (N < 1 || N > 65535 || H < 1 || W < 1 || (long long)N * C * H * W >= (1LL << 40)) { set_error("%s: bad arguments", what); return false; }
+    return true;
+}
+
+}  // namespace mvs
+
+using namespace mvs;
+
+extern "C" size_t mvs_fmt_weights_bytes(void) { return (size_t)FT_W_END * 16; }
+extern "C" size_t mvs_fmt_vectors_bytes(void) { return (size_t)FT_V_END * 4; }
+extern "C" size_t mvs_fmt_kv_operand_bytes(void) { return (size_t)FT_KVOP * 16; }
+
+extern "C" size_t mvs_fmt_kv_workspace_bytes(int N, int n) {
+    if (N < 1 || n < 1) return 0;
+    return (size_t)N * ft_slabs(n) * FT_PART * sizeof(float);
+}
+
+extern "C" int mvs_fmt_kv_fwd(const float* x, const float* pe, const void* w_packed, const float* vectors, void* workspace, size_t workspace_bytes,
+                              void* kv_operand, int N, int n, void* stream) {
+    if (!x || !w_packed || !vectors || !workspace || !kv_operand || N < 1 || N > 65535 || n < 1 || (long long)N * 64 * n >= (1LL << 40)) {
+        set_error("mvs_fmt_kv_fwd: bad arguments");
+        return MVS_ERR_ARG;
+    }
+    if (workspace_bytes < mvs_fmt_kv_workspace_bytes(N, n)) { set_error("mvs_fmt_kv_fwd: workspace smaller than mvs_fmt_kv_workspace_bytes"); return MVS_ERR_ARG; }
+    hipStream_t st = (hipStream_t)stream;
+    const int slabs = ft_slabs(n);
+    hipLaunchKernelGGL(fmt_kv_partial_kernel, dim3(slabs, N), dim3(256), 4 * FT_PART * sizeof(float), st, x, pe,
+                       reinterpret_cast<const bf16x8*>(w_packed), vectors, reinterpret_cast<float*>(workspace), n, (int)ceil_div(n, FT_TOK));
+    int rc = check_launch("fmt_kv_partial_kernel");
+    if (rc != MVS_OK) return rc;
+    hipLaunchKernelGGL(fmt_kv_reduce_kernel, dim3(5, N), dim3(256), 256 * sizeof(float), st, reinterpret_cast<const float*>(workspace),
+                       reinterpret_cast<bf16x8*>(kv_operand), slabs);
+    return check_launch("fmt_kv_reduce_kernel");
+}
+
+extern "C" int mvs_fmt_block_fwd(const float* x, const float* pe, const void* kv_operand, const void* w_packed, const float* vectors, float* y,
+                                 int N, int n, int kv_div, void* stream) {
+    if (!x || !kv_operand || !w_packed || !vectors || !y || N < 1 || N > 65535 || n < 1 || kv_div < 1 || (long long)N * 64 * n >= (1LL << 40)) {
+        set_error("mvs_fmt_block_fwd: bad arguments");
+        return MVS_ERR_ARG;
+    }
+    FmtBlockArgs a{x, pe, reinterpret_cast<const bf16x8*>(kv_operand), reinterpret_cast<const bf16x8*>(w_packed), vectors, y, n, kv_div};
+    hipLaunchKernelGGL(fmt_block_kernel, dim3(ceil_div(n, 4 * FT_TOK), N), dim3(256), 0, (hipStream_t)stream, a);
+    return check_launch("fmt_block_kernel");
+}
+
+#define MVS_FMT_LEVELS(X) X(32) X(16) X(8)
+
+extern "C" int mvs_fmt_path_fwd(const float* prev, const float* lateral, const float* w_reduce, const void* w_packed, float* y, int N, int C, int h,
+                                int w, int H, int W, void* stream) {
+    if (!prev || !lateral || !w_reduce || !w_packed || !y || h < 1 || w < 1 || !ft_path_args("mvs_fmt_path_fwd", N, C, H, W)) {
+        set_error("mvs_fmt_path_fwd: bad arguments");
+        return MVS_ERR_ARG;
+    }
+#define MVS_FMT_GO(CC) \
+    if (C == CC) return launch_fmt_path<CC>(ft_merge_src<CC>(prev, lateral, w_reduce, h, w, H, W), w_packed, y, N, H, W, (hipStream_t)stream, "fmt_path_kernel");
+    MVS_FMT_LEVELS(MVS_FMT_GO)
+#undef MVS_FMT_GO
+    set_error("mvs_fmt_path_fwd: built for the pathway levels 64 -> 32, 32 -> 16, 16 -> 8 (C = 32, 16, 8) [FMT.py:146-152]; got C = %d", C);
+    return MVS_ERR_UNSUPPORTED;
+}
+
+extern "C" int mvs_fmt_merge_fwd(const float* prev, const float* lateral, const float* w_reduce, float* merged, int N, int C, int h, int w, int H,
+                                 int W, void* stream) {
+    if (!prev || !lateral || !w_reduce || !merged || h < 1 || w < 1 || !ft_path_args("mvs_fmt_merge_fwd", N, C, H, W)) {
+        set_error("mvs_fmt_merge_fwd: bad arguments");
+        return MVS_ERR_ARG;
+    }
+    const dim3 grid(ceil_div(W, 64), ceil_div(H, 4), N);
+#define MVS_FMT_MG(CC) \
+    if (C == CC) { \
+        hipLaunchKernelGGL((fmt_merge_kernel<CC>), grid, dim3(256), 0, (hipStream_t)stream, ft_merge_src<CC>(prev, lateral, w_reduce, h, w, H, W), merged); \
+        return check_launch("fmt_merge_kernel"); \
+    }
+    MVS_FMT_LEVELS(MVS_FMT_MG)
+#undef MVS_FMT_MG
+    set_error("mvs_fmt_merge_fwd: built for C = 32, 16, 8 [FMT.py:146-152]; got C = %d", C);
+    return MVS_ERR_UNSUPPORTED;
+}
+
+extern "C" int mvs_fmt_smooth_fwd(const float* x, const void* w_packed, float* y, int N, int C, int H, int W, void* stream) {
+    if (!x || !w_packed || !y || !ft_path_args("mvs_fmt_smooth_fwd", N, C, H, W)) { set_error("mvs_fmt_smooth_fwd: bad arguments"); return MVS_ERR_ARG; }
+#define MVS_FMT_SM(CC) \
+    if (C == CC) return launch_fmt_path<CC>(FtPlanarSrc<CC>{x, H, W, nullptr}, w_packed, y, N, H, W, (hipStream_t)stream, "fmt_path_kernel");
+    MVS_FMT_LEVELS(MVS_FMT_SM)
+#undef MVS_FMT_SM
+    set_error("mvs_fmt_smooth_fwd: built for C = 32, 16, 8 [FMT.py:150-152]; got C = %d", C);
+    return MVS_ERR_UNSUPPORTED;
+}

@@ -142,6 +142,105 @@ def fpn_merge_conv(prev: torch.Tensor, lateral: torch.Tensor, w_inner: torch.Ten
     return out
 
 
+def _fmt_tokens(x: torch.Tensor) -> torch.Tensor:
+    x = _planar32(x)
+    if x.dim() < 3 or x.shape[1] != 64:
+        raise ValueError("FMT tokens are planar [N, 64, n] (or the feature map [N, 64, h, w]); got %s" % (tuple(x.shape),))
+    return x
+
+
+def _fmt_params(w_packed: torch.Tensor, vectors: torch.Tensor) -> None:
+    L = lib()
+    if w_packed.numel() * w_packed.element_size() != L.mvs_fmt_weights_bytes() or vectors.dtype != torch.float32 \
+            or vectors.numel() * 4 != L.mvs_fmt_vectors_bytes():
+        raise ValueError("(w_packed, vectors) must come from packing.pack_fmt_block")
+
+
+def _fmt_pe(pe: Optional[torch.Tensor], x: torch.Tensor) -> None:
+    n = x[0, 0].numel()
+    if pe is not None and (pe.dtype != torch.float32 or tuple(pe.shape) != (64, n) or not pe.is_contiguous() or pe.device != x.device):
+        raise ValueError("pe must be the fp32 contiguous position table [64, %d] of this map size on %s; got %s %s on %s"
+                         % (n, x.device, pe.dtype, tuple(pe.shape), pe.device))
+
+
+def _fmt_smooth_weights(w_packed: torch.Tensor, C: int) -> None:
+    """w_packed must be packing.pack_fpn_conv_weights(w [C, C, 3, 3], 1): [steps][row blocks][hi|lo][64 lanes][8] bf16."""
+    want = ((9 * (C // 8) + 3) // 4) * ((C + 15) // 16) * 2 * 64 * 8 * 2
+    if C % 8 == 0 and w_packed.numel() * w_packed.element_size() != want:
+        raise ValueError("w_packed must come from packing.pack_fpn_conv_weights(w [%d, %d, 3, 3], 1): %d bytes, got %d"
+                         % (C, C, want, w_packed.numel() * w_packed.element_size()))
+
+
+def fmt_kv(x: torch.Tensor, w_packed: torch.Tensor, vectors: torch.Tensor, pe: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Key/value summary of one FMT block: x [N, 64, n] or [N, 64, h, w] planar (+ pe [64, n]) -> the packed
+    operand [N, mvs_fmt_kv_operand_bytes] (uint8) that fmt_block consumes: KV_h = sum_s k_s (x) v_s and sum_s k_s of LN1(x), k = elu(Wk .) + 1.
+    (w_packed, vectors) = packing.pack_fmt_block.  Deterministic (fixed-order reduction, no atomics)."""
+    x = _fmt_tokens(x)
+    _fmt_params(w_packed, vectors)
+    _fmt_pe(pe, x)
+    N, n = x.shape[0], x[0, 0].numel()
+    L = lib()
+    ws_bytes = L.mvs_fmt_kv_workspace_bytes(N, n)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
+    out = torch.empty(N, L.mvs_fmt_kv_operand_bytes(), dtype=torch.uint8, device=x.device)
+    check(L.mvs_fmt_kv_fwd(ptr(x), ptr(pe), ptr(w_packed), ptr(vectors), ptr(ws), ws_bytes, ptr(out), N, n, stream_of(x)), "mvs_fmt_kv_fwd")
+    return out
+
+
+def fmt_block(x: torch.Tensor, kv_operand: torch.Tensor, w_packed: torch.Tensor, vectors: torch.Tensor, pe: Optional[torch.Tensor] = None,
+              kv_div: int = 1) -> torch.Tensor:
+    """One pre-norm CrossBlock with linear attention for N views in one launch: x [N, 64, n] or [N, 64, h, w] (+ pe) -> the same shape,
+    fp32.  View i attends to kv_operand[i // kv_div] (fmt_kv of x itself for self attention, of the reference view's tokens for cross
+    attention with kv_div = V - 1)."""
+    x = _fmt_tokens(x)
+    _fmt_params(w_packed, vectors)
+    _fmt_pe(pe, x)
+    N, n = x.shape[0], x[0, 0].numel()
+    assert kv_div >= 1 and kv_operand.shape[0] * kv_div >= N and kv_operand.shape[1] == lib().mvs_fmt_kv_operand_bytes(), \
+        (tuple(kv_operand.shape), kv_div, N)
+    out = torch.empty_like(x)
+    check(lib().mvs_fmt_block_fwd(ptr(x), ptr(pe), ptr(kv_operand), ptr(w_packed), ptr(vectors), ptr(out), N, n, int(kv_div), stream_of(x)),
+          "mvs_fmt_block_fwd")
+    return out
+
+
+def _fmt_level(prev: torch.Tensor, lateral: torch.Tensor, w_reduce: torch.Tensor):
+    prev, lateral = _planar32(prev), _planar32(lateral)
+    N, C, H, W = lateral.shape
+    assert prev.dim() == 4 and prev.shape[:2] == (N, 2 * C) and tuple(w_reduce.shape) == (C, 2 * C), (tuple(prev.shape), tuple(lateral.shape))
+    return prev, lateral, _planar32(w_reduce), N, C, prev.shape[2], prev.shape[3], H, W
+
+
+def fmt_path(prev: torch.Tensor, lateral: torch.Tensor, w_reduce: torch.Tensor, w_packed: torch.Tensor) -> torch.Tensor:
+    """One pathway level fused (FMT.py:195-197): smooth(bilinear(dim_reduction(prev [N,2C,h,w]), size (H,W), align_corners=False) + lateral
+    [N,C,H,W]) -> [N,C,H,W] fp32; w_reduce [C,2C], w_packed = packing.pack_fpn_conv_weights(smooth.weight, 1).  The merged map is
+    computed inside the convolution's staging and never written."""
+    prev, lateral, w_reduce, N, C, h, w, H, W = _fmt_level(prev, lateral, w_reduce)
+    _fmt_smooth_weights(w_packed, C)
+    out = torch.empty_like(lateral)
+    check(lib().mvs_fmt_path_fwd(ptr(prev), ptr(lateral), ptr(w_reduce), ptr(w_packed), ptr(out), N, C, h, w, H, W, stream_of(lateral)),
+          "mvs_fmt_path_fwd")
+    return out
+
+
+def fmt_merge(prev: torch.Tensor, lateral: torch.Tensor, w_reduce: torch.Tensor) -> torch.Tensor:
+    """The merged map of a pathway level, written out (the unfused form): bilinear(dim_reduction(prev)) + lateral -> [N,C,H,W] fp32."""
+    prev, lateral, w_reduce, N, C, h, w, H, W = _fmt_level(prev, lateral, w_reduce)
+    out = torch.empty_like(lateral)
+    check(lib().mvs_fmt_merge_fwd(ptr(prev), ptr(lateral), ptr(w_reduce), ptr(out), N, C, h, w, H, W, stream_of(lateral)), "mvs_fmt_merge_fwd")
+    return out
+
+
+def fmt_smooth(x: torch.Tensor, w_packed: torch.Tensor) -> torch.Tensor:
+    """Conv2d(C, C, 3, padding=1, bias=False) of the pathway (smooth_k) on a planar map [N,C,H,W], C = 32 | 16 | 8 -> fp32."""
+    x = _planar32(x)
+    N, C, H, W = x.shape
+    _fmt_smooth_weights(w_packed, C)
+    out = torch.empty_like(x)
+    check(lib().mvs_fmt_smooth_fwd(ptr(x), ptr(w_packed), ptr(out), N, C, H, W, stream_of(x)), "mvs_fmt_smooth_fwd")
+    return out
+
+
 def _feat(t) -> Tuple[torch.Tensor, int]:
     if isinstance(t, PackedFeatures):
         return t, _lib.DTYPE_CODE[t.dtype]

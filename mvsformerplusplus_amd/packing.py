@@ -216,3 +216,35 @@ def pack_generic_deconv_weights(w: torch.Tensor) -> torch.Tensor:
     (the kernel gathers input i = (o + p - k) / s for kernel index k)."""
     cin, cout = w.shape[:2]
     return w.float().permute(2, 3, 4, 0, 1).reshape(-1, cin, cout).contiguous()
+
+
+def pack_fmt_linear(w: torch.Tensor) -> torch.Tensor:
+    """w [N, K] (y = w @ x; N padded to a multiple of 16, K % 32 == 0) -> bf16 1-D tensor for the GEMMs of csrc/fmt_kernels.hip, whose
+    operand is the previous GEMM's accumulator: k-slot (step, g, e) holds input channel 32*step + 16*(e >> 2) + 4*g + (e & 3):
+
+        packed[step][mb][hi|lo][lane = g*16 + j][e] = w[16*mb + j][32*step + 16*(e >> 2) + 4*g + (e & 3)]
+    """
+    n, k = w.shape
+    assert k % 32 == 0, (n, k)
+    npad = (n + 15) // 16 * 16
+    if npad != n:
+        w = torch.cat([w.float(), w.new_zeros(npad - n, k).float()], 0)
+    full = w.float().reshape(npad // 16, 16, k // 32, 2, 4, 4).permute(2, 0, 4, 1, 3, 5).reshape(k // 32, npad // 16, 4, 16, 8)  # [step, mb, g, j, e]
+    return _split_bf16(full).permute(1, 2, 0, 3, 4, 5).contiguous().reshape(-1)                                    # [step, mb, 2, g, j, e]
+
+
+FMT_VECTORS = ("norm1.weight", "norm1.bias", "attn.proj.bias", "ls1.gamma", "norm2.weight", "norm2.bias", "mlp.fc1.bias", "mlp.fc2.bias",
+               "ls2.gamma")
+
+
+def pack_fmt_block(sd: Dict[str, torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
+    """One CrossBlock of the FMT (keys relative to ``FMT.layers.N.``; d_model 64, hidden 256) -> (packed weights bf16: q_proj | proj | fc1 |
+    fc2 | [k_proj; v_proj], vectors fp32 [768] in the order of FMT_VECTORS): the layout constants FT_W_* / FT_V_* of fmt_kernels.hip."""
+    mats = [sd["attn.q_proj.weight"], sd["attn.proj.weight"], sd["mlp.fc1.weight"], sd["mlp.fc2.weight"],
+            torch.cat([sd["attn.k_proj.weight"], sd["attn.v_proj.weight"]], 0)]
+    want = [(64, 64), (64, 64), (256, 64), (64, 256), (128, 64)]
+    assert [tuple(m.shape) for m in mats] == want, [tuple(m.shape) for m in mats]
+    w = torch.cat([pack_fmt_linear(m.detach().float().cpu()) for m in mats])
+    v = torch.cat([sd[k].detach().float().cpu().reshape(-1) for k in FMT_VECTORS])
+    assert w.numel() == 12288 * 8 and v.numel() == 768
+    return w, v
