@@ -965,7 +965,7 @@ struct BfDeconv {
     static constexpr size_t LDS_BYTES = (F16 || MVS_DECONV_PLANES) ? (size_t)OPT * PLANE : Cfg::LDS_BYTES;
 };
 
-template <class Cfg>
+template <class Cfg, bool ONE = false>
 __device__ __forceinline__ void bf_deconv_load_step(int st, int ntap, int pd, int ph, int pw, int g, const bf16x8* wq, const char* ldsb,
                                                     const int* voxbase, bf16x8* ah, bf16x8* al, bf16x8* bh, bf16x8* bl) {
     constexpr int SD = Cfg::SD, OPT = BfDeconv<Cfg>::OPT;
@@ -984,7 +984,7 @@ __device__ __forceinline__ void bf_deconv_load_step(int st, int ntap, int pd, in
     for (int mb = 0; mb < Cfg::MREP; ++mb) {
         if (MVS_ABL == 2 && st > 1) continue;
         ah[mb] = wq[(size_t)((st * CfgSplit<Cfg>::MREP_ALL + mb) * 2) * 64];
-        al[mb] = wq[(size_t)((st * CfgSplit<Cfg>::MREP_ALL + mb) * 2 + 1) * 64];
+        if constexpr (!ONE) al[mb] = wq[(size_t)((st * CfgSplit<Cfg>::MREP_ALL + mb) * 2 + 1) * 64];
     }
 #pragma unroll
     for (int nb = 0; nb < Cfg::NREP; ++nb) {
@@ -994,7 +994,155 @@ __device__ __forceinline__ void bf_deconv_load_step(int st, int ntap, int pd, in
     }
 }
 
-template <class Cfg, bool SPLIT>
+// ------------------------------------------------------------------------------------------------
+// Class-fused contraction of the (1,2,2) layers with 32 / 64 input channels (32 -> 16 and 64 -> 32, CostRegNet3D).
+//
+// The loop above runs the four (ph, pw) parity classes one after the other: 3 + 6 + 6 + 12 = 27 taps, each with its own LDS
+// operand reads and a run-time decode of the tap address in every step.  The 27 taps sit on only 3 x 2 x 2 = 12 input positions
+// (od, oh, ow): (oh, ow) = (0, 0) serves all four classes, (0, 1) and (1, 0) two each, (1, 1) one.  This form walks the 12
+// positions once, in descending (od, oh, ow) - the order in which every class visits its own taps - reads a position's operand
+// fragments once (12 instead of 27 reads per channel block, at compile-time offsets from one address register) and issues the MFMAs
+// of the 1-4 classes that use it into four accumulator sets.  OPT is 4 or 8, so a K = 32 step is a whole or half tap of ONE
+// class: every class still sums the same K groups in the same order (and the same term order per accumulator) - the outputs are
+// bit-identical to the per-class loop.  The packed weights stay class by class (wstep: the class base plus the tap's place in it).
+// ------------------------------------------------------------------------------------------------
+#ifndef MVS_DECONV_ONE_TERM
+#define MVS_DECONV_ONE_TERM 1      // the one-tile transposed kernels honour the one-term fp16 format (0: both weight terms, as rounds 4-6 shipped)
+#endif
+#ifndef MVS_DECONV_FUSED_DEFAULT
+#define MVS_DECONV_FUSED_DEFAULT 1 // 0: the dispatch never picks the class-fused walk by itself (MVS_DECONV_CLASS_FUSED=1 still forces it)
+#endif
+#ifndef MVS_DECONV_WPF
+#define MVS_DECONV_WPF 0           // class-fused walk: weight prefetch distance in K steps (0: one weight set, refilled in place)
+#endif
+template <class Cfg>
+struct BfDeconvF {
+    static constexpr bool ENABLED = Cfg::SD == 1 && (Cfg::CIN == 32 || Cfg::CIN == 64) && Cfg::COUT >= 16;
+    static constexpr bool F16 = CfgFmt<Cfg>::F16, ONE = MVS_DECONV_ONE_TERM && CfgFmt<Cfg>::ONE;
+    // which form the dispatch picks when MVS_DECONV_CLASS_FUSED is unset: the walk where it measured faster than the loop - the one-term 64 -> 32
+    // layer (38.4 / 23.4 us against 41.0 / 24.2 at stage 4 / 3).  The four accumulator sets cost a resident wave (4 per SIMD against 5-6) and
+    // these kernels live on the latency their waves hide: two-term 32 -> 16 60.8 / 32.1 against 57.8 / 31.9, two-term 64 -> 32 53.4 / 32.2 against 52.6 / 32.3
+    static constexpr bool DEFAULT = ENABLED && MVS_DECONV_FUSED_DEFAULT && ONE && Cfg::CIN == 64;
+    static constexpr int SPT = BfDeconv<Cfg>::OPT / 4;                     // K = 32 steps per tap
+    static constexpr int NSTEP = 12 * SPT;                                // steps of the walk: position U / SPT, channel half U % SPT
+    static constexpr int NW = MVS_DECONV_WPF + 1;
+    static constexpr int ROWB = Cfg::LW * BfDeconv<Cfg>::SB;              // bytes between a wave's consecutive rows
+    // position p = 0..11 <-> od = 1 - p / 4, oh = 1 - (p >> 1 & 1), ow = 1 - (p & 1); class cls = 2 ph + pw
+    static constexpr bool uses(int cls, int p) { return ((cls & 2) || (p & 2)) && ((cls & 1) || (p & 1)); }
+    static constexpr int ntap(int cls) { return 3 * ((cls & 2) ? 2 : 1) * ((cls & 1) ? 2 : 1); }
+    static constexpr int wbase(int cls) { return cls == 0 ? 0 : wbase(cls - 1) + ntap(cls - 1) * SPT; }   // first step of a class in the packed weights
+    static constexpr int wstep(int cls, int u) {
+        const int p = u / SPT, nkh = (cls & 2) ? 2 : 1, nkw = (cls & 1) ? 2 : 1;
+        const int a_d = p >> 2, a_h = (cls & 2) ? (p >> 1) & 1 : 0, a_w = (cls & 1) ? p & 1 : 0;
+        return wbase(cls) + ((a_d * nkh + a_h) * nkw + a_w) * SPT + u % SPT;
+    }
+    // byte offset of step u's operand, relative to the lane's voxel ONE PLANE BELOW its own (od = -1: offsets stay non-negative) in octet plane g
+    static constexpr int xoff(int u) {
+        const int p = u / SPT, od = 1 - (p >> 2), oh = 1 - ((p >> 1) & 1), ow = 1 - (p & 1);
+        return (((od + 1) * Cfg::LH + oh) * Cfg::LW + ow) * BfDeconv<Cfg>::SB + (u % SPT) * 4 * BfDeconv<Cfg>::PLANE;
+    }
+    static_assert(!ENABLED || Cfg::THM % Cfg::NREP == 0, "a wave's rows must stay inside one input plane");
+};
+
+// WHICH: 1 = w_lo, 2 = w_hi, 3 = both; WHEN (the in-place refill of MVS_DECONV_WPF = 0): 0 = every class step U uses, 1 = only the classes step U - 1
+// uses too (their registers are free once step U - 1 has issued its MFMAs on them), 2 = only the classes step U - 1 does not use
+template <class Cfg, int U, int CLS, int WHICH = 3, int WHEN = 0>
+__device__ __forceinline__ void bfdf_load_w(__amdgpu_buffer_rsrc_t wrs, unsigned wvoff, bf16x8* ah, bf16x8* al) {
+    using P = BfDeconvF<Cfg>;
+    constexpr bool prev = U > 0 && P::uses(CLS, (U > 0 ? U - 1 : 0) / P::SPT);
+    if constexpr (P::uses(CLS, U / P::SPT) && (WHEN == 0 || (WHEN == 1) == prev)) {
+        if (MVS_ABL == 2 && U > 1) return;
+#pragma unroll
+        for (int mb = 0; mb < Cfg::MREP; ++mb) {
+            constexpr int MREP_ALL = CfgSplit<Cfg>::MREP_ALL;
+            const int e = (P::wstep(CLS, U) * MREP_ALL + mb) * 2 * 1024;  // wave-uniform byte offset: the scalar operand of the buffer load
+            if constexpr ((WHICH & 2) != 0) ah[mb] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(wrs, (int)wvoff, e, 0));
+            if constexpr ((WHICH & 1) != 0 && !P::ONE) al[mb] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(wrs, (int)wvoff, e + 1024, 0));
+        }
+    }
+}
+template <class Cfg, int U, int WHICH = 3, int WHEN = 0>
+__device__ __forceinline__ void bfdf_load_w_all(__amdgpu_buffer_rsrc_t wrs, unsigned wvoff, bf16x8 (*ah)[Cfg::MREP], bf16x8 (*al)[Cfg::MREP]) {
+    bfdf_load_w<Cfg, U, 0, WHICH, WHEN>(wrs, wvoff, ah[0], al[0]);
+    bfdf_load_w<Cfg, U, 1, WHICH, WHEN>(wrs, wvoff, ah[1], al[1]);
+    bfdf_load_w<Cfg, U, 2, WHICH, WHEN>(wrs, wvoff, ah[2], al[2]);
+    bfdf_load_w<Cfg, U, 3, WHICH, WHEN>(wrs, wvoff, ah[3], al[3]);
+}
+template <class Cfg, int U>
+__device__ __forceinline__ void bfdf_load_x(const char* px, bf16x8* bh, bf16x8* bl) {
+    using P = BfDeconvF<Cfg>;
+#pragma unroll
+    for (int nb = 0; nb < Cfg::NREP; ++nb) {
+        if (MVS_ABL == 3 && U > 1) continue;
+        bh[nb] = *reinterpret_cast<const bf16x8*>(px + P::xoff(U) + nb * P::ROWB);
+        if constexpr (!P::F16) bl[nb] = *reinterpret_cast<const bf16x8*>(px + P::xoff(U) + nb * P::ROWB + 16);
+    }
+}
+// one MFMA term of step U for every class that uses the position, class-outer: consecutive MFMAs hit different accumulators
+// TERM (bf_mfma_step's order per accumulator): fp16 0 = w_lo . x, 1 = w_hi . x; split bf16 0 = lo . hi, 1 = hi . lo, 2 = hi . hi
+template <class Cfg, int U, int TERM, int CLS>
+__device__ __forceinline__ void bfdf_mfma(const bf16x8* ah, const bf16x8* al, const bf16x8* bh, const bf16x8* bl, f32x4 (*acc)[Cfg::NREP]) {
+    using P = BfDeconvF<Cfg>;
+    if constexpr (P::uses(CLS, U / P::SPT)) {
+#pragma unroll
+        for (int mb = 0; mb < Cfg::MREP; ++mb)
+#pragma unroll
+            for (int nb = 0; nb < Cfg::NREP; ++nb) {
+                if constexpr (P::F16)
+                    acc[mb][nb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, TERM == 0 ? al[mb] : ah[mb]), __builtin_bit_cast(f16x8, bh[nb]),
+                                                                         acc[mb][nb], 0, 0, 0);
+                else
+                    acc[mb][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(TERM == 0 ? al[mb] : ah[mb], TERM == 1 ? bl[nb] : bh[nb], acc[mb][nb], 0, 0, 0);
+            }
+    }
+}
+template <class Cfg, int U, int TERM>
+__device__ __forceinline__ void bfdf_mfma_all(bf16x8 (*ah)[Cfg::MREP], bf16x8 (*al)[Cfg::MREP], const bf16x8* bh, const bf16x8* bl,
+                                              f32x4 (*acc)[Cfg::MREP][Cfg::NREP]) {
+    bfdf_mfma<Cfg, U, TERM, 0>(ah[0], al[0], bh, bl, acc[0]);
+    bfdf_mfma<Cfg, U, TERM, 1>(ah[1], al[1], bh, bl, acc[1]);
+    bfdf_mfma<Cfg, U, TERM, 2>(ah[2], al[2], bh, bl, acc[2]);
+    bfdf_mfma<Cfg, U, TERM, 3>(ah[3], al[3], bh, bl, acc[3]);
+}
+
+// the walk, fully unrolled and software-pipelined as the forward convolutions: LDS operands one step ahead in two alternating register
+// sets, weights MVS_DECONV_WPF steps ahead in rotating sets; sched_barrier keeps the requests above the MFMAs they hide under.
+// MVS_DECONV_WPF = 0 keeps ONE weight set and refills it in place: a class's w_lo of step U + 1 is requested as soon as step U's lo term
+// has been issued, its w_hi after the last term - nearly a step ahead at half the weight registers (these kernels are paced by the
+// latency their resident waves hide, and a second weight set costs one to two of them).
+template <class Cfg, int U>
+struct BfDeconvFSteps {
+    using P = BfDeconvF<Cfg>;
+    static __device__ __forceinline__ void run(__amdgpu_buffer_rsrc_t wrs, unsigned wvoff, const char* px, f32x4 (*acc)[Cfg::MREP][Cfg::NREP],
+                                               bf16x8 (*ah)[4][Cfg::MREP], bf16x8 (*al)[4][Cfg::MREP], bf16x8 (*bh)[Cfg::NREP], bf16x8 (*bl)[Cfg::NREP]) {
+        constexpr int NSTEP = MVS_ABL == 6 ? 1 : P::NSTEP, WPF = MVS_DECONV_WPF, NW = P::NW;
+        constexpr bool NEXT = U + 1 < NSTEP;
+        if constexpr (U < NSTEP) {
+            if constexpr (WPF > 0 && U + WPF < NSTEP) bfdf_load_w_all<Cfg, U + WPF>(wrs, wvoff, ah[(U + WPF) % NW], al[(U + WPF) % NW]);
+            if constexpr (WPF == 0 && NEXT) bfdf_load_w_all<Cfg, U + 1, 3, 2>(wrs, wvoff, ah[0], al[0]);
+            if constexpr (NEXT) bfdf_load_x<Cfg, U + 1>(px, bh[(U + 1) & 1], bl[(U + 1) & 1]);
+            __builtin_amdgcn_sched_barrier(0);
+            if constexpr (!P::ONE) {
+                bfdf_mfma_all<Cfg, U, 0>(ah[U % NW], al[U % NW], bh[U & 1], bl[U & 1], acc);
+                if constexpr (WPF == 0 && NEXT) {
+                    __builtin_amdgcn_sched_barrier(0);
+                    bfdf_load_w_all<Cfg, U + 1, 1, 1>(wrs, wvoff, ah[0], al[0]);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            }
+            if constexpr (!P::F16) bfdf_mfma_all<Cfg, U, 1>(ah[U % NW], al[U % NW], bh[U & 1], bl[U & 1], acc);
+            bfdf_mfma_all<Cfg, U, P::F16 ? 1 : 2>(ah[U % NW], al[U % NW], bh[U & 1], bl[U & 1], acc);
+            if constexpr (WPF == 0 && NEXT) {
+                __builtin_amdgcn_sched_barrier(0);
+                bfdf_load_w_all<Cfg, U + 1, 2, 1>(wrs, wvoff, ah[0], al[0]);
+            }
+            BfDeconvFSteps<Cfg, U + 1>::run(wrs, wvoff, px, acc, ah, al, bh, bl);
+        }
+    }
+};
+
+// FUSED: the class-fused walk (BfDeconvF::ENABLED layers; launch_deconv_bf chooses, MVS_DECONV_CLASS_FUSED overrides)
+template <class Cfg, bool SPLIT, bool FUSED = false>
 __global__ __launch_bounds__(256) void deconv3d_mfma_bf16x3_kernel(const float* __restrict__ x, const void* wp, const float* __restrict__ bias,
                                                                    const float* __restrict__ skip, float* __restrict__ y,
                                                                    const float* __restrict__ prob_w, const float* __restrict__ prob_b,
@@ -1093,32 +1241,63 @@ __global__ __launch_bounds__(256) void deconv3d_mfma_bf16x3_kernel(const float* 
             }
         }
     }
+    constexpr bool ONE = MVS_DECONV_ONE_TERM && CfgFmt<Cfg>::ONE;          // one fp16 weight term: w_lo is neither loaded nor multiplied
+    // FUSED: all four classes are contracted here, in one walk over the 12 input positions (BfDeconvF); the class loop below keeps the epilogues
+    f32x4 accf[FUSED ? 4 : 1][MREP][NREP];
+    if constexpr (FUSED) {
+        using P = BfDeconvF<Cfg>;
+        static_assert(P::ENABLED && NCLS == 4 && !PAIR, "class-fused walk: the (1,2,2) layers with 32 / 64 input channels");
+#pragma unroll
+        for (int cls = 0; cls < 4; ++cls)
+#pragma unroll
+            for (int mb = 0; mb < MREP; ++mb)
+#pragma unroll
+                for (int nb = 0; nb < NREP; ++nb) accf[cls][mb][nb] = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
+        const __amdgpu_buffer_rsrc_t wrs = bf_make_rsrc(wp, (unsigned)(27 * P::SPT * MREP_ALL * 2 * 1024));
+        const unsigned wvoff = (unsigned)((mb0 * 2 * 64 + lane) * 16);
+        const char* px = ldsb + voxbase[0] - LH * LW * SB + g * BfDeconv<Cfg>::PLANE;
+        bf16x8 ah[P::NW][4][MREP], al[P::NW][4][MREP], bh[2][NREP], bl[2][NREP];
+        static_assert(MVS_DECONV_WPF >= 0 && MVS_DECONV_WPF <= 2, "weight prefetch distance of the class-fused walk");
+        prio_contract_begin();
+        bfdf_load_w_all<Cfg, 0>(wrs, wvoff, ah[0], al[0]);
+        if constexpr (MVS_DECONV_WPF > 1) bfdf_load_w_all<Cfg, 1>(wrs, wvoff, ah[1], al[1]);
+        bfdf_load_x<Cfg, 0>(px, bh[0], bl[0]);
+        BfDeconvFSteps<Cfg, 0>::run(wrs, wvoff, px, accf, ah, al, bh, bl);
+        prio_contract_end();
+    }
 #pragma unroll
     for (int cls = 0; cls < NCLS; cls += PAIR ? 2 : 1) {
         const int it = PAIR ? cls / 2 : cls;
         const int pw = PAIR ? 1 : (cls & 1), ph = (cls >> 1) & 1, pd = (SD == 2) ? (cls >> 2) : 0;
         f32x4 acc[MREP][NREP];
+        if constexpr (FUSED) {
 #pragma unroll
-        for (int mb = 0; mb < MREP; ++mb)
+            for (int mb = 0; mb < MREP; ++mb)
 #pragma unroll
-            for (int nb = 0; nb < NREP; ++nb) acc[mb][nb] = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
-        const int ntap = ((SD == 2) ? (pd ? 2 : 1) : 3) * (ph ? 2 : 1) * (pw ? 2 : 1);
-        const int nst = MVS_ABL == 6 ? 1 : (ntap * OPT + 3) / 4;
-        bf16x8 ah0[MREP], al0[MREP], bh0[NREP], bl0[NREP], ah1[MREP], al1[MREP], bh1[NREP], bl1[NREP];
-        prio_contract_begin();
-        bf_deconv_load_step<Cfg>(0, ntap, pd, ph, pw, g, wq, ldsb, voxbase, ah0, al0, bh0, bl0);
+                for (int nb = 0; nb < NREP; ++nb) acc[mb][nb] = accf[cls][mb][nb];
+        } else {
+#pragma unroll
+            for (int mb = 0; mb < MREP; ++mb)
+#pragma unroll
+                for (int nb = 0; nb < NREP; ++nb) acc[mb][nb] = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
+            const int ntap = ((SD == 2) ? (pd ? 2 : 1) : 3) * (ph ? 2 : 1) * (pw ? 2 : 1);
+            const int nst = MVS_ABL == 6 ? 1 : (ntap * OPT + 3) / 4;
+            bf16x8 ah0[MREP], al0[MREP], bh0[NREP], bl0[NREP], ah1[MREP], al1[MREP], bh1[NREP], bl1[NREP];
+            prio_contract_begin();
+            bf_deconv_load_step<Cfg, ONE>(0, ntap, pd, ph, pw, g, wq, ldsb, voxbase, ah0, al0, bh0, bl0);
 #pragma unroll 1
-        for (int st = 0; st + 1 < nst; st += 2) {
-            bf_deconv_load_step<Cfg>(st + 1, ntap, pd, ph, pw, g, wq, ldsb, voxbase, ah1, al1, bh1, bl1);
-            __builtin_amdgcn_sched_barrier(0);
-            bf_mfma_step<MREP, NREP, F16>(ah0, al0, bh0, bl0, acc);
-            bf_deconv_load_step<Cfg>(st + 2 < nst ? st + 2 : nst - 1, ntap, pd, ph, pw, g, wq, ldsb, voxbase, ah0, al0, bh0, bl0);
-            __builtin_amdgcn_sched_barrier(0);
-            bf_mfma_step<MREP, NREP, F16>(ah1, al1, bh1, bl1, acc);
+            for (int st = 0; st + 1 < nst; st += 2) {
+                bf_deconv_load_step<Cfg, ONE>(st + 1, ntap, pd, ph, pw, g, wq, ldsb, voxbase, ah1, al1, bh1, bl1);
+                __builtin_amdgcn_sched_barrier(0);
+                bf_mfma_step<MREP, NREP, F16, ONE>(ah0, al0, bh0, bl0, acc);
+                bf_deconv_load_step<Cfg, ONE>(st + 2 < nst ? st + 2 : nst - 1, ntap, pd, ph, pw, g, wq, ldsb, voxbase, ah0, al0, bh0, bl0);
+                __builtin_amdgcn_sched_barrier(0);
+                bf_mfma_step<MREP, NREP, F16, ONE>(ah1, al1, bh1, bl1, acc);
+            }
+            if (nst & 1) bf_mfma_step<MREP, NREP, F16, ONE>(ah0, al0, bh0, bl0, acc);
+            prio_contract_end();
+            wq += (size_t)nst * MREP_ALL * 2 * 64;
         }
-        if (nst & 1) bf_mfma_step<MREP, NREP, F16>(ah0, al0, bh0, bl0, acc);
-        prio_contract_end();
-        wq += (size_t)nst * MREP_ALL * 2 * 64;
 
 #pragma unroll
         for (int nb = 0; nb < NREP; ++nb) {
@@ -1511,6 +1690,19 @@ static int launch_deconv_bf(const float* x, const void* wp, const float* bias, c
         return check_launch("deconv3d_mfma_bf16x3_persist_kernel");
     }
     constexpr size_t DLDS = BfDeconv<Cfg>::LDS_BYTES;
+    if constexpr (BfDeconvF<Cfg>::ENABLED) {
+        // A/B switch, read at every dispatch (not cached): one process can run both forms on the same tensors (tests/test_deconv_class_fused.py).
+        // MVS_DECONV_CLASS_FUSED = 1 / 0 forces the class-fused walk / the per-class loop; unset: the measured choice per instantiation.
+        const char* sw = getenv("MVS_DECONV_CLASS_FUSED");
+        const bool fused = (sw == nullptr || sw[0] == '\0') ? BfDeconvF<Cfg>::DEFAULT : sw[0] != '0';
+        if (fused) {
+            if (DLDS > 48 * 1024)
+                hipFuncSetAttribute(reinterpret_cast<const void*>(&deconv3d_mfma_bf16x3_kernel<Cfg, SPLIT, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)DLDS);
+            hipLaunchKernelGGL((deconv3d_mfma_bf16x3_kernel<Cfg, SPLIT, true>), dim3(ntiles, B), dim3(256), DLDS, st, x, wp, bias, skip, y, prob_w, prob_b,
+                               logits, D, H, W, tx, ty, ntiles, relu);
+            return check_launch("deconv3d_mfma_bf16x3_kernel");
+        }
+    }
     if (DLDS > 48 * 1024)
         hipFuncSetAttribute(reinterpret_cast<const void*>(&deconv3d_mfma_bf16x3_kernel<Cfg, SPLIT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)DLDS);
     hipLaunchKernelGGL((deconv3d_mfma_bf16x3_kernel<Cfg, SPLIT>), dim3(ntiles, B), dim3(256), DLDS, st, x, wp, bias, skip, y, prob_w, prob_b,
