@@ -25,31 +25,6 @@
 #include "conv_cfg.h"
 #include "split_format.h"
 
-// ---- experiment switches -------------------------------------------------------------------------------------------
-// The defaults ARE the shipped configuration; scripts/conv_ablate.py builds variants of this file with other values to measure
-// what each choice is worth (DESIGN.md section 4.2 quotes the numbers).  Nothing outside this file and conv_cfg.h reads them.
-#ifndef MVS_ABL
-#define MVS_ABL 0                  // ablation: 1 no activation loads, 2 no weight loads after step 1, 3 no LDS operand reads after step 1,
-#endif                             // 4 one MFMA term of three, 5 no output stores, 6 one contraction step only (results are then meaningless)
-#ifndef MVS_WPF
-#define MVS_WPF 1                  // weight prefetch distance of the forward convolutions in contraction steps (2, 3: +-2 %, not kept)
-#endif
-#ifndef MVS_MSPLIT
-#define MVS_MSPLIT 1               // split wave mapping (SplitCfg) for the layers bound by the texture addresser
-#endif
-#ifndef MVS_MSPLIT_MIN_MREP
-#define MVS_MSPLIT_MIN_MREP 4      // ... forward convs: 64 output channels only (16 -> 32: -2 %, the extra registers cost a resident block)
-#endif
-#ifndef MVS_PERSIST
-#define MVS_PERSIST 1              // persistent kernels for the Cin = 8 convolutions and the 16 -> 8 transposed convolution
-#endif
-#ifndef MVS_PERSIST_PFD
-#define MVS_PERSIST_PFD 1          // tiles the persistent forward convolution prefetches ahead (2: a second register set costs the first
-#endif                             // U-Net layer a resident block, 82 vs 75 us, and changes nothing elsewhere)
-#ifndef MVS_XPASS_PREFETCH
-#define MVS_XPASS_PREFETCH 1       // loads of channel pass p + 1 issued before the contraction of pass p
-#endif
-
 namespace mvs {
 
 // ---- fp16 activation format (MVS_PREC_F16X2, round 3) ------------------------------------------------------------------
@@ -106,16 +81,6 @@ __device__ __forceinline__ void bf_mfma_step(const bf16x8* ah, const bf16x8* al,
                 acc[mb][nb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, ah[mb]), __builtin_bit_cast(f16x8, bh[nb]), acc[mb][nb], 0, 0, 0);
         return;
     }
-#if MVS_ABL == 4
-#pragma unroll
-    for (int mb = 0; mb < MREP; ++mb)
-#pragma unroll
-        for (int nb = 0; nb < NREP; ++nb) {
-            acc[mb][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[mb], bh[nb], acc[mb][nb], 0, 0, 0);
-            acc[mb][nb][0] += (float)al[mb][0] * (float)bl[nb][0];
-        }
-    return;
-#endif
 #pragma unroll
     for (int mb = 0; mb < MREP; ++mb)
 #pragma unroll
@@ -154,14 +119,8 @@ template <class Cfg> struct CfgSplit<Cfg, decltype((void)Cfg::MSPLIT)> { static 
 // (MI355X_MICROARCH.md, LDS) - so with 16 consecutive voxels per lane group the partner plane must sit on the SAME 16-byte slots
 // (shift 0: slots {0-3, 12-15} + {4-11}); with every other voxel (stride-2 reads: even slots) one slot further (16).  Rounds 3-4 shipped
 // 128 ("half a bank row"), which makes both halves of every service group hit the same eight slots: the 34-61 % bank conflicts PMC
-// counted on these kernels.  -DMVS_F16_PLANE_SHIFT=128 rebuilds that form for A/B runs.
-constexpr int bf_f16_plane_shift(int sw) {
-#ifdef MVS_F16_PLANE_SHIFT
-    return MVS_F16_PLANE_SHIFT;
-#else
-    return sw == 1 ? 0 : 16;
-#endif
-}
+// counted on these kernels.
+constexpr int bf_f16_plane_shift(int sw) { return sw == 1 ? 0 : 16; }
 
 template <class Cfg>
 struct BfConv {
@@ -184,13 +143,10 @@ struct BfConv {
     // persistent, weights-in-registers form (below): one pass whose packed weights take at most 64 VGPRs
     // (one-term fp16 weights: 4 VGPRs per step and output block - the stride-1 16 -> 16 layer fits too: 14 x 4 = 56)
     static constexpr bool ONE = CfgFmt<Cfg>::ONE;
-    static constexpr bool PERSIST = MVS_PERSIST && (Cfg::CIN == 8 || ONE) && Cfg::NPASS == 1 && NSTEP * Cfg::MREP * (ONE ? 4 : 8) <= 64;
+    static constexpr bool PERSIST = (Cfg::CIN == 8 || ONE) && Cfg::NPASS == 1 && NSTEP * Cfg::MREP * (ONE ? 4 : 8) <= 64;
     // ... and where those registers would cost resident blocks (Cin = 16: 56 weight + 24 prefetch registers on top of 32 operand registers = 2
     // blocks per CU) the block keeps the weights in LDS instead, behind the tile image: one more conflict-free ds_read_b128 per step and wave
-#ifndef MVS_PERSIST_WLDS
-#define MVS_PERSIST_WLDS 1
-#endif
-    static constexpr bool PERSIST_WLDS = MVS_PERSIST_WLDS && PERSIST && ONE && Cfg::CIN == 16;
+    static constexpr bool PERSIST_WLDS = PERSIST && ONE && Cfg::CIN == 16;
     static constexpr int WLDS_OFF = ((int)LDS_BYTES + 255) / 256 * 256;
     static constexpr size_t PERSIST_LDS_BYTES = PERSIST_WLDS ? (size_t)WLDS_OFF + (size_t)NSTEP * Cfg::MREP * 1024 : LDS_BYTES;
     // staging of the one-tile-per-block kernel: all loads of a pass issued back to back (registers: 8 per 256 voxel-octets of the
@@ -279,7 +235,6 @@ template <class Cfg, int T>
 __device__ __forceinline__ void bf_conv_load_w(const bf16x8* wq, bf16x8* ah, bf16x8* al) {
 #pragma unroll
     for (int mb = 0; mb < Cfg::MREP; ++mb) {
-        if (MVS_ABL == 2 && T > 1) continue;
         ah[mb] = wq[(size_t)((T * CfgSplit<Cfg>::MREP_ALL + mb) * 2) * 64];
         al[mb] = wq[(size_t)((T * CfgSplit<Cfg>::MREP_ALL + mb) * 2 + 1) * 64];
     }
@@ -306,7 +261,6 @@ __device__ __forceinline__ void bf_conv_load_x(int g, const char* ldsb, int voxb
     const char* p = ldsb + voxbase0 + sel;
 #pragma unroll
     for (int nb = 0; nb < Cfg::NREP; ++nb) {
-        if (MVS_ABL == 3 && T > 1) continue;
         bh[nb] = *reinterpret_cast<const bf16x8*>(p + nb * ROWB);
         if constexpr (!BfConv<Cfg>::F16) bl[nb] = *reinterpret_cast<const bf16x8*>(p + nb * ROWB + 16);
     }
@@ -321,14 +275,15 @@ __device__ __forceinline__ void bf_conv_load_step(int g, const bf16x8* wq, const
 
 // software-pipelined contraction of one staged channel chunk, fully unrolled.  Activations (LDS, ~100+ cycles) are requested
 // one step ahead into two alternating register sets; weights (L2, several hundred cycles under load - more than the 48-384
-// MFMA cycles of a step) MVS_WPF steps ahead into MVS_WPF + 1 rotating sets.  sched_barrier keeps the requests above the
+// MFMA cycles of a step) BF_WPF steps ahead into BF_WPF + 1 rotating sets.  sched_barrier keeps the requests above the
 // MFMAs they hide under.
+constexpr int BF_WPF = 1;          // weight prefetch distance of the forward convolutions in contraction steps (2, 3: +-2 %, not kept)
 template <class Cfg, int T>
 struct BfConvSteps {
-    static constexpr int WPF = MVS_WPF, NW = WPF + 1;
+    static constexpr int WPF = BF_WPF, NW = WPF + 1;
     static __device__ __forceinline__ void run(int g, const bf16x8* wq, const char* ldsb, int voxbase0, f32x4 (*acc)[Cfg::NREP],
                                                bf16x8 (*ah)[Cfg::MREP], bf16x8 (*al)[Cfg::MREP], bf16x8* bh0, bf16x8* bl0, bf16x8* bh1, bf16x8* bl1) {
-        constexpr int NSTEP = MVS_ABL == 6 ? 1 : BfConv<Cfg>::NSTEP;
+        constexpr int NSTEP = BfConv<Cfg>::NSTEP;
         if constexpr (T < NSTEP) {
             if constexpr (T + WPF < NSTEP) bf_conv_load_w<Cfg, T + WPF>(wq, ah[(T + WPF) % NW], al[(T + WPF) % NW]);
             if constexpr (T + 1 < NSTEP) {
@@ -343,11 +298,11 @@ struct BfConvSteps {
     }
 };
 
-// preload of the first MVS_WPF weight steps (requested by the caller before the tile is committed to LDS, so their L2 latency
+// preload of the first BF_WPF weight steps (requested by the caller before the tile is committed to LDS, so their L2 latency
 // runs under the split + barrier)
 template <class Cfg, int T = 0>
 __device__ __forceinline__ void bf_conv_preload_w(const bf16x8* wq, bf16x8 (*ah)[Cfg::MREP], bf16x8 (*al)[Cfg::MREP]) {
-    if constexpr (T < MVS_WPF && T < BfConv<Cfg>::NSTEP) {
+    if constexpr (T < BF_WPF && T < BfConv<Cfg>::NSTEP) {
         bf_conv_load_w<Cfg, T>(wq, ah[T], al[T]);
         bf_conv_preload_w<Cfg, T + 1>(wq, ah, al);
     }
@@ -372,9 +327,6 @@ __device__ __forceinline__ void bf_conv_contract(const bf16x8* wq, const char* l
 // its A fragments with conflict-free ds_read_b128 (lane-linear 16-byte slots).  TA traffic of a tile: weights once instead of once
 // per wave; the contraction issues no vector-memory instruction except the one prefetch per chunk.
 // ------------------------------------------------------------------------------------------------
-#ifndef MVS_WLDS
-#define MVS_WLDS 1
-#endif
 template <class Cfg>
 struct BfWlds {
     static constexpr int MREP_ALL = CfgSplit<Cfg>::MREP_ALL;
@@ -388,8 +340,8 @@ struct BfWlds {
     static constexpr size_t LDS_BYTES = (size_t)RING_OFF + 2 * CHUNK_BYTES;
     // Measured (profiles/r03_conv_weights_via_lds_ab.txt): +4 % on the 16 -> 16 layer (one output block: all four waves fetched the SAME
     // fragments, chunks of two steps).  With two or four output blocks the ring needs a barrier per step and, for 32 -> 32, costs the
-    // third resident workgroup: 32 -> 32 -22 %, 64 -> 64 -34 %, the strided layers -3 ... -11 %.  MVS_WLDS = 2 enables it everywhere.
-    static constexpr bool ENABLED = MVS_WLDS && !BfConv<Cfg>::PERSIST && NSTEP % WC == 0 && CHUNK_BYTES % 4096 == 0 && (MVS_WLDS > 1 || (MREP_ALL == 1 && WC == 2));
+    // third resident workgroup: 32 -> 32 -22 %, 64 -> 64 -34 %, the strided layers -3 ... -11 %.
+    static constexpr bool ENABLED = !BfConv<Cfg>::PERSIST && NSTEP % WC == 0 && CHUNK_BYTES % 4096 == 0 && MREP_ALL == 1 && WC == 2;
 };
 
 // global -> registers: this thread's pieces of global chunk `gc` (chunks are numbered through the passes: the packed weights are
@@ -399,7 +351,7 @@ template <class Cfg>
 __device__ __forceinline__ void bf_wlds_fetch(const void* wp, int gc, int nchunk_total, int tid, BfWPiece& piece) {
     using W = BfWlds<Cfg>;
     static_assert(W::NPIECE <= 2, "at most two pieces per thread and chunk");
-    if (gc >= nchunk_total || (MVS_ABL == 2 && gc > 0)) return;
+    if (gc >= nchunk_total) return;
     const float4* src = reinterpret_cast<const float4*>(reinterpret_cast<const char*>(wp) + (size_t)gc * W::CHUNK_BYTES);
     piece.a = src[tid];
     if constexpr (W::NPIECE > 1) piece.b = src[tid + 256];
@@ -431,7 +383,7 @@ struct BfWldsSteps {
                                                const char* ldsb, int voxbase0, f32x4 (*acc)[Cfg::NREP], BfWPiece& piece, bf16x8* bh0, bf16x8* bl0,
                                                bf16x8* bh1, bf16x8* bl1) {
         using W = BfWlds<Cfg>;
-        constexpr int NSTEP = MVS_ABL == 6 ? 1 : W::NSTEP;
+        constexpr int NSTEP = W::NSTEP;
         if constexpr (T < NSTEP) {
             const int gc = gc0 + T / W::WC;
             if constexpr (T % W::WC == 0) bf_wlds_fetch<Cfg>(wp, gc + 1, nchunk_total, tid, piece);       // next chunk: in flight under this chunk's MFMAs
@@ -465,8 +417,6 @@ __global__ __launch_bounds__(256) void conv3d_mfma_bf16x3_kernel(const float* __
     char* ldsb = reinterpret_cast<char*>(lds4);
     const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int li = lane & 15, g = lane >> 4;
-    start_stagger(2048);
-    prio_kernel_begin();
     int tile = (int)xcd_remap(blockIdx.x, (unsigned)ntiles);
     const int b = (int)blockIdx.y;
     const int tx = tile % tiles_x;
@@ -508,7 +458,7 @@ __global__ __launch_bounds__(256) void conv3d_mfma_bf16x3_kernel(const float* __
 #pragma unroll
         for (int it = 0; it < NIT; ++it) {
             if (it > 0) wk.advance();
-            const bool ok = MVS_ABL != 1 && (it * 256 + 255 < NITEM || tid + it * 256 < NITEM) && wk.inside(iz0, iy0, ix0, D, H, W);
+            const bool ok = (it * 256 + 255 < NITEM || tid + it * 256 < NITEM) && wk.inside(iz0, iy0, ix0, D, H, W);
             const unsigned voff = ok ? wk.off : BF_OOB;                     // out of the volume (or of the tile): zeros from the descriptor's range check
             su[it] = bf_buf_load16(xrs, voff, 0);
             if constexpr (!F16) sv[it] = bf_buf_load16(xrs, voff, 16);
@@ -537,7 +487,7 @@ __global__ __launch_bounds__(256) void conv3d_mfma_bf16x3_kernel(const float* __
     if constexpr (WLDS) bf_wlds_store<Cfg>(ring, 0, tid, piece);
     for (int pass = 0; pass < Cfg::NPASS; ++pass) {
         const bf16x8* wq = reinterpret_cast<const bf16x8*>(wp) + ((size_t)pass * NSTEP * MREP_ALL + mb0) * 2 * 64 + lane;
-        bf16x8 ah[MVS_WPF + 1][MREP], al[MVS_WPF + 1][MREP];
+        bf16x8 ah[BF_WPF + 1][MREP], al[BF_WPF + 1][MREP];
         if constexpr (!WLDS) bf_conv_preload_w<Cfg>(wq, ah, al);
         if (pass > 0 && !WLDS) __syncthreads();                   // (the weight ring's chunk barrier already separates the passes)
         if constexpr (UNROLLED) {
@@ -547,7 +497,7 @@ __global__ __launch_bounds__(256) void conv3d_mfma_bf16x3_kernel(const float* __
             int ldso = (tid / OPT) * SB + (tid % OPT) * BfConv<Cfg>::PLANE;
 #pragma unroll 1
             for (int e = tid; e < NITEM; e += 256) {
-                const bool ok = MVS_ABL != 1 && wk.inside(iz0, iy0, ix0, D, H, W);
+                const bool ok = wk.inside(iz0, iy0, ix0, D, H, W);
                 const unsigned voff = ok ? wk.off : BF_OOB;
                 const float4 u = bf_buf_load16(xrs, voff, 0);
                 if constexpr (F16) {
@@ -561,8 +511,7 @@ __global__ __launch_bounds__(256) void conv3d_mfma_bf16x3_kernel(const float* __
             }
         }
         __syncthreads();
-        if (UNROLLED && MVS_XPASS_PREFETCH && pass + 1 < Cfg::NPASS) issue(pass + 1);
-        prio_contract_begin();
+        if (UNROLLED && pass + 1 < Cfg::NPASS) issue(pass + 1);
         if constexpr (WLDS) {
             bf16x8 bh0[NREP], bl0[NREP], bh1[NREP], bl1[NREP];
             bf_conv_load_x<Cfg, 0>(g, ldsb, voxbase[0], bh0, bl0);
@@ -570,8 +519,6 @@ __global__ __launch_bounds__(256) void conv3d_mfma_bf16x3_kernel(const float* __
         } else {
             bf_conv_contract<Cfg>(wq, ldsb, voxbase, g, acc, ah, al);
         }
-        prio_contract_end();
-        if (UNROLLED && !MVS_XPASS_PREFETCH && pass + 1 < Cfg::NPASS) issue(pass + 1);
     }
 
     float* yb = reinterpret_cast<float*>(reinterpret_cast<char*>(y) + (size_t)b * OD * OH * OW * COUT * EB);
@@ -589,7 +536,6 @@ __global__ __launch_bounds__(256) void conv3d_mfma_bf16x3_kernel(const float* __
             const float4 bb = *reinterpret_cast<const float4*>(bias + (co < COUT ? co : 0));
             float4 v = make_float4(acc[mb][nb][0] + bb.x, acc[mb][nb][1] + bb.y, acc[mb][nb][2] + bb.z, acc[mb][nb][3] + bb.w);
             if (relu) { v.x = fmaxf(v.x, 0.0f); v.y = fmaxf(v.y, 0.0f); v.z = fmaxf(v.z, 0.0f); v.w = fmaxf(v.w, 0.0f); }
-            if (MVS_ABL == 5 && v.x != 12345.678f) continue;
             if constexpr (F16) *reinterpret_cast<f16x4*>(reinterpret_cast<_Float16*>(o) + co) = f16_pack4(v, sat_amax);
             else if (SPLIT) split_store_quad(o + (co & ~7), g, v, inside && co < COUT);
             else *reinterpret_cast<float4*>(o + co) = v;
@@ -699,9 +645,10 @@ __global__ __launch_bounds__(256) void conv3d_mfma_bf16x3_persist_kernel(const f
     char* yb = y ? reinterpret_cast<char*>(y) + (size_t)b * OD * OH * OW * COUT * EB : nullptr;
 
     constexpr int NITEM = Cfg::NVOX * OPT, NIT = (NITEM + 255) / 256;
-    // MVS_PERSIST_PFD register sets: the loads of tile t + PFD are issued while tile t is contracted
-    float4 su0[NIT], sv0[NIT], su1[NIT], sv1[NIT];
-    auto issue = [&](int tile, float4* su, float4* sv) {
+    // one register set: the loads of tile t + 1 are issued while tile t is contracted (a second set, two tiles ahead, costs the first
+    // U-Net layer a resident block, 82 vs 75 us, and changes nothing elsewhere)
+    float4 su[NIT], sv[NIT];
+    auto issue = [&](int tile) {
         const int tx = tile % tiles_x;
         const int t1 = tile / tiles_x;
         const int ty = t1 % tiles_y, tz = t1 / tiles_y;
@@ -712,13 +659,13 @@ __global__ __launch_bounds__(256) void conv3d_mfma_bf16x3_persist_kernel(const f
 #pragma unroll
         for (int it = 0; it < NIT; ++it) {
             if (it > 0) wk.advance();
-            const bool ok = MVS_ABL != 1 && (it * 256 + 255 < NITEM || tid + it * 256 < NITEM) && wk.inside(iz0, iy0, ix0, D, H, W);
+            const bool ok = (it * 256 + 255 < NITEM || tid + it * 256 < NITEM) && wk.inside(iz0, iy0, ix0, D, H, W);
             const unsigned voff = ok ? wk.off : BF_OOB;
             su[it] = bf_buf_load16(xrs, voff, 0);
             if constexpr (!F16) sv[it] = bf_buf_load16(xrs, voff, 16);
         }
     };
-    auto process = [&](int tile, float4* su, float4* sv) {
+    auto process = [&](int tile) {
 #pragma unroll
         for (int it = 0; it < NIT; ++it) {
             const int e = tid + it * 256;
@@ -728,7 +675,7 @@ __global__ __launch_bounds__(256) void conv3d_mfma_bf16x3_persist_kernel(const f
             else stage_to_lds<SPLIT>(ldsb + vox * SB + oc * BfConv<Cfg>::PLANE, su[it], sv[it]);
         }
         __syncthreads();
-        if (tile + MVS_PERSIST_PFD < t_end) issue(tile + MVS_PERSIST_PFD, su, sv);
+        if (tile + 1 < t_end) issue(tile + 1);
 
         f32x4 acc[MREP][NREP];
 #pragma unroll
@@ -753,7 +700,7 @@ __global__ __launch_bounds__(256) void conv3d_mfma_bf16x3_persist_kernel(const f
             if (!inside && (!SPLIT || logits != nullptr)) continue;          // split stores exchange lanes: every lane takes part
             if (logits != nullptr) {
                 // single-output-channel head (CostRegNet.prob, module.py:391): row 0 of the 16-row tile, planar store
-                if (g == 0 && !(MVS_ABL == 5 && acc[0][nb][0] != 12345.678f)) logits[(size_t)b * OD * OH * OW + ((size_t)oz * OH + oy) * OW + ox] = acc[0][nb][0] + bb[0].x;
+                if (g == 0) logits[(size_t)b * OD * OH * OW + ((size_t)oz * OH + oy) * OW + ox] = acc[0][nb][0] + bb[0].x;
                 continue;
             }
             float* o = reinterpret_cast<float*>(yb + (((size_t)oz * OH + oy) * OW + ox) * COUT * EB);
@@ -763,7 +710,6 @@ __global__ __launch_bounds__(256) void conv3d_mfma_bf16x3_persist_kernel(const f
                 if (!SPLIT && co >= COUT) continue;
                 float4 v = make_float4(acc[mb][nb][0] + bb[mb].x, acc[mb][nb][1] + bb[mb].y, acc[mb][nb][2] + bb[mb].z, acc[mb][nb][3] + bb[mb].w);
                 if (relu) { v.x = fmaxf(v.x, 0.0f); v.y = fmaxf(v.y, 0.0f); v.z = fmaxf(v.z, 0.0f); v.w = fmaxf(v.w, 0.0f); }
-                if (MVS_ABL == 5 && v.x != 12345.678f) continue;
                 if constexpr (F16) *reinterpret_cast<f16x4*>(reinterpret_cast<_Float16*>(o) + co) = f16_pack4(v, sat_amax);
                 else if (SPLIT) split_store_quad(o + (co & ~7), g, v, inside && co < COUT);
                 else *reinterpret_cast<float4*>(o + co) = v;
@@ -771,176 +717,18 @@ __global__ __launch_bounds__(256) void conv3d_mfma_bf16x3_persist_kernel(const f
         }
         __syncthreads();                                                     // every wave is done reading this tile's LDS image
     };
-    issue(t_begin, su0, sv0);
-    if (MVS_PERSIST_PFD == 2 && t_begin + 1 < t_end) issue(t_begin + 1, su1, sv1);
-    for (int tile = t_begin; tile < t_end; tile += MVS_PERSIST_PFD) {
-        process(tile, su0, sv0);
-        if (MVS_PERSIST_PFD == 2 && tile + 1 < t_end) process(tile + 1, su1, sv1);
-    }
+    issue(t_begin);
+    for (int tile = t_begin; tile < t_end; ++tile) process(tile);
     if constexpr (F16) sat::commit(sat_amax);
 }
 
-// ------------------------------------------------------------------------------------------------
-// Loader-wave form of the fp16 tile convolutions (round 4): 4 contracting waves + 1 wave that only moves data.
-//
-// Why.  Every one-tile kernel above runs ~2.5x above BOTH of its floors (stage-4 16 -> 16: 58 us against 22 us of MFMA issue and 19 us
-// of HBM time; 32 -> 32 and the transposed layers alike), and the counters say the SIMDs wait (wait 38-48 %, stall 33-43 %, MFMA busy
-// 22-24 %).  A block's life is load tile -> commit -> contract -> store; the co-resident blocks of a CU start together and stay in step,
-// so the chip alternates between a phase in which nobody contracts and a phase in which nobody has loads in flight (round 2's ablation:
-// the phases ADD).  Bytes in flight are what a latency-bound stream is made of: ~18 KB per CU on average in the one-tile form.  The
-// remedy is a block that prefetches the next tile while it contracts this one - but a wave that loads weights in its contraction cannot
-// also have the prefetch in flight: vmcnt retires in order, so the first weight it waits for drags the whole prefetch along (round 3's
-// LDS-DMA kernel issued both from the same waves and lost 1.2-1.8x).  Hence a FIFTH wave with its own vmcnt: it copies chunk c + 1
-// (one tile x one pass of 16 / 8 input channels) into the other LDS image with LDS-DMA (global_load_lds_dwordx4: no registers, no
-// ds_write; lanes outside the volume read a zeroed 16-byte line), while waves 0-3 contract chunk c exactly as the one-tile kernel does
-// (same operand layout, same weight path through L2).  One barrier per chunk; blocks are persistent over a contiguous run of tiles.
-// fp16 activations only (both weight forms); the Cin = 8 layers keep their weights-in-registers persistent form.
-// ------------------------------------------------------------------------------------------------
-// MEASURED (profiles/r04_conv_loader_ab.txt, stage-4 shapes, us per launch, loader form vs one-tile form): 16 -> 16 two-term 75.1 vs 57.0,
-// 32 -> 32 54.7 vs 58.5, 64 -> 64 54.9 vs 49.2, 16 -> 32 s122 53.4 vs 43.9, 32 -> 64 s122 49.2 vs 38.8; one-term weights: 32 -> 32 38.6 vs
-// 32.2, 64 -> 64 50.0 vs 32.6; whole path 539 vs 572 ref-views/s.  The pipelined form loses: 152 VGPRs and two 20-KB images leave 3 blocks
-// of 4 contracting waves per CU where the one-tile form holds 4-5, and one loader wave fills LDS at ~25 GB/s per CU (MI355X_MICROARCH.md
-// "ldsdma-fill"), i.e. a 20-KB chunk takes about as long as its contraction.  Resident waves, not bytes in flight, carry these kernels.
-// Kept as an experiment (MVS_CONV_LOADER=1 builds it; MVS_CONV_LOADER_OFF=1 then switches it off at run time); not compiled by default.
-#ifndef MVS_CONV_LOADER
-#define MVS_CONV_LOADER 0
-#endif
-#if MVS_CONV_LOADER
-__device__ float4 g_conv_zero_line[4];               // zero-initialised: the source of every out-of-volume run
-
-template <class Cfg>
-struct BfConvLd {
-    static constexpr int OPT = BfConv<Cfg>::OPT;
-    static constexpr int IMG = ((int)BfConv<Cfg>::LDS_BYTES + 255) / 256 * 256;     // one staged chunk; two of them ping-pong
-    static constexpr int NPC = (Cfg::NVOX + 63) / 64;                               // 1-KiB pieces per octet plane
-    static constexpr int NP = OPT * NPC;
-    static constexpr size_t LDS_BYTES = (size_t)2 * IMG;
-    static constexpr bool ENABLED = MVS_CONV_LOADER && BfConv<Cfg>::F16 && !BfConv<Cfg>::PERSIST && Cfg::KD == 3;
-};
-
-template <class Cfg>
-__global__ __launch_bounds__(320) void conv3d_mfma_f16_loader_kernel(const _Float16* __restrict__ x, const void* wp, const float* __restrict__ bias,
-                                                                     _Float16* __restrict__ y, int D, int H, int W, int OD, int OH, int OW,
-                                                                     int relu, int tiles_x, int tiles_y, int ntiles) {
-    constexpr int CIN = Cfg::CIN, COUT = Cfg::COUT, SD = Cfg::SD, SH = Cfg::SH, SW = Cfg::SW, TD = Cfg::TD, TH = Cfg::TH, CH = Cfg::CH;
-    constexpr int IH = Cfg::IH, IW = Cfg::IW, MREP = Cfg::MREP, NREP = Cfg::NREP, NPASS = Cfg::NPASS, NVOX = Cfg::NVOX;
-    constexpr int NSTEP = BfConv<Cfg>::NSTEP, SB = BfConv<Cfg>::SB, PLANE = BfConv<Cfg>::PLANE;
-    constexpr int IMG = BfConvLd<Cfg>::IMG, NPC = BfConvLd<Cfg>::NPC, NP = BfConvLd<Cfg>::NP;
-    static_assert(BfConv<Cfg>::F16 && SB == 16, "fp16 activations: 16 bytes per voxel and octet");
-    HIP_DYNAMIC_SHARED(float4, lds4)
-    char* lds = reinterpret_cast<char*>(lds4);
-    const int tid = (int)threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int b = (int)blockIdx.y;
-    // a contiguous run of tiles per block; neighbouring runs on the same XCD (shared halo rows hit its L2)
-    const int nblk = (int)gridDim.x, per = (ntiles + nblk - 1) / nblk;
-    const int t_begin = (int)xcd_remap(blockIdx.x, (unsigned)nblk) * per;
-    const int t_end = t_begin + per < ntiles ? t_begin + per : ntiles;
-    if (t_begin >= t_end) return;
-    const int nchunk = (t_end - t_begin) * NPASS;
-    const char* xb = reinterpret_cast<const char*>(x) + (size_t)b * D * H * W * CIN * 2;
-
-    if (wave == 4) {
-        // ---------------- loader wave: piece k = 64 consecutive voxels of octet plane k / NPC; lane -> voxel 64 (k % NPC) + lane
-        const char* zero = reinterpret_cast<const char*>(g_conv_zero_line);
-        int crd[NPC];                                           // packed tile-local halo coordinates dz << 16 | dy << 8 | dx, -1: no such voxel
-        int rel[NPC];                                           // byte offset of the voxel from the tile's first halo voxel
-#pragma unroll
-        for (int k = 0; k < NPC; ++k) {
-            const int v = 64 * k + lane;
-            const int dx = v % IW, t2 = v / IW, dy = t2 % IH, dz = t2 / IH;
-            crd[k] = v < NVOX ? (dz << 16 | dy << 8 | dx) : -1;
-            rel[k] = ((dz * H + dy) * W + dx) * (CIN * 2);
-        }
-        auto issue = [&](int c, int buf) {
-            const int tile = t_begin + c / NPASS, pass = c - (c / NPASS) * NPASS;
-            const int tx = tile % tiles_x, t1 = tile / tiles_x;
-            const int ty = t1 % tiles_y, tz = t1 / tiles_y;
-            const int iz0 = tz * TD * SD - Cfg::PD, iy0 = ty * TH * SH - 1, ix0 = tx * 16 * SW - 1;
-            const long long base = ((long long)(iz0 * H + iy0) * W + ix0) * (CIN * 2) + pass * (CH * 2);
-            char* img = lds + buf * IMG;
-#pragma unroll
-            for (int k = 0; k < NPC; ++k) {
-                if (crd[k] < 0) continue;                       // tail of the plane: these lanes take no part (their LDS slots lie beyond the plane)
-                const int z = iz0 + (crd[k] >> 16), yy = iy0 + ((crd[k] >> 8) & 0xff), xx = ix0 + (crd[k] & 0xff);
-                const bool ok = MVS_ABL != 1 && (unsigned)z < (unsigned)D && (unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W;
-#pragma unroll
-                for (int oc = 0; oc < BfConvLd<Cfg>::OPT; ++oc) {
-                    const char* src = ok ? xb + base + rel[k] + oc * 16 : zero;
-                    MVS_GLOBAL_LOAD_LDS16(src, img + oc * PLANE + k * 1024);
-                }
-            }
-        };
-        issue(0, 0);
-        MVS_WAIT_VMEM();
-        __syncthreads();                                        // chunk 0 is in LDS
-        for (int c = 0; c < nchunk; ++c) {
-            if (c + 1 < nchunk) issue(c + 1, (c + 1) & 1);      // lands while waves 0-3 contract chunk c
-            MVS_WAIT_VMEM();
-            __syncthreads();                                    // chunk c + 1 visible; everybody has left chunk c (its image is free for c + 2)
-        }
-        return;
-    }
-
-    // ---------------- contracting waves: the one-tile kernel's mapping (tid 0..255)
-    float sat_amax = 0.0f;
-    const int li = lane & 15, g = lane >> 4;
-    constexpr int MSPLIT = CfgSplit<Cfg>::MSPLIT, MREP_ALL = CfgSplit<Cfg>::MREP_ALL;
-    const int mb0 = (wave % MSPLIT) * MREP, rowgrp = wave / MSPLIT;       // this wave's output blocks and rows (SplitCfg)
-    int voxbase[NREP];
-#pragma unroll
-    for (int nb = 0; nb < NREP; ++nb) {
-        const int nbg = rowgrp * NREP + nb;
-        const int oz = nbg / TH, oy = nbg % TH;
-        voxbase[nb] = (((oz * SD) * IH + oy * SH) * IW + li * SW) * SB;
-    }
-    float4 bb[MREP];
-#pragma unroll
-    for (int mb = 0; mb < MREP; ++mb) {
-        const int co = 16 * (mb0 + mb) + 4 * g;
-        bb[mb] = co < COUT ? *reinterpret_cast<const float4*>(bias + co) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    }
-    _Float16* yb = y + (size_t)b * OD * OH * OW * COUT;
-    f32x4 acc[MREP][NREP];
-    __syncthreads();                                            // chunk 0 is in LDS
-    for (int c = 0; c < nchunk; ++c) {
-        const int tile = t_begin + c / NPASS, pass = c - (c / NPASS) * NPASS;
-        const char* cur = lds + (c & 1) * IMG;
-        const bf16x8* wq = reinterpret_cast<const bf16x8*>(wp) + ((size_t)pass * NSTEP * MREP_ALL + mb0) * 2 * 64 + lane;
-        bf16x8 ah[MVS_WPF + 1][MREP], al[MVS_WPF + 1][MREP];
-        bf_conv_preload_w<Cfg>(wq, ah, al);
-        if (pass == 0) {
-#pragma unroll
-            for (int mb = 0; mb < MREP; ++mb)
-#pragma unroll
-                for (int nb = 0; nb < NREP; ++nb) acc[mb][nb] = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
-        }
-        bf_conv_contract<Cfg>(wq, cur, voxbase, g, acc, ah, al);
-        if (pass == NPASS - 1) {
-            const int tx = tile % tiles_x, t1 = tile / tiles_x;
-            const int ty = t1 % tiles_y, tz = t1 / tiles_y;
-            const int oz0 = tz * TD, oy0 = ty * TH, ox0 = tx * 16;
-#pragma unroll
-            for (int nb = 0; nb < NREP; ++nb) {
-                const int nbg = rowgrp * NREP + nb;
-                const int oz = oz0 + nbg / TH, oy = oy0 + nbg % TH, ox = ox0 + li;
-                if (!(oz < OD && oy < OH && ox < OW)) continue;
-                _Float16* o = yb + (((size_t)oz * OH + oy) * OW + ox) * COUT;
-#pragma unroll
-                for (int mb = 0; mb < MREP; ++mb) {
-                    const int co = 16 * (mb0 + mb) + 4 * g;
-                    if (co >= COUT) continue;
-                    float4 v = make_float4(acc[mb][nb][0] + bb[mb].x, acc[mb][nb][1] + bb[mb].y, acc[mb][nb][2] + bb[mb].z, acc[mb][nb][3] + bb[mb].w);
-                    if (relu) { v.x = fmaxf(v.x, 0.0f); v.y = fmaxf(v.y, 0.0f); v.z = fmaxf(v.z, 0.0f); v.w = fmaxf(v.w, 0.0f); }
-                    *reinterpret_cast<f16x4*>(o + co) = f16_pack4(v, sat_amax);
-                }
-            }
-        }
-        __syncthreads();                                        // chunk c + 1 has landed; this chunk's image may be overwritten
-    }
-    sat::commit(sat_amax);
-}
-#endif  // MVS_CONV_LOADER
+// (Round 4 measured a loader-wave form of the fp16 tile convolutions - 4 contracting waves + a fifth wave with its own vmcnt that copies
+// the next chunk into a second LDS image with LDS-DMA, blocks persistent over a run of tiles.  It loses (profiles/r04_conv_loader_ab.txt,
+// stage-4 shapes, us per launch, loader form vs one-tile form): 16 -> 16 two-term 75.1 vs 57.0, 32 -> 32 54.7 vs 58.5, 64 -> 64 54.9 vs 49.2,
+// 16 -> 32 s122 53.4 vs 43.9, 32 -> 64 s122 49.2 vs 38.8; one-term weights: 32 -> 32 38.6 vs 32.2, 64 -> 64 50.0 vs 32.6; whole path 539 vs
+// 572 ref-views/s: 152 VGPRs and two 20-KB images leave 3 blocks of 4 contracting waves per CU where the one-tile form holds 4-5, and one
+// loader wave fills LDS at ~25 GB/s per CU (MI355X_MICROARCH.md "ldsdma-fill"), i.e. a 20-KB chunk takes about as long as its contraction.
+// Resident waves, not bytes in flight, carry these kernels.  The kernel lives in git history, commit ff86576.)
 
 // ------------------------------------------------------------------------------------------------
 // ConvTranspose3d (parity classes as in conv_kernels.hip)
@@ -953,16 +741,13 @@ struct BfDeconv {
     // groups that share a ds_read_b128 service group (g, g ^ 1) always read ADJACENT octets of one tap (OPT is 2, 4 or 8), i.e.
     // addresses PLANE apart: 16 different bank slots.  (The interleaved (CIN + 4)-float voxel of rounds 1-2 2-way conflicted on
     // every read: PMC SQ_LDS_BANK_CONFLICT = 46-50 % of the LDS cycles of the 32 -> 16 and 64 -> 32 layers, round-3 pass.)
-#ifndef MVS_DECONV_PLANES
-#define MVS_DECONV_PLANES 1
-#endif
     // fp16 activations (F16Cfg): 16 B per voxel and octet, plane offset as BfConv (stride-1 reads)
     static constexpr bool F16 = CfgFmt<Cfg>::F16;
     static constexpr int RUNB = F16 ? 16 : 32;
-    static constexpr int SB = F16 ? 16 : (MVS_DECONV_PLANES ? 32 : Cfg::S * 4);
+    static constexpr int SB = F16 ? 16 : 32;
     static constexpr int PLANE = F16 ? (Cfg::NVOX * 16 + 255) / 256 * 256 + bf_f16_plane_shift(1)
-                                     : (MVS_DECONV_PLANES ? (Cfg::NVOX * 32 + 255) / 256 * 256 + 16 : 32);     // byte offset between octets
-    static constexpr size_t LDS_BYTES = (F16 || MVS_DECONV_PLANES) ? (size_t)OPT * PLANE : Cfg::LDS_BYTES;
+                                     : (Cfg::NVOX * 32 + 255) / 256 * 256 + 16;     // byte offset between octets
+    static constexpr size_t LDS_BYTES = (size_t)OPT * PLANE;
 };
 
 template <class Cfg, bool ONE = false>
@@ -982,13 +767,11 @@ __device__ __forceinline__ void bf_deconv_load_step(int st, int ntap, int pd, in
     const int ldsoff = ((od * Cfg::LH + oh) * Cfg::LW + ow) * BfDeconv<Cfg>::SB + oc * BfDeconv<Cfg>::PLANE;
 #pragma unroll
     for (int mb = 0; mb < Cfg::MREP; ++mb) {
-        if (MVS_ABL == 2 && st > 1) continue;
         ah[mb] = wq[(size_t)((st * CfgSplit<Cfg>::MREP_ALL + mb) * 2) * 64];
         if constexpr (!ONE) al[mb] = wq[(size_t)((st * CfgSplit<Cfg>::MREP_ALL + mb) * 2 + 1) * 64];
     }
 #pragma unroll
     for (int nb = 0; nb < Cfg::NREP; ++nb) {
-        if (MVS_ABL == 3 && st > 1) continue;
         bh[nb] = *reinterpret_cast<const bf16x8*>(ldsb + voxbase[nb] + ldsoff);
         if constexpr (!BfDeconv<Cfg>::F16) bl[nb] = *reinterpret_cast<const bf16x8*>(ldsb + voxbase[nb] + ldsoff + 16);
     }
@@ -1006,26 +789,16 @@ __device__ __forceinline__ void bf_deconv_load_step(int st, int ntap, int pd, in
 // class: every class still sums the same K groups in the same order (and the same term order per accumulator) - the outputs are
 // bit-identical to the per-class loop.  The packed weights stay class by class (wstep: the class base plus the tap's place in it).
 // ------------------------------------------------------------------------------------------------
-#ifndef MVS_DECONV_ONE_TERM
-#define MVS_DECONV_ONE_TERM 1      // the one-tile transposed kernels honour the one-term fp16 format (0: both weight terms, as rounds 4-6 shipped)
-#endif
-#ifndef MVS_DECONV_FUSED_DEFAULT
-#define MVS_DECONV_FUSED_DEFAULT 1 // 0: the dispatch never picks the class-fused walk by itself (MVS_DECONV_CLASS_FUSED=1 still forces it)
-#endif
-#ifndef MVS_DECONV_WPF
-#define MVS_DECONV_WPF 0           // class-fused walk: weight prefetch distance in K steps (0: one weight set, refilled in place)
-#endif
 template <class Cfg>
 struct BfDeconvF {
     static constexpr bool ENABLED = Cfg::SD == 1 && (Cfg::CIN == 32 || Cfg::CIN == 64) && Cfg::COUT >= 16;
-    static constexpr bool F16 = CfgFmt<Cfg>::F16, ONE = MVS_DECONV_ONE_TERM && CfgFmt<Cfg>::ONE;
+    static constexpr bool F16 = CfgFmt<Cfg>::F16, ONE = CfgFmt<Cfg>::ONE;     // the one-tile transposed kernels honour the one-term fp16 format
     // which form the dispatch picks when MVS_DECONV_CLASS_FUSED is unset: the walk where it measured faster than the loop - the one-term 64 -> 32
     // layer (38.4 / 23.4 us against 41.0 / 24.2 at stage 4 / 3).  The four accumulator sets cost a resident wave (4 per SIMD against 5-6) and
     // these kernels live on the latency their waves hide: two-term 32 -> 16 60.8 / 32.1 against 57.8 / 31.9, two-term 64 -> 32 53.4 / 32.2 against 52.6 / 32.3
-    static constexpr bool DEFAULT = ENABLED && MVS_DECONV_FUSED_DEFAULT && ONE && Cfg::CIN == 64;
+    static constexpr bool DEFAULT = ENABLED && ONE && Cfg::CIN == 64;
     static constexpr int SPT = BfDeconv<Cfg>::OPT / 4;                     // K = 32 steps per tap
     static constexpr int NSTEP = 12 * SPT;                                // steps of the walk: position U / SPT, channel half U % SPT
-    static constexpr int NW = MVS_DECONV_WPF + 1;
     static constexpr int ROWB = Cfg::LW * BfDeconv<Cfg>::SB;              // bytes between a wave's consecutive rows
     // position p = 0..11 <-> od = 1 - p / 4, oh = 1 - (p >> 1 & 1), ow = 1 - (p & 1); class cls = 2 ph + pw
     static constexpr bool uses(int cls, int p) { return ((cls & 2) || (p & 2)) && ((cls & 1) || (p & 1)); }
@@ -1044,14 +817,13 @@ struct BfDeconvF {
     static_assert(!ENABLED || Cfg::THM % Cfg::NREP == 0, "a wave's rows must stay inside one input plane");
 };
 
-// WHICH: 1 = w_lo, 2 = w_hi, 3 = both; WHEN (the in-place refill of MVS_DECONV_WPF = 0): 0 = every class step U uses, 1 = only the classes step U - 1
+// WHICH: 1 = w_lo, 2 = w_hi, 3 = both; WHEN (the in-place refill of the one weight set): 0 = every class step U uses, 1 = only the classes step U - 1
 // uses too (their registers are free once step U - 1 has issued its MFMAs on them), 2 = only the classes step U - 1 does not use
 template <class Cfg, int U, int CLS, int WHICH = 3, int WHEN = 0>
 __device__ __forceinline__ void bfdf_load_w(__amdgpu_buffer_rsrc_t wrs, unsigned wvoff, bf16x8* ah, bf16x8* al) {
     using P = BfDeconvF<Cfg>;
     constexpr bool prev = U > 0 && P::uses(CLS, (U > 0 ? U - 1 : 0) / P::SPT);
     if constexpr (P::uses(CLS, U / P::SPT) && (WHEN == 0 || (WHEN == 1) == prev)) {
-        if (MVS_ABL == 2 && U > 1) return;
 #pragma unroll
         for (int mb = 0; mb < Cfg::MREP; ++mb) {
             constexpr int MREP_ALL = CfgSplit<Cfg>::MREP_ALL;
@@ -1073,7 +845,6 @@ __device__ __forceinline__ void bfdf_load_x(const char* px, bf16x8* bh, bf16x8* 
     using P = BfDeconvF<Cfg>;
 #pragma unroll
     for (int nb = 0; nb < Cfg::NREP; ++nb) {
-        if (MVS_ABL == 3 && U > 1) continue;
         bh[nb] = *reinterpret_cast<const bf16x8*>(px + P::xoff(U) + nb * P::ROWB);
         if constexpr (!P::F16) bl[nb] = *reinterpret_cast<const bf16x8*>(px + P::xoff(U) + nb * P::ROWB + 16);
     }
@@ -1106,35 +877,34 @@ __device__ __forceinline__ void bfdf_mfma_all(bf16x8 (*ah)[Cfg::MREP], bf16x8 (*
 }
 
 // the walk, fully unrolled and software-pipelined as the forward convolutions: LDS operands one step ahead in two alternating register
-// sets, weights MVS_DECONV_WPF steps ahead in rotating sets; sched_barrier keeps the requests above the MFMAs they hide under.
-// MVS_DECONV_WPF = 0 keeps ONE weight set and refills it in place: a class's w_lo of step U + 1 is requested as soon as step U's lo term
+// sets; sched_barrier keeps the requests above the MFMAs they hide under.
+// The weights live in ONE register set that is refilled in place: a class's w_lo of step U + 1 is requested as soon as step U's lo term
 // has been issued, its w_hi after the last term - nearly a step ahead at half the weight registers (these kernels are paced by the
 // latency their resident waves hide, and a second weight set costs one to two of them).
 template <class Cfg, int U>
 struct BfDeconvFSteps {
     using P = BfDeconvF<Cfg>;
     static __device__ __forceinline__ void run(__amdgpu_buffer_rsrc_t wrs, unsigned wvoff, const char* px, f32x4 (*acc)[Cfg::MREP][Cfg::NREP],
-                                               bf16x8 (*ah)[4][Cfg::MREP], bf16x8 (*al)[4][Cfg::MREP], bf16x8 (*bh)[Cfg::NREP], bf16x8 (*bl)[Cfg::NREP]) {
-        constexpr int NSTEP = MVS_ABL == 6 ? 1 : P::NSTEP, WPF = MVS_DECONV_WPF, NW = P::NW;
+                                               bf16x8 (*ah)[Cfg::MREP], bf16x8 (*al)[Cfg::MREP], bf16x8 (*bh)[Cfg::NREP], bf16x8 (*bl)[Cfg::NREP]) {
+        constexpr int NSTEP = P::NSTEP;
         constexpr bool NEXT = U + 1 < NSTEP;
         if constexpr (U < NSTEP) {
-            if constexpr (WPF > 0 && U + WPF < NSTEP) bfdf_load_w_all<Cfg, U + WPF>(wrs, wvoff, ah[(U + WPF) % NW], al[(U + WPF) % NW]);
-            if constexpr (WPF == 0 && NEXT) bfdf_load_w_all<Cfg, U + 1, 3, 2>(wrs, wvoff, ah[0], al[0]);
+            if constexpr (NEXT) bfdf_load_w_all<Cfg, U + 1, 3, 2>(wrs, wvoff, ah, al);
             if constexpr (NEXT) bfdf_load_x<Cfg, U + 1>(px, bh[(U + 1) & 1], bl[(U + 1) & 1]);
             __builtin_amdgcn_sched_barrier(0);
             if constexpr (!P::ONE) {
-                bfdf_mfma_all<Cfg, U, 0>(ah[U % NW], al[U % NW], bh[U & 1], bl[U & 1], acc);
-                if constexpr (WPF == 0 && NEXT) {
+                bfdf_mfma_all<Cfg, U, 0>(ah, al, bh[U & 1], bl[U & 1], acc);
+                if constexpr (NEXT) {
                     __builtin_amdgcn_sched_barrier(0);
-                    bfdf_load_w_all<Cfg, U + 1, 1, 1>(wrs, wvoff, ah[0], al[0]);
+                    bfdf_load_w_all<Cfg, U + 1, 1, 1>(wrs, wvoff, ah, al);
                     __builtin_amdgcn_sched_barrier(0);
                 }
             }
-            if constexpr (!P::F16) bfdf_mfma_all<Cfg, U, 1>(ah[U % NW], al[U % NW], bh[U & 1], bl[U & 1], acc);
-            bfdf_mfma_all<Cfg, U, P::F16 ? 1 : 2>(ah[U % NW], al[U % NW], bh[U & 1], bl[U & 1], acc);
-            if constexpr (WPF == 0 && NEXT) {
+            if constexpr (!P::F16) bfdf_mfma_all<Cfg, U, 1>(ah, al, bh[U & 1], bl[U & 1], acc);
+            bfdf_mfma_all<Cfg, U, P::F16 ? 1 : 2>(ah, al, bh[U & 1], bl[U & 1], acc);
+            if constexpr (NEXT) {
                 __builtin_amdgcn_sched_barrier(0);
-                bfdf_load_w_all<Cfg, U + 1, 2, 1>(wrs, wvoff, ah[0], al[0]);
+                bfdf_load_w_all<Cfg, U + 1, 2, 1>(wrs, wvoff, ah, al);
             }
             BfDeconvFSteps<Cfg, U + 1>::run(wrs, wvoff, px, acc, ah, al, bh, bl);
         }
@@ -1157,8 +927,6 @@ __global__ __launch_bounds__(256) void deconv3d_mfma_bf16x3_kernel(const float* 
     char* ldsb = reinterpret_cast<char*>(lds4);
     const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int li = lane & 15, g = lane >> 4;
-    start_stagger(2048);
-    prio_kernel_begin();
     int tile = (int)xcd_remap(blockIdx.x, (unsigned)ntiles);
     const int b = (int)blockIdx.y;
     const int tx = tile % tiles_x;
@@ -1176,7 +944,7 @@ __global__ __launch_bounds__(256) void deconv3d_mfma_bf16x3_kernel(const float* 
         BfTileWalk<LW, LH, OPT, RUNB> wk(tid, zrel, my0, mx0, H, W, CIN * EB, 0u);
         int ldso = (tid / OPT) * SB + (tid % OPT) * BfDeconv<Cfg>::PLANE;
         for (int e = tid; e < Cfg::NVOX * OPT; e += 256) {
-            const bool ok = MVS_ABL != 1 && wk.inside(mz0 - Cfg::ZO, my0, mx0, D, H, W);
+            const bool ok = wk.inside(mz0 - Cfg::ZO, my0, mx0, D, H, W);
             const unsigned voff = ok ? wk.off : BF_OOB;
             const float4 u = bf_buf_load16(xrs, voff, 0);
             if constexpr (F16) {
@@ -1241,7 +1009,7 @@ __global__ __launch_bounds__(256) void deconv3d_mfma_bf16x3_kernel(const float* 
             }
         }
     }
-    constexpr bool ONE = MVS_DECONV_ONE_TERM && CfgFmt<Cfg>::ONE;          // one fp16 weight term: w_lo is neither loaded nor multiplied
+    constexpr bool ONE = CfgFmt<Cfg>::ONE;                                 // one fp16 weight term: w_lo is neither loaded nor multiplied
     // FUSED: all four classes are contracted here, in one walk over the 12 input positions (BfDeconvF); the class loop below keeps the epilogues
     f32x4 accf[FUSED ? 4 : 1][MREP][NREP];
     if constexpr (FUSED) {
@@ -1256,14 +1024,10 @@ __global__ __launch_bounds__(256) void deconv3d_mfma_bf16x3_kernel(const float* 
         const __amdgpu_buffer_rsrc_t wrs = bf_make_rsrc(wp, (unsigned)(27 * P::SPT * MREP_ALL * 2 * 1024));
         const unsigned wvoff = (unsigned)((mb0 * 2 * 64 + lane) * 16);
         const char* px = ldsb + voxbase[0] - LH * LW * SB + g * BfDeconv<Cfg>::PLANE;
-        bf16x8 ah[P::NW][4][MREP], al[P::NW][4][MREP], bh[2][NREP], bl[2][NREP];
-        static_assert(MVS_DECONV_WPF >= 0 && MVS_DECONV_WPF <= 2, "weight prefetch distance of the class-fused walk");
-        prio_contract_begin();
-        bfdf_load_w_all<Cfg, 0>(wrs, wvoff, ah[0], al[0]);
-        if constexpr (MVS_DECONV_WPF > 1) bfdf_load_w_all<Cfg, 1>(wrs, wvoff, ah[1], al[1]);
+        bf16x8 ah[4][MREP], al[4][MREP], bh[2][NREP], bl[2][NREP];
+        bfdf_load_w_all<Cfg, 0>(wrs, wvoff, ah, al);
         bfdf_load_x<Cfg, 0>(px, bh[0], bl[0]);
         BfDeconvFSteps<Cfg, 0>::run(wrs, wvoff, px, accf, ah, al, bh, bl);
-        prio_contract_end();
     }
 #pragma unroll
     for (int cls = 0; cls < NCLS; cls += PAIR ? 2 : 1) {
@@ -1281,9 +1045,8 @@ __global__ __launch_bounds__(256) void deconv3d_mfma_bf16x3_kernel(const float* 
 #pragma unroll
                 for (int nb = 0; nb < NREP; ++nb) acc[mb][nb] = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
             const int ntap = ((SD == 2) ? (pd ? 2 : 1) : 3) * (ph ? 2 : 1) * (pw ? 2 : 1);
-            const int nst = MVS_ABL == 6 ? 1 : (ntap * OPT + 3) / 4;
+            const int nst = (ntap * OPT + 3) / 4;
             bf16x8 ah0[MREP], al0[MREP], bh0[NREP], bl0[NREP], ah1[MREP], al1[MREP], bh1[NREP], bl1[NREP];
-            prio_contract_begin();
             bf_deconv_load_step<Cfg, ONE>(0, ntap, pd, ph, pw, g, wq, ldsb, voxbase, ah0, al0, bh0, bl0);
 #pragma unroll 1
             for (int st = 0; st + 1 < nst; st += 2) {
@@ -1295,7 +1058,6 @@ __global__ __launch_bounds__(256) void deconv3d_mfma_bf16x3_kernel(const float* 
                 bf_mfma_step<MREP, NREP, F16, ONE>(ah1, al1, bh1, bl1, acc);
             }
             if (nst & 1) bf_mfma_step<MREP, NREP, F16, ONE>(ah0, al0, bh0, bl0, acc);
-            prio_contract_end();
             wq += (size_t)nst * MREP_ALL * 2 * 64;
         }
 
@@ -1325,13 +1087,13 @@ __global__ __launch_bounds__(256) void deconv3d_mfma_bf16x3_kernel(const float* 
                     part += v.z * pw4.z;
                     part += v.w * pw4.w;
                     part += __shfl_xor(part, 16);
-                    if ((g & 1) == 0 && inside && !(MVS_ABL == 5 && part != 12345.678f)) logits[(size_t)b * OD * OH * OW + ((size_t)oz * OH + oy) * OW + ox] = part + prob_b[0];
+                    if ((g & 1) == 0 && inside) logits[(size_t)b * OD * OH * OW + ((size_t)oz * OH + oy) * OW + ox] = part + prob_b[0];
                 } else if (F16) {
                     if (inside) *reinterpret_cast<f16x4*>(reinterpret_cast<_Float16*>(yb) + off) = f16_pack4(v, sat_amax);
                 } else if (SPLIT) {
                     split_store_quad(yb + off - co, g, v, inside);
                 } else {
-                    if (!(MVS_ABL == 5 && v.x != 12345.678f)) *reinterpret_cast<float4*>(yb + off) = v;
+                    *reinterpret_cast<float4*>(yb + off) = v;
                 }
                 continue;
             }
@@ -1348,7 +1110,6 @@ __global__ __launch_bounds__(256) void deconv3d_mfma_bf16x3_kernel(const float* 
                     const float4 sk = F16 ? f16_quad_to_f32(skp[it][nb][mb]) : SPLIT ? split_join_quad(skp[it][nb][mb]) : skp[it][nb][mb];
                     v.x += sk.x; v.y += sk.y; v.z += sk.z; v.w += sk.w;
                 }
-                if (MVS_ABL == 5 && v.x != 12345.678f) continue;
                 if constexpr (F16) *reinterpret_cast<f16x4*>(reinterpret_cast<_Float16*>(yb) + off + co) = f16_pack4(v, sat_amax);
                 else if (SPLIT) split_store_quad(yb + off + (co & ~7), g, v, inside && co < COUT);
                 else *reinterpret_cast<float4*>(yb + off + co) = v;
@@ -1495,7 +1256,7 @@ __global__ __launch_bounds__(256) void deconv3d_mfma_bf16x3_persist_kernel(const
 #pragma unroll
         for (int it = 0; it < NITX; ++it) {
             if (it > 0) wk.advance();
-            const bool ok = MVS_ABL != 1 && (it * 256 + 255 < NITEM || tid + it * 256 < NITEM) && wk.inside(mz0 - Cfg::ZO, my0, mx0, D, H, W);
+            const bool ok = (it * 256 + 255 < NITEM || tid + it * 256 < NITEM) && wk.inside(mz0 - Cfg::ZO, my0, mx0, D, H, W);
             const unsigned voff = ok ? wk.off : BF_OOB;
             su[it] = bf_buf_load16(xrs, voff, 0);
             if constexpr (!F16) sv[it] = bf_buf_load16(xrs, voff, 16);
@@ -1586,14 +1347,14 @@ __global__ __launch_bounds__(256) void deconv3d_mfma_bf16x3_persist_kernel(const
                     part += v.z * pw4.z;
                     part += v.w * pw4.w;
                     part += __shfl_xor(part, 16);                            // the voxel's other four channels (every lane takes part)
-                    if ((g & 1) == 0 && inside && !(MVS_ABL == 5 && part != 12345.678f))
+                    if ((g & 1) == 0 && inside)
                         logits[(size_t)b * OD * OH * OW + ((size_t)oz * OH + oy) * OW + ox] = part + pb;
                 } else if (F16) {
                     if (inside) *reinterpret_cast<f16x4*>(reinterpret_cast<_Float16*>(yb) + (((size_t)oz * OH + oy) * OW + ox) * COUT + co) =
                         f16_pack4(v, sat_amax);
                 } else if (SPLIT) {
                     split_store_quad(yb + (((size_t)oz * OH + oy) * OW + ox) * COUT, g, v, inside);
-                } else if (inside && !(MVS_ABL == 5 && v.x != 12345.678f)) {
+                } else if (inside) {
                     *reinterpret_cast<float4*>(yb + (((size_t)oz * OH + oy) * OW + ox) * COUT + co) = v;
                 }
             }
@@ -1624,9 +1385,10 @@ static int resident_blocks(const void* func, size_t lds, int threads = 256) {
 }
 
 // which layers use the split wave mapping: 64 output channels with at most two rows per wave (the 2 x 4 x 16 / 2 x 2 x 16 tiles)
+constexpr int BF_MSPLIT_MIN_MREP = 4;      // forward convs: 64 output channels only (16 -> 32: -2 %, the extra registers cost a resident block)
 template <class Cfg>
 struct BfSplitOf {
-    static constexpr bool SPLIT = MVS_MSPLIT && Cfg::MREP >= MVS_MSPLIT_MIN_MREP && Cfg::NREP <= 2 && Cfg::TH % (Cfg::NREP * 2) == 0;
+    static constexpr bool SPLIT = Cfg::MREP >= BF_MSPLIT_MIN_MREP && Cfg::NREP <= 2 && Cfg::TH % (Cfg::NREP * 2) == 0;
     typedef typename std::conditional<SPLIT, SplitCfg<Cfg, 2>, Cfg>::type type;
 };
 
@@ -1647,20 +1409,6 @@ static int launch_conv_bf(const float* x, const void* wp, const float* bias, flo
         return check_launch("conv3d_mfma_bf16x3_persist_kernel");
     }
     if (logits != nullptr) { set_error("conv3d(bf16x3): the planar single-channel output needs a persistent (Cin = 8) kernel"); return MVS_ERR_UNSUPPORTED; }
-#if MVS_CONV_LOADER
-    if constexpr (BfConvLd<Cfg>::ENABLED) {
-        static const bool off = getenv("MVS_CONV_LOADER_OFF") != nullptr;            // A/B switch (scripts/bench_layer.py)
-        if (!off) {
-            constexpr size_t LLDS = BfConvLd<Cfg>::LDS_BYTES;
-            const int resident = resident_blocks(reinterpret_cast<const void*>(&conv3d_mfma_f16_loader_kernel<Cfg>), LLDS, 320);
-            if (resident < 1) { set_error("conv3d(f16, loader): occupancy query failed"); return MVS_ERR_LAUNCH; }
-            const int nblk = ntiles < resident ? ntiles : resident;
-            hipLaunchKernelGGL((conv3d_mfma_f16_loader_kernel<Cfg>), dim3(nblk, B), dim3(320), LLDS, st, reinterpret_cast<const _Float16*>(x), wp, bias,
-                               reinterpret_cast<_Float16*>(y), D, H, W, OD, OH, OW, relu, tx, ty, ntiles);
-            return check_launch("conv3d_mfma_f16_loader_kernel");
-        }
-    }
-#endif
     constexpr size_t TLDS = BfWlds<Cfg>::ENABLED ? BfWlds<Cfg>::LDS_BYTES : LDS;
     if (TLDS > 48 * 1024)
         hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3d_mfma_bf16x3_kernel<Cfg, SPLIT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)TLDS);
@@ -1671,7 +1419,7 @@ static int launch_conv_bf(const float* x, const void* wp, const float* bias, flo
 // transposed convolutions with two output blocks (64 -> 32): one block per wave pair, twice the rows per wave
 template <class Cfg>
 struct BfDeconvSplitOf {
-    static constexpr bool SPLIT = MVS_MSPLIT && Cfg::MREP == 2 && Cfg::THM % (Cfg::NREP * 2) == 0;
+    static constexpr bool SPLIT = Cfg::MREP == 2 && Cfg::THM % (Cfg::NREP * 2) == 0;
     typedef typename std::conditional<SPLIT, SplitCfg<Cfg, 2>, Cfg>::type type;
 };
 
@@ -1680,7 +1428,7 @@ static int launch_deconv_bf(const float* x, const void* wp, const float* bias, c
                             const float* prob_b, float* logits, int B, int D, int H, int W, hipStream_t st, int relu) {
     const int tx = (int)ceil_div(W, 16), ty = (int)ceil_div(H, Cfg::THM), tz = (int)ceil_div(D, Cfg::TDM);
     const int ntiles = tx * ty * tz;
-    if constexpr (MVS_PERSIST && Cfg::CIN == 16 && Cfg::COUT == 8) {
+    if constexpr (Cfg::CIN == 16 && Cfg::COUT == 8) {
         constexpr size_t LDS = BfDeconvP<Cfg>::LDS_BYTES;
         const int resident = resident_blocks(reinterpret_cast<const void*>(&deconv3d_mfma_bf16x3_persist_kernel<Cfg, SPLIT>), LDS);
         if (resident < 1) { set_error("deconv3d(bf16x3): occupancy query failed"); return MVS_ERR_LAUNCH; }

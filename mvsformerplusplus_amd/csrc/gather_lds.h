@@ -28,10 +28,7 @@
 
 namespace mvs {
 
-#ifndef MVS_GL_CAP
-#define MVS_GL_CAP 1024
-#endif
-constexpr int GL_CAP = MVS_GL_CAP;   // window capacity in source positions: LDS = 2 quads * GL_CAP * 16 B = 32 KiB
+constexpr int GL_CAP = 1024;      // window capacity in source positions: LDS = 2 quads * GL_CAP * 16 B = 32 KiB
 constexpr int GL_XALIGN = 8;       // window x origin / width granularity in pixels (32 B of fp32, 16 B of bf16)
 constexpr int GL_DCH = 4;          // depth planes per work-item
 constexpr int GL_TH = 4;           // tile height in pixels
@@ -56,22 +53,19 @@ constexpr int GL_TH = 4;           // tile height in pixels
 //   (exact for fp16 / in-range bf16 features) and nothing else changes.  The fp16 volume formats use it (MVS_GATHER_F16).
 __device__ __forceinline__ float gl_round_f16(float v) { return (float)(_Float16)fminf(fmaxf(v, -65504.0f), 65504.0f); }
 
-// DIRECT (round 5, MVS_GL_DIRECT16): with fp16 octet tiles in HBM (the producer-side emitter's fp16 hand-off, mvs_conv2d3x3_tiles_fwd) a bilinear
+// DIRECT (round 5): with fp16 octet tiles in HBM (the producer-side emitter's fp16 hand-off, mvs_conv2d3x3_tiles_fwd) a bilinear
 // tap of 8 channels IS one 16-byte run - the four taps of a plane are four buffer_load_dwordx4 with ONE 32-bit offset register (the right
 // column through the instruction's immediate offset, the lower row through a wave-uniform soffset), so the unit needs no bounding box, no
 // window, no barrier and no LDS at all.  Same fp16 values, same v_fma_mix order as the fp16 window path: bit-identical results.
-#ifndef MVS_GL_DIRECT16
-#define MVS_GL_DIRECT16 1
-#endif
 // Where it is used is a measured choice (profiles/r05_gather_direct_pmc.txt, r05_gather_direct_ab.txt): the direct form is bound by the vector-memory
 // return path (~25-33 TD cycles per 16-byte-per-lane load), which grows with the octet count, while the window form amortises its bounding box over the
 // octets - C = 8 (one octet) wins in every pass on every box measured (-12 ... -16 % pass 2, -8 ... -12 % pass 1); C = 16 loses 5-17 % in the plain passes and
 // is box-dependent in the keeping pass 1 (-3.5 ... -6 % on two boxes, +9 % on two others): C >= 16 keeps the windows.  KEEPPASS stays a parameter of the
 // choice for that reason.
 template <typename T, bool TILED, bool W16, int NOCT, bool KEEPPASS>
-constexpr bool gl_direct_v = (MVS_GL_DIRECT16 != 0) && W16 && TILED && std::is_same<T, _Float16>::value && NOCT == 1;
+constexpr bool gl_direct_v = W16 && TILED && std::is_same<T, _Float16>::value && NOCT == 1;
 
-// Round 6 instruction diet of the unit (ISA census in DESIGN.md section 4.1, scripts/isa_census.py): MVS_GL_OPT = 0 rebuilds round 5's form for A/B runs.
+// Round 6 instruction diet of the unit (ISA census in DESIGN.md section 4.1, scripts/isa_census.py):
 //   * the bilinear blend is issued tap-outer / channel-inner: round 5 emitted each channel's four dependent v_fma_mix back to back and the
 //     compiler separated them with s_nop (96 per unit: the dependent-VALU hazard of an op_sel source) - eight independent chains interleaved need none
 //   * planar staging through ONE buffer descriptor: channel plane c is a wave-uniform soffset, the position a 32-bit voffset - no 64-bit
@@ -79,15 +73,7 @@ constexpr bool gl_direct_v = (MVS_GL_DIRECT16 != 0) && W16 && TILED && std::is_s
 //   * the "no tap inside the image" sentinel GL_NONE (0xffff, 0xffff) is neutral for the packed minimum as it stands and, after a packed + 1
 //     (which wraps it to 0), for the maximum: no compare / select per plane in the bounding box; its window position is clamped by one
 //     v_min_u32 (the weights are zero: any finite window value will do) instead of an exec-masked branch per plane
-#ifndef MVS_GL_OPT
-#define MVS_GL_OPT 1
-#endif
-#ifndef MVS_GL_SB
-#define MVS_GL_SB 2                // planar staging: rounds of 256 window positions whose loads are issued back to back before any is consumed (1: round-5 order)
-#endif
-#ifndef MVS_GL_ABL
-#define MVS_GL_ABL 0               // measurement only (scripts/gather_ablate.py; results are wrong): 1 no window loads (zeros staged), 2 no staging at all,
-#endif                             // 3 no window reads in the gather, 4 no blend arithmetic, 5 no bounding-box reduction (a fixed window), 6 no tap projection
+constexpr int GL_SB = 2;           // planar staging: rounds of 256 window positions whose loads are issued back to back before any is consumed
 
 // the four taps of one plane into wv[0..7]: t = 8 halves (4 registers) per tap
 #define GL_BLEND8(wv, t00, t01, t10, t11, tp)                                                          \
@@ -108,6 +94,21 @@ constexpr bool gl_direct_v = (MVS_GL_DIRECT16 != 0) && W16 && TILED && std::is_s
         wv[2 * j + 1] = MVS_FMA_MIX_HI(t11[j], tp.w11, wv[2 * j + 1]);                                 \
     }
 
+// commit one position to the window: one fp16 octet, clamped to the fp16 range by v_med3, or two fp32 quads
+template <bool W16>
+__device__ __forceinline__ void gl_window_put(f32x4* win, int i, const float* v) {
+    if (W16) {
+        typedef _Float16 h8 __attribute__((ext_vector_type(8)));
+        h8 hv;
+#pragma unroll
+        for (int c = 0; c < 8; ++c) hv[c] = (_Float16)__builtin_amdgcn_fmed3f(v[c], -65504.0f, 65504.0f);
+        reinterpret_cast<h8*>(win)[i] = hv;
+    } else {
+        win[i] = f32x4{v[0], v[1], v[2], v[3]};
+        win[GL_CAP + i] = f32x4{v[4], v[5], v[6], v[7]};
+    }
+}
+
 template <typename T, int NOCT, bool KEEP_GROUPS, bool TILED, bool W16, bool DIRECT = false>
 __device__ __forceinline__ void gl_unit(const T* __restrict__ src, const T* __restrict__ ref, const Homography& hm, float fx, float fy,
                                         const float* depth, bool active, int H, int W, unsigned HW, unsigned pc, f32x4* win,
@@ -122,31 +123,15 @@ __device__ __forceinline__ void gl_unit(const T* __restrict__ src, const T* __re
     GTap tp[GL_DCH];
     u16x2 mn = {0xffff, 0xffff}, mx = {0, 0};
     const float cx = 0.5f * (float)(W - 1), cy = 0.5f * (float)(H - 1);
-#if MVS_GL_OPT
     // mx holds the maximum of (x + 1, y + 1): the sentinel GL_NONE wraps to (0, 0), neutral for it; mn takes the sentinel as it is
 #pragma unroll
     for (int dd = 0; dd < GL_DCH; ++dd) {
-#if MVS_GL_ABL == 6
-        tp[dd].pk = ((unsigned)(int)fy << 16) | (unsigned)(int)fx; tp[dd].w00 = depth[dd]; tp[dd].w01 = qx; tp[dd].w10 = 0.25f; tp[dd].w11 = 0.25f;
-        if ((int)fx > W - 2 || (int)fy > H - 2) tp[dd].pk = 0;
-#else
         tp[dd] = make_gtap(hm, qx, qy, qz, depth[dd], H, W, cx, cy);
-#endif
         const u16x2 pkv = gl_as_vec(tp[dd].pk);
         mn = __builtin_elementwise_min(mn, pkv);
         mx = __builtin_elementwise_max(mx, (u16x2)(pkv + (u16x2){1, 1}));
     }
     if (!active) { mn = (u16x2){0xffff, 0xffff}; mx = (u16x2){0, 0}; }
-#else
-#pragma unroll
-    for (int dd = 0; dd < GL_DCH; ++dd) {
-        tp[dd] = make_gtap(hm, qx, qy, qz, depth[dd], H, W, cx, cy);
-        if (active && tp[dd].pk != GL_NONE) {
-            mn = __builtin_elementwise_min(mn, gl_as_vec(tp[dd].pk));
-            mx = __builtin_elementwise_max(mx, gl_as_vec(tp[dd].pk));
-        }
-    }
-#endif
     if constexpr (DIRECT) {
         static_assert(W16 && TILED && std::is_same<T, _Float16>::value, "the direct form reads fp16 octet tiles");
         typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
@@ -173,44 +158,17 @@ __device__ __forceinline__ void gl_unit(const T* __restrict__ src, const T* __re
             u32x4 t[GL_DCH][4];
 #pragma unroll
             for (int dd = 0; dd < GL_DCH; ++dd) {
-#if MVS_GL_DIRECT16 == 3      // ablation (scripts/prof_gather_direct.py): no loads
-                (void)rs; (void)rowb;
-#pragma unroll
-                for (int k = 0; k < 4; ++k) t[dd][k] = u32x4{tofs[dd], tofs[dd] + (unsigned)k, tofs[dd] ^ 0x3c003c00u, 0x3c003c00u};
-#else
                 t[dd][0] = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)tofs[dd], 0, 0);
                 t[dd][1] = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)(tofs[dd] + 16u), 0, 0);
                 t[dd][2] = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)tofs[dd], rowb, 0);
                 t[dd][3] = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)(tofs[dd] + 16u), rowb, 0);
-#endif
             }
 #pragma unroll
             for (int c = 0; c < 8; ++c) rf[c] *= wscale;
 #pragma unroll
             for (int dd = 0; dd < GL_DCH; ++dd) {
                 float wv[8];
-#if MVS_GL_DIRECT16 == 2      // ablation: the loads are consumed by one xor each, no interpolation
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const unsigned x = t[dd][0][j] ^ t[dd][1][j] ^ t[dd][2][j] ^ t[dd][3][j];
-                    wv[2 * j] = __builtin_bit_cast(float, x & 0x3fffffffu);
-                    wv[2 * j + 1] = tp[dd].w00;
-                }
-#elif MVS_GL_OPT
                 GL_BLEND8(wv, t[dd][0], t[dd][1], t[dd][2], t[dd][3], tp[dd])
-#else
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    float a = MVS_FMA_MIX_LO(t[dd][0][j], tp[dd].w00, 0.0f);
-                    a = MVS_FMA_MIX_LO(t[dd][1][j], tp[dd].w01, a);
-                    a = MVS_FMA_MIX_LO(t[dd][2][j], tp[dd].w10, a);
-                    wv[2 * j] = MVS_FMA_MIX_LO(t[dd][3][j], tp[dd].w11, a);
-                    float b = MVS_FMA_MIX_HI(t[dd][0][j], tp[dd].w00, 0.0f);
-                    b = MVS_FMA_MIX_HI(t[dd][1][j], tp[dd].w01, b);
-                    b = MVS_FMA_MIX_HI(t[dd][2][j], tp[dd].w10, b);
-                    wv[2 * j + 1] = MVS_FMA_MIX_HI(t[dd][3][j], tp[dd].w11, b);
-                }
-#endif
                 if (KEEP_GROUPS) {
 #pragma unroll
                     for (int j = 0; j < GPO; ++j) {
@@ -229,17 +187,6 @@ __device__ __forceinline__ void gl_unit(const T* __restrict__ src, const T* __re
         }
         return;
     }
-#if MVS_GL_ABL == 5
-    {
-        __syncthreads();
-        const unsigned p0 = (unsigned)__builtin_amdgcn_readfirstlane((int)tp[0].pk);
-        const unsigned bx = (p0 & 0xffffu) > 8u ? (p0 & 0xffffu) - 8u : 0u, by = (p0 >> 16) > 2u ? (p0 >> 16) - 2u : 0u;
-        mn = gl_as_vec((by << 16) | bx);
-        mx = gl_as_vec(((by + 9u) << 16) | (bx + 81u));
-#pragma unroll
-        for (int dd = 0; dd < GL_DCH; ++dd) tp[dd].pk = ((by + 1u + (unsigned)(lane & 3)) << 16) | (bx + 1u + (unsigned)(lane & 63));
-    }
-#else
     mn = gl_wave_reduce<false>(mn);                               // lane 63 holds the wave's result
     mx = gl_wave_reduce<true>(mx);
     unsigned* rd = red + (unit & 1) * 8;
@@ -249,12 +196,7 @@ __device__ __forceinline__ void gl_unit(const T* __restrict__ src, const T* __re
                                    __builtin_elementwise_min(gl_as_vec(rd[2]), gl_as_vec(rd[3])));
     mx = __builtin_elementwise_max(__builtin_elementwise_max(gl_as_vec(rd[4]), gl_as_vec(rd[5])),
                                    __builtin_elementwise_max(gl_as_vec(rd[6]), gl_as_vec(rd[7])));
-#endif
-#if MVS_GL_OPT
     const int xmin = mn[0], ymin = mn[1], xmax = (int)mx[0] - 1, ymax = (int)mx[1] - 1;       // mx = maximum of (x + 1, y + 1); 0 = nothing
-#else
-    const int xmin = mn[0], ymin = mn[1], xmax = mx[0], ymax = mx[1];
-#endif
     if (xmax < xmin) return;                                    // no tap of the whole tile is inside the source image
     const int wx0 = xmin & ~(GL_XALIGN - 1);
     const int ww = (xmax + 2 - wx0 + GL_XALIGN - 1) & ~(GL_XALIGN - 1);
@@ -267,13 +209,9 @@ __device__ __forceinline__ void gl_unit(const T* __restrict__ src, const T* __re
 #pragma unroll
         for (int dd = 0; dd < GL_DCH; ++dd) {
             const unsigned pk = tp[dd].pk;
-#if MVS_GL_OPT
             // a 2x2 block inside the window sits at <= n - ww - 2; GL_NONE (weights zero) lands far beyond and is clamped there
             const unsigned raw = ((pk >> 16) - (unsigned)ymin) * (unsigned)ww + ((pk & 0xffffu) - (unsigned)wx0);
             pos[dd] = raw < (unsigned)(n - ww - 2) ? raw : (unsigned)(n - ww - 2);
-#else
-            pos[dd] = pk == GL_NONE ? 0u : ((pk >> 16) - (unsigned)ymin) * (unsigned)ww + ((pk & 0xffffu) - (unsigned)wx0);
-#endif
         }
         const float inv_ww = __builtin_amdgcn_rcpf((float)ww) * 1.000001f;   // row = floor((i + 0.5) / ww): exact for i < 2^16
         const unsigned gbase = (unsigned)ymin * (unsigned)W + (unsigned)wx0;
@@ -292,21 +230,18 @@ __device__ __forceinline__ void gl_unit(const T* __restrict__ src, const T* __re
 #pragma unroll
                 for (int c = 0; c < 8; ++c) rf[c] = rf_in[c];
             }
-#if MVS_GL_OPT
             // planar maps: one descriptor over the octet's 8 channel planes; plane c = wave-uniform soffset, position = 32-bit voffset
             const __amdgpu_buffer_rsrc_t srs = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(so), 0, (int)(8u * HW * (unsigned)sizeof(T)), 0x00020000);
             const unsigned planeb = HW * (unsigned)sizeof(T);
-#endif
             int istart = tid;
-#if MVS_GL_OPT && MVS_GL_ABL == 0
             if constexpr (!TILED) {
                 // Round 6 (profiles/r06_gather_ablation.txt): the rolled loop below - load 8 dwords, wait, convert, ds_write - exposed one global-memory
                 // latency per round of 256 positions, two or three rounds per unit between two barriers: 19-36 % of a fine-stage pass.  Here the loads
-                // of MVS_GL_SB rounds are all in flight before the first is consumed (8 VGPRs per extra round).  Measured (profiles/r06_gather_staging_rounds_ab.txt):
+                // of GL_SB rounds are all in flight before the first is consumed (8 VGPRs per extra round).  Measured (profiles/r06_gather_staging_rounds_ab.txt):
                 // stage-4 pass 1 -4 %, pass 2 -5 %; at C = 16 the extra registers cost the keeping pass its fourth wave per SIMD (+12 %), at C >= 32 nothing
                 // moves: one octet per unit only.  (The ablation's 19-36 % are mostly the HBM time of the feature maps themselves, which the
                 // barrier-separated phases of four resident blocks overlap imperfectly - not a latency two rounds in flight could hide.)
-                constexpr int SBR = NOCT == 1 ? MVS_GL_SB : 1;
+                constexpr int SBR = NOCT == 1 ? GL_SB : 1;
 #pragma unroll 1
                 for (int i0 = tid; i0 < n; i0 += 256 * SBR) {
                     float v[SBR][8];
@@ -328,31 +263,17 @@ __device__ __forceinline__ void gl_unit(const T* __restrict__ src, const T* __re
 #pragma unroll
                     for (int k = 0; k < SBR; ++k) {
                         const int i = i0 + 256 * k;
-                        if (i < n) {
-                            if (W16) {
-                                h8 hv;
-#pragma unroll
-                                for (int c = 0; c < 8; ++c) hv[c] = (_Float16)__builtin_amdgcn_fmed3f(v[k][c], -65504.0f, 65504.0f);
-                                win16[i] = hv;
-                            } else {
-                                win[i] = f32x4{v[k][0], v[k][1], v[k][2], v[k][3]};
-                                win[GL_CAP + i] = f32x4{v[k][4], v[k][5], v[k][6], v[k][7]};
-                            }
-                        }
+                        if (i < n) gl_window_put<W16>(win, i, v[k]);
                     }
                 }
                 istart = n;
             }
-#endif
+            // octet tiles.  (Planar maps arrive with istart = n and never enter; the planar branch stays in the body, and the direct form stays
+            // inside this function, because taking either out changes the register allocation of some gather kernels: profiles/switch_retirement_isa.txt.)
 #pragma unroll 1
-            for (int i = istart; i < (MVS_GL_ABL == 2 ? 0 : n); i += 256) {
-#if MVS_GL_ABL == 1
-                if (W16) { h8 hz; for (int c = 0; c < 8; ++c) hz[c] = (_Float16)(float)(i & 7); win16[i] = hz; } else { win[i] = f32x4{1, 2, 3, 4}; win[GL_CAP + i] = f32x4{1, 2, 3, 4}; }
-                continue;
-#endif
+            for (int i = istart; i < n; i += 256) {
                 const int row = (int)(((float)i + 0.5f) * inv_ww);
                 const unsigned g = gbase + (unsigned)row * (unsigned)(W - ww) + (unsigned)i;    // (ymin+row)*W + wx0 + (i - row*ww)
-#if MVS_GL_OPT
                 if constexpr (!TILED) {
                     float v[8];
 #pragma unroll
@@ -362,18 +283,9 @@ __device__ __forceinline__ void gl_unit(const T* __restrict__ src, const T* __re
                         else
                             v[c] = to_f32(__builtin_bit_cast(T, (unsigned short)__builtin_amdgcn_raw_buffer_load_b16(srs, (int)(g * 2u), (int)((unsigned)c * planeb), 0)));
                     }
-                    if (W16) {
-                        h8 hv;
-#pragma unroll
-                        for (int c = 0; c < 8; ++c) hv[c] = (_Float16)__builtin_amdgcn_fmed3f(v[c], -65504.0f, 65504.0f);
-                        win16[i] = hv;
-                    } else {
-                        win[i] = f32x4{v[0], v[1], v[2], v[3]};
-                        win[GL_CAP + i] = f32x4{v[4], v[5], v[6], v[7]};
-                    }
+                    gl_window_put<W16>(win, i, v);
                     continue;
                 }
-#endif
                 if constexpr (W16 && TILED && std::is_same<T, _Float16>::value) {
                     // fp16 octet tiles (what a producer-side emitter hands over, mvs_conv2d3x3_tiles_fwd with out_dtype fp16): the window
                     // position IS the 16-byte run in HBM - staging is a copy, no conversion, no clamp (round 5)
@@ -403,29 +315,8 @@ __device__ __forceinline__ void gl_unit(const T* __restrict__ src, const T* __re
                     if (W16) {
                         typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
                         const u32x4* w0 = reinterpret_cast<const u32x4*>(win16) + pos[dd];
-#if MVS_GL_ABL == 3
-                        const u32x4 t00 = {pos[dd], 0x3c003c00u, 0x3c003c00u, pos[dd]}, t01 = t00, t10 = {0x3c003c00u, pos[dd], pos[dd], 0x3c003c00u}, t11 = t10;
-#else
                         const u32x4 t00 = w0[0], t01 = w0[1], t10 = w0[ww], t11 = w0[ww + 1];
-#endif
-#if MVS_GL_ABL == 4
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) { wv[2 * j] = __builtin_bit_cast(float, (t00[j] ^ t01[j] ^ t10[j] ^ t11[j]) & 0x3fffffffu); wv[2 * j + 1] = tp[dd].w00; }
-#elif MVS_GL_OPT
                         GL_BLEND8(wv, t00, t01, t10, t11, tp[dd])
-#else
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) {            // 4 v_fma_mix_f32 per channel, no conversion instructions
-                            float a = MVS_FMA_MIX_LO(t00[j], tp[dd].w00, 0.0f);
-                            a = MVS_FMA_MIX_LO(t01[j], tp[dd].w01, a);
-                            a = MVS_FMA_MIX_LO(t10[j], tp[dd].w10, a);
-                            wv[2 * j] = MVS_FMA_MIX_LO(t11[j], tp[dd].w11, a);
-                            float b = MVS_FMA_MIX_HI(t00[j], tp[dd].w00, 0.0f);
-                            b = MVS_FMA_MIX_HI(t01[j], tp[dd].w01, b);
-                            b = MVS_FMA_MIX_HI(t10[j], tp[dd].w10, b);
-                            wv[2 * j + 1] = MVS_FMA_MIX_HI(t11[j], tp[dd].w11, b);
-                        }
-#endif
                     } else {
                         const f32x4* w0 = win + pos[dd];
                         const f32x4 a0 = w0[0], a1 = w0[1], b0 = w0[ww], b1 = w0[ww + 1];

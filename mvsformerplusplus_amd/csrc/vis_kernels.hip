@@ -38,13 +38,7 @@ constexpr int VS_ENT_BYTES = (VS_SH_MAX + 6) * VS_EP * 4;
 // fp16 rings: the second octet plane on the SAME 16-byte slots as the first (see bf_f16_plane_shift in conv_bf16x3_kernels.hip: the
 // service groups of a ds_read_b128 pair lanes {0-3, 12-15} of one operand group with {20-27} of the other; rounds 3-4 shipped 128 and
 // with it a 2-way conflict on every operand read - 40 % of the kernel's LDS cycles)
-#ifndef VS_F16_PLANE_SHIFT
-#ifdef MVS_F16_PLANE_SHIFT
-#define VS_F16_PLANE_SHIFT MVS_F16_PLANE_SHIFT
-#else
-#define VS_F16_PLANE_SHIFT 0
-#endif
-#endif
+constexpr int VS_F16_PLANE_SHIFT = 0;
 template <bool F16>
 struct VsL {
     static constexpr int POSB = F16 ? 16 : 32;                 // bytes per (position, octet)

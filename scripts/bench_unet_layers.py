@@ -1,6 +1,6 @@
 """Every layer of CostRegNet3D at cfg2's stage-4 / stage-3 shapes in the product format of the fine stages ("f16mix": fp16 activations, two fp16
 weight terms on the 8- / 16-channel layers, one on conv4 .. conv7), HIP-event timing, best of three interleaved runs.  MVS_HIP_LIB selects a variant
-library for A/B runs (round 6: -DMVS_ZSKIP=0).  Prints us per launch and the stage sums."""
+library for A/B runs (build.build(extra_flags=..., out=...)).  Prints us per launch and the stage sums."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

@@ -525,7 +525,7 @@ def case_stage_lowp_features(device, prec=None):
         assert errs[-1] <= tol(prec, 2e-5, 2e-4), errs      # fp16: measured 4.8e-5
         if dt == torch.float16:
             # the same features handed over as fp16 octet tiles (the emitter's fp16 hand-off): in the fp16 gather forms the taps are read straight
-            # from the tiles (gather_lds.h, MVS_GL_DIRECT16 - no window) - the same values in the same order: every output bit for bit
+            # from the tiles (gather_lds.h, the direct form (`gl_direct_v`) - no window) - the same values in the same order: every output bit for bit
             with torch.no_grad():
                 out_t = net(ops.pack_features(dev(f, device)), dev(fx["proj"], device), dev(fx["hyp"], device), 1.0)
             same = all(torch.equal(cpu(out[k]), cpu(out_t[k])) for k in ("depth", "photometric_confidence", "prob_volume"))
@@ -1225,7 +1225,7 @@ def case_cascade_vs_oracle(device, H, W, V, peaky=False, conv_precision=None, **
     assert float(dconf.mean()) <= tol(conv_precision, 1e-3, 1e-2), "confidence mean abs error %g" % float(dconf.mean())
     if conv_precision is None and feats["stage4"].dtype in (torch.float32, torch.float16):
         # the product default fed with the producer-side emitter's hand-off for the fine stages: stages 3-4 as fp16 octet tiles -
-        # the gather reads its taps straight from the tiles where C = 8 (gather_lds.h, MVS_GL_DIRECT16): the same bar against the same oracle
+        # the gather reads its taps straight from the tiles where C = 8 (gather_lds.h, the direct form (`gl_direct_v`)): the same bar against the same oracle
         with torch.no_grad():
             ft = {k: (ops.pack_features(dev(v, device), torch.float16) if k in ("stage3", "stage4") else dev(v, device)) for k, v in feats.items()}
             out_t = head(ft, {k: dev(v, device) for k, v in projs.items()}, dev(dv, device))
