@@ -582,6 +582,37 @@ int mvs_fmt_merge_fwd(const float* prev, const float* lateral, const float* w_re
                       void* stream);
 int mvs_fmt_smooth_fwd(const float* x, const void* w_packed, float* y, int N, int C, int H, int W, void* stream);
 
+/* ==== CrossVITDecoder: the ViT feature decoder at d_model 768 =========================================
+ * models/module.py:273-364 with the shipped decoder_cfg (Linear attention, 12 heads of 64, ffn, pre-norm, LayerScale).  The residual
+ * stream is token-major fp32 [M, 768], M = views x n tokens.  A GEMM's row operand is a PACKED-SPLIT tensor of
+ * mvs_vitdec_packed_bytes(rows, channels) bytes: packed[row >> 4][k >> 5][hi|lo][lane = ((k >> 3) & 3) * 16 + (row & 15)][k & 7] bf16,
+ * x ~= hi + lo, written by its producer.  Weights are packing.pack_linear_bf16x3; three-term products, fp32 accumulation.
+ * mvs_vitdec_rows_fwd: per row [prev_value[0] * prev +] in [-> LayerNorm(mix_w, mix_b, eps 1e-6)] -> x (fp32, nullable), x_packed
+ *   (nullable) and xn_packed = packed(LayerNorm(ln_w, ln_b, eps 1e-5)(x)) (nullable).  Row r = (b * in_views + j) * n + t is read at
+ *   in + b * in_batch_stride + (in_v0 + j) * in_view_stride + t * in_row_stride (elements of in_dtype, 768 contiguous) and x_packed is
+ *   written at row (b * out_V + out_v0 + j) * n + t.  prev_value lives in device memory.
+ * mvs_vitdec_linear_fwd: y = epilogue(a W^T), K -> N = 768 -> 768 | 1536 | 3072 or 3072 -> 768.  epilogue 0: fp32 [M, N], elu(.) + 1 on
+ *   columns < elu_cols; 1: fp32 residual + gamma * (. + bias); 2: packed-split GELU(. + bias).
+ * mvs_vitdec_kv_fwd: kv [NV * n, 1536] fp32 (elu(k) + 1 | v) -> summary [NV][12][KV_h 64 x 64 | ksum_h 64] fp32 from exact fp32
+ *   products; per-slab partials in `workspace` (mvs_vitdec_kv_workspace_bytes) added in a fixed order: no atomics.
+ * mvs_vitdec_apply_fwd: a = (q . KV_h) / (q . ksum_h + 1e-6), q [NV * n, 768] fp32, view i uses summary[i / kv_div] -> packed-split.
+ * mvs_vitdec_conv_fwd: layer 0 = proj (Conv2d 768 -> 256, 3x3, padding 1), 1 / 2 = upsampler0 / 1 (ConvTranspose2d 256 -> 128 / 128 -> 64,
+ *   4x4, stride 2, padding 1), BatchNorm folded, SiLU; x packed-split tokens of the [NV, H, W] map; y packed-split tokens of the
+ *   output map (planar 0) or planar fp32 [NV, Cout, Ho, Wo] (planar 1).  w_packed = packing.pack_vitdec_conv / pack_vitdec_deconv.   */
+size_t mvs_vitdec_packed_bytes(long long rows, int channels);
+size_t mvs_vitdec_summary_bytes(int NV);
+size_t mvs_vitdec_kv_workspace_bytes(int NV, int n);
+int mvs_vitdec_rows_fwd(const void* in, int in_dtype, long long in_batch_stride, long long in_view_stride, long long in_row_stride, int in_v0,
+                        int in_views, const float* prev, const float* prev_value, const float* mix_w, const float* mix_b, float* x,
+                        void* x_packed, int out_V, int out_v0, const float* ln_w, const float* ln_b, void* xn_packed, int NV, int n,
+                        int channels, void* stream);
+int mvs_vitdec_linear_fwd(const void* a_packed, const void* w_packed, const float* bias, const float* gamma, const float* residual, void* y,
+                          int M, int K, int N, int epilogue, int elu_cols, void* stream);
+int mvs_vitdec_kv_fwd(const float* kv, void* workspace, size_t workspace_bytes, float* summary, int NV, int n, int channels, void* stream);
+int mvs_vitdec_apply_fwd(const float* q, const float* summary, void* a_packed, int NV, int n, int kv_div, int channels, void* stream);
+int mvs_vitdec_conv_fwd(const void* x_packed, const void* w_packed, const float* bias, void* y, int layer, int planar, int NV, int H, int W,
+                        void* stream);
+
 /* ---- layout helpers for the nn.Module-level API (NCDHW <-> channel-last) -------------------------*/
 int mvs_ncdhw_to_cl(const float* x, float* y_cl, int B, int C, int D, int H, int W, void* stream);
 int mvs_cl_to_ncdhw(const float* x_cl, float* y, int B, int C, int D, int H, int W, void* stream);

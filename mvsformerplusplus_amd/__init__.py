@@ -15,11 +15,12 @@ from .ops import PackedFeatures, pack_features
 from .handoff import TiledFeatureHead
 from .features import FPNDecoder, FPNEncoder, patch_fpn
 from .fmt import FMT_with_pathway, patch_fmt
+from .vit_decoder import CrossVITDecoder, patch_vit_decoder
 from .position_encoding import PositionEncoding3D, get_position_3d
 from .warping import diff_homo_warping_3D_with_mask, homo_warping_3D, homo_warping_3D_with_mask
 
 __all__ = ["CascadeDepthHead", "patch_model", "StageNet", "Conv3d", "Deconv3d", "ConvBnReLU", "CostRegNet", "CostRegNet3D", "CostRegNet2D",
            "PureTransformerCostReg", "get_position_3d", "PositionEncoding3D", "fusion", "PackedFeatures", "pack_features", "TiledFeatureHead", "FPNEncoder", "FPNDecoder", "patch_fpn",
-           "FMT_with_pathway", "patch_fmt",
+           "FMT_with_pathway", "patch_fmt", "CrossVITDecoder", "patch_vit_decoder",
            "depth_regression", "conf_regression", "init_range", "init_inverse_range", "schedule_inverse_range", "schedule_range",
            "homo_warping_3D_with_mask", "homo_warping_3D", "diff_homo_warping_3D_with_mask"]

@@ -133,6 +133,14 @@ SIGNATURES = {
     "mvs_fmt_path_fwd": (_i, [_vp] * 5 + [_i] * 6 + [_vp]),
     "mvs_fmt_merge_fwd": (_i, [_vp] * 4 + [_i] * 6 + [_vp]),
     "mvs_fmt_smooth_fwd": (_i, [_vp] * 3 + [_i] * 4 + [_vp]),
+    "mvs_vitdec_packed_bytes": (_sz, [C.c_longlong, _i]),
+    "mvs_vitdec_summary_bytes": (_sz, [_i]),
+    "mvs_vitdec_kv_workspace_bytes": (_sz, [_i, _i]),
+    "mvs_vitdec_rows_fwd": (_i, [_vp, _i, C.c_longlong, C.c_longlong, C.c_longlong, _i, _i] + [_vp] * 6 + [_i, _i, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "mvs_vitdec_linear_fwd": (_i, [_vp] * 6 + [_i] * 5 + [_vp]),
+    "mvs_vitdec_kv_fwd": (_i, [_vp, _vp, _sz, _vp, _i, _i, _i, _vp]),
+    "mvs_vitdec_apply_fwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "mvs_vitdec_conv_fwd": (_i, [_vp] * 4 + [_i] * 5 + [_vp]),
     "mvs_ncdhw_to_cl": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "mvs_cl_to_ncdhw": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
 }

@@ -1,0 +1,598 @@
+// CrossVITDecoder: the ViT feature decoder of the shipped network at d_model 768, fp32-equivalent.
+//
+// Reference (restated, never copied): models/module.py:273-364 (CrossVITDecoder), models/dino/layers/block.py (CrossBlock, pre-norm,
+// LayerScale), models/dino/layers/attention.py (CrossLinearAttention), models/dino/layers/mlp.py (fc1, GELU (erf), fc2).
+//
+// Layout.  Tokens are token-major.  The residual stream is fp32 [M, 768] (M = views x tokens, the views one after the other).
+// Everything that is only ever a GEMM's row operand is kept as a PACKED-SPLIT tensor: per 16-row block and per 32-wide k-step the
+// 64-lane hi fragment, then the 64-lane lo fragment of v_mfma_f32_16x16x32_bf16,
+//     packed[row >> 4][k >> 5][hi|lo][lane = ((k >> 3) & 3) * 16 + (row & 15)][k & 7],       x ~= hi + lo (both bf16, RNE)
+// i.e. 4 bytes per element like fp32, split ONCE by its producer (LayerNorm, the attention apply, the GELU / SiLU epilogues), so that a
+// GEMM stages both operands with plain 16-byte copies in the order its lanes read them (conflict-free ds_read_b128).  Weights are
+// packing.pack_linear_bf16x3: [k >> 5][out >> 4][hi|lo][lane][k & 7].  Every product is the three-term one (lo*hi + hi*lo + hi*hi,
+// fp32 accumulate, k ascending: the result of an element does not depend on the tile that computes it).
+//
+// Kernels:
+//   1. vd_rows_kernel: one wave per token row.  [prev_value * prev +] input row (fp32 / bf16 / fp16, any batch / view / row stride)
+//      [-> LayerNorm eps 1e-6 (norm_layers)] -> x fp32 and / or packed-split(x) and / or packed-split(LayerNorm eps 1e-5 (x)).
+//      prev_value is read from device memory.
+//   2. vd_gemm_kernel<NREP>: Y = epilogue(A W^T).  Workgroup = 2 x 2 waves, wave = 16 NREP tokens x 64 channels, tile 32 NREP x 128,
+//      K in chunks of 64 through LDS (both operands), the next chunk's global loads in flight during the MFMAs.  The row operand is
+//      read in place (linear layers), through a 3x3 window (proj: implicit GEMM, K = 9 x 768) or through the 2x2 window of one
+//      parity class of ConvTranspose2d(4, stride 2, padding 1) (upsampler0 / 1: K = 4 x Cin, blockIdx.z = class).  Epilogues: fp32
+//      (elu + 1 on the leading columns), residual + gamma * (. + bias), packed-split act(. + bias), planar fp32 silu(. + bias).
+//   3. vd_kv_partial_kernel + vd_kv_reduce_kernel: KV_h = sum_s k_s (x) v_s and ksum_h = sum_s k_s from exact fp32 products
+//      (v_mfma_f32_16x16x4_f32); per-slab partials added in slab order by the second launch: no atomics, bit-identical run to run.
+//   4. vd_apply_kernel: a = (q . KV_h) / (q . ksum_h + 1e-6) on the exact fp32 MFMA, KV_h held in registers -> packed-split.
+// Rows past the end and window positions outside the map read as zero from a branch, never from an out-of-range load.
+#include "mvs_common.h"
+#include "split_format.h"
+
+namespace mvs {
+
+constexpr int VD_C = 768, VD_HEADS = 12, VD_HD = 64, VD_HID = 3072;
+constexpr int VD_KC = 64;                     // contraction per LDS chunk: two MFMA k-steps
+constexpr int VD_TN = 128;                    // output channels per workgroup
+constexpr int VD_KVPART = VD_HD * VD_HD + VD_HD;      // floats of one (view, head) summary: KV_h [d][m] | ksum_h [d]
+constexpr int VD_MAX_SLABS = 16;
+
+enum { VD_A_ROWS = 0, VD_A_CONV3 = 1, VD_A_DECONV = 2 };
+enum { VD_EPI_F32 = 0, VD_EPI_RESID = 1, VD_EPI_SPLIT = 2, VD_EPI_PLANAR = 3 };
+enum { VD_ACT_NONE = 0, VD_ACT_GELU = 1, VD_ACT_SILU = 2 };
+
+__device__ __forceinline__ float vd_elu1(float t) { return t > 0.0f ? t + 1.0f : expf(t); }                      // elu(t) + 1
+__device__ __forceinline__ float vd_act(float t, int act) {
+    if (act == VD_ACT_GELU) return 0.5f * t * (1.0f + erff(t * 0.70710678118654752440f));
+    if (act == VD_ACT_SILU) return t / (1.0f + expf(-t));
+    return t;
+}
+
+// four consecutive channels ch .. ch + 3 (ch % 4 == 0) of row `orow` into a packed-split tensor of `steps` k-steps per row
+__device__ __forceinline__ void vd_store_split4(bf16x8* buf, int steps, int orow, int ch, const float (&v)[4]) {
+    __bf16 h[4], l[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        h[j] = (__bf16)v[j];
+        l[j] = (__bf16)(v[j] - (float)h[j]);
+    }
+    char* dst = reinterpret_cast<char*>(buf + (((size_t)(orow >> 4) * steps + (ch >> 5)) * 2) * 64 + ((ch >> 3) & 3) * 16 + (orow & 15)) + (ch & 4) * 2;
+    *reinterpret_cast<u32x2*>(dst) = (u32x2){pack_bf16x2(h[0], h[1]), pack_bf16x2(h[2], h[3])};
+    *reinterpret_cast<u32x2*>(dst + 64 * 16) = (u32x2){pack_bf16x2(l[0], l[1]), pack_bf16x2(l[2], l[3])};
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// rows: mix, norm, split
+// ---------------------------------------------------------------------------------------------------------------------------------
+struct VdRowsArgs {
+    const void* in;              // row r = (b * in_views + j) * n + t  at  in + b * in_bs + (in_v0 + j) * in_vs + t * in_rs  (elements)
+    int in_dtype;
+    long long in_bs, in_vs, in_rs;
+    int in_v0, in_views;
+    const float* prev;           // [M, 768] fp32 (nullable): value = prev_value[0] * prev + in
+    const float* prev_value;
+    const float* mix_w;          // norm_layers (eps 1e-6) applied to the mix (nullable)
+    const float* mix_b;
+    float* x;                    // [M, 768] fp32 (nullable)
+    bf16x8* xp;                  // packed-split(x) at row ((b * out_V + out_v0 + j) * n + t) (nullable)
+    const float* ln_w;           // LayerNorm (eps 1e-5) -> xn packed-split at row r (nullable)
+    const float* ln_b;
+    bf16x8* xn;
+    int M, n, out_V, out_v0;
+};
+
+__device__ __forceinline__ float vd_wave_sum(float s) {
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) s += __shfl_xor(s, m);
+    return s;
+}
+
+// LayerNorm over the 768 channels of a row held as 3 x 4 values per lane (channels 4 (lane + 64 j) ..)
+__device__ __forceinline__ void vd_row_norm(const float (&v)[3][4], const float* __restrict__ w, const float* __restrict__ b, float eps, int lane,
+                                            float (&y)[3][4]) {
+    float s = 0.0f;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) s += (v[j][0] + v[j][1]) + (v[j][2] + v[j][3]);
+    const float mean = vd_wave_sum(s) * (1.0f / VD_C);
+    float q = 0.0f;
+#pragma unroll
+    for (int j = 0; j < 3; ++j)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float d = v[j][k] - mean;
+            q = fmaf(d, d, q);
+        }
+    const float rstd = 1.0f / sqrtf(vd_wave_sum(q) * (1.0f / VD_C) + eps);
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        const float4 ww = *reinterpret_cast<const float4*>(w + 4 * (lane + 64 * j));
+        const float4 bb = *reinterpret_cast<const float4*>(b + 4 * (lane + 64 * j));
+        y[j][0] = fmaf((v[j][0] - mean) * rstd, ww.x, bb.x);
+        y[j][1] = fmaf((v[j][1] - mean) * rstd, ww.y, bb.y);
+        y[j][2] = fmaf((v[j][2] - mean) * rstd, ww.z, bb.z);
+        y[j][3] = fmaf((v[j][3] - mean) * rstd, ww.w, bb.w);
+    }
+}
+
+template <int DT>
+__global__ __launch_bounds__(256) void vd_rows_kernel(VdRowsArgs a) {
+    typedef typename FeatT<DT>::type T;
+    const int lane = (int)threadIdx.x & 63, r = (int)blockIdx.x * 4 + ((int)threadIdx.x >> 6);
+    if (r >= a.M) return;                                          // wave-uniform; no workgroup barrier
+    const int vv = r / a.n, t = r - vv * a.n, b = vv / a.in_views, j0 = vv - b * a.in_views;
+    const T* src = reinterpret_cast<const T*>(a.in) + (size_t)b * a.in_bs + (size_t)(a.in_v0 + j0) * a.in_vs + (size_t)t * a.in_rs;
+    float v[3][4];
+#pragma unroll
+    for (int j = 0; j < 3; ++j)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[j][k] = to_f32(src[4 * (lane + 64 * j) + k]);
+    if (a.prev) {
+        const float pv = a.prev_value[0];
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const float4 p = *reinterpret_cast<const float4*>(a.prev + (size_t)r * VD_C + 4 * (lane + 64 * j));
+            v[j][0] = fmaf(pv, p.x, v[j][0]);
+            v[j][1] = fmaf(pv, p.y, v[j][1]);
+            v[j][2] = fmaf(pv, p.z, v[j][2]);
+            v[j][3] = fmaf(pv, p.w, v[j][3]);
+        }
+    }
+    if (a.mix_w) {
+        float y[3][4];
+        vd_row_norm(v, a.mix_w, a.mix_b, 1e-6f, lane, y);
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+#pragma unroll
+            for (int k = 0; k < 4; ++k) v[j][k] = y[j][k];
+    }
+    if (a.x) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+            *reinterpret_cast<float4*>(a.x + (size_t)r * VD_C + 4 * (lane + 64 * j)) = make_float4(v[j][0], v[j][1], v[j][2], v[j][3]);
+    }
+    if (a.xp) {
+        const int orow = (b * a.out_V + a.out_v0 + j0) * a.n + t;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) vd_store_split4(a.xp, VD_C / 32, orow, 4 * (lane + 64 * j), v[j]);
+    }
+    if (a.xn) {
+        float y[3][4];
+        vd_row_norm(v, a.ln_w, a.ln_b, 1e-5f, lane, y);
+#pragma unroll
+        for (int j = 0; j < 3; ++j) vd_store_split4(a.xn, VD_C / 32, r, 4 * (lane + 64 * j), y[j]);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// GEMM
+// ---------------------------------------------------------------------------------------------------------------------------------
+struct VdGemmArgs {
+    const bf16x8* a;             // packed-split row operand, K (ROWS) or C (windows) channels per row
+    const bf16x8* w;             // packed weights [K / 32][Npad / 16][hi|lo][64]; class z at w + z * w_class
+    const float* bias;           // [N] (nullable)
+    const float* gamma;          // [N]   (RESID)
+    const float* res;            // [M, N] (RESID)
+    void* out;
+    int M, K, N, Npad;
+    int a_mode, epi, act, elu_cols;
+    int C, H, W;                 // windows: channels per tap, the source map; PLANAR: H W = pixels per view
+    size_t w_class;
+};
+
+// The staged rows of one work-item, decomposed ONCE per workgroup: `base` = first source row of the row's view (windows) or the row itself
+// (ROWS), -1 = past the end; `yx` = (y << 16) | x of the row's pixel (windows).
+struct VdRow {
+    int base, yx;
+};
+
+__device__ __forceinline__ VdRow vd_row(const VdGemmArgs& p, int row) {
+    VdRow r{-1, 0};
+    if (row >= p.M) return r;
+    if (p.a_mode == VD_A_ROWS) {
+        r.base = row;
+    } else {
+        const int hw = p.H * p.W, view = row / hw, pix = row - view * hw, y = pix / p.W;
+        r.base = view * hw;
+        r.yx = (y << 16) | (pix - y * p.W);
+    }
+    return r;
+}
+
+// index (in 16-byte units) of the fragment piece (k-step `kstep` of the source row, hi|lo, lane group gl) of a staged row whose window
+// offset is (dy, dx), or -1 = zero
+__device__ __forceinline__ long long vd_a_piece(const VdGemmArgs& p, const VdRow& r, int dy, int dx, int steps, int kstep, int hl, int gl) {
+    if (r.base < 0) return -1;
+    int srow = r.base;
+    if (p.a_mode != VD_A_ROWS) {
+        const int sy = (r.yx >> 16) + dy, sx = (r.yx & 0xffff) + dx;
+        if (sy < 0 || sy >= p.H || sx < 0 || sx >= p.W) return -1;
+        srow += sy * p.W + sx;
+    }
+    return ((((long long)(srow >> 4) * steps + kstep) * 2 + hl) * 64) + gl * 16 + (srow & 15);
+}
+
+template <int NREP>
+__global__ __launch_bounds__(256) void vd_gemm_kernel(VdGemmArgs p) {
+    constexpr int NTB = 2 * NREP, TM = 16 * NTB;
+    HIP_DYNAMIC_SHARED(float4, lds4)
+    bf16x8* la = reinterpret_cast<bf16x8*>(lds4);                 // [NTB token blocks][2 steps][hi|lo][64 lanes]
+    bf16x8* lw = la + NTB * 256;                                  // [2 steps][8 channel blocks][hi|lo][64 lanes]
+    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, g = lane >> 4;
+    const int wm = wave & 1, wn = wave >> 1;
+    const int m0 = (int)blockIdx.x * TM, nb0 = (int)blockIdx.y * (VD_TN / 16), cls = (int)blockIdx.z;
+    const bf16x8* wsrc = p.w + (size_t)cls * p.w_class;
+    const int nmb = p.Npad >> 4;
+    // staging: piece (token block i, tid) of the row operand; pieces tid + 256 i (i < 8) of the weight chunk
+    const int ps = tid >> 7, phl = (tid >> 6) & 1, pgl = lane >> 4;
+    bf16x8 ra[NTB], rw[8];
+    bf16x8 zero;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) zero[e] = (__bf16)0.0f;
+
+    VdRow rows[NTB];
+#pragma unroll
+    for (int i = 0; i < NTB; ++i) rows[i] = vd_row(p, m0 + 16 * i + li);
+
+    auto fetch = [&](int k0) {
+        // the chunk's tap and window offset are workgroup-uniform: output (2 y + py, 2 x + px) of a transposed convolution reads input
+        // (y + py - ay, x + px - ax) with ky = 1 - py + 2 ay
+        int steps = p.K >> 5, kstep = (k0 >> 5) + ps, dy = 0, dx = 0;
+        if (p.a_mode != VD_A_ROWS) {
+            const int tap = k0 / p.C;
+            steps = p.C >> 5;
+            kstep = ((k0 - tap * p.C) >> 5) + ps;
+            if (p.a_mode == VD_A_CONV3) {
+                dy = tap / 3 - 1;
+                dx = tap - (tap / 3) * 3 - 1;
+            } else {
+                dy = (cls >> 1) - (tap >> 1);
+                dx = (cls & 1) - (tap & 1);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < NTB; ++i) {
+            const long long idx = vd_a_piece(p, rows[i], dy, dx, steps, kstep, phl, pgl);
+            ra[i] = idx >= 0 ? p.a[idx] : zero;
+        }
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const int j = tid + 256 * i, s = j >> 10, rest = j & 1023;
+            rw[i] = wsrc[((size_t)((k0 >> 5) + s) * nmb + nb0) * 128 + rest];
+        }
+    };
+
+    f32x4 acc[4][NREP];
+#pragma unroll
+    for (int mb = 0; mb < 4; ++mb)
+#pragma unroll
+        for (int nb = 0; nb < NREP; ++nb) acc[mb][nb] = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
+
+    fetch(0);
+#pragma unroll 1
+    for (int k0 = 0; k0 < p.K; k0 += VD_KC) {
+        __syncthreads();                                           // the previous chunk has been read
+#pragma unroll
+        for (int i = 0; i < NTB; ++i) la[i * 256 + tid] = ra[i];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) lw[tid + 256 * i] = rw[i];
+        __syncthreads();
+        if (k0 + VD_KC < p.K) fetch(k0 + VD_KC);                   // in flight during the MFMAs below
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            bf16x8 ah[4], al[4], bh[NREP], bl[NREP];
+#pragma unroll
+            for (int mb = 0; mb < 4; ++mb) {
+                ah[mb] = lw[((s * 8 + wn * 4 + mb) * 2 + 0) * 64 + lane];
+                al[mb] = lw[((s * 8 + wn * 4 + mb) * 2 + 1) * 64 + lane];
+            }
+#pragma unroll
+            for (int nb = 0; nb < NREP; ++nb) {
+                bh[nb] = la[(((wm * NREP + nb) * 2 + s) * 2 + 0) * 64 + lane];
+                bl[nb] = la[(((wm * NREP + nb) * 2 + s) * 2 + 1) * 64 + lane];
+            }
+#pragma unroll
+            for (int mb = 0; mb < 4; ++mb)
+#pragma unroll
+                for (int nb = 0; nb < NREP; ++nb) {
+                    acc[mb][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[mb], bh[nb], acc[mb][nb], 0, 0, 0);
+                    acc[mb][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[mb], bl[nb], acc[mb][nb], 0, 0, 0);
+                    acc[mb][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[mb], bh[nb], acc[mb][nb], 0, 0, 0);
+                }
+        }
+    }
+
+    // ---- epilogue: lane (li, g) holds channels 16 mb + 4 g .. + 3 of token li of block nb ----
+#pragma unroll
+    for (int nb = 0; nb < NREP; ++nb) {
+        const int row = m0 + (wm * NREP + nb) * 16 + li;
+        if (row >= p.M) continue;
+        int orow = row, view = 0, opix = 0, opixn = 1;
+        if (p.a_mode == VD_A_DECONV) {
+            const int hw = p.H * p.W, pix = row - (row / hw) * hw, y = pix / p.W, x = pix - y * p.W;
+            view = row / hw;
+            opixn = 4 * hw;
+            opix = (2 * y + (cls >> 1)) * 2 * p.W + 2 * x + (cls & 1);
+            orow = view * opixn + opix;
+        } else if (p.epi == VD_EPI_PLANAR) {
+            opixn = p.H * p.W;
+            view = row / opixn;
+            opix = row - view * opixn;
+        }
+#pragma unroll
+        for (int mb = 0; mb < 4; ++mb) {
+            const int ch = (nb0 + wn * 4 + mb) * 16 + 4 * g;
+            if (ch >= p.N) continue;
+            float v[4] = {acc[mb][nb][0], acc[mb][nb][1], acc[mb][nb][2], acc[mb][nb][3]};
+            if (p.bias) {
+                const float4 bb = *reinterpret_cast<const float4*>(p.bias + ch);
+                v[0] += bb.x; v[1] += bb.y; v[2] += bb.z; v[3] += bb.w;
+            }
+            if (p.epi == VD_EPI_F32) {
+                if (ch < p.elu_cols) {
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) v[k] = vd_elu1(v[k]);
+                }
+                *reinterpret_cast<float4*>(reinterpret_cast<float*>(p.out) + (size_t)row * p.N + ch) = make_float4(v[0], v[1], v[2], v[3]);
+            } else if (p.epi == VD_EPI_RESID) {
+                const float4 gg = *reinterpret_cast<const float4*>(p.gamma + ch);
+                const float4 rr = *reinterpret_cast<const float4*>(p.res + (size_t)row * p.N + ch);
+                *reinterpret_cast<float4*>(reinterpret_cast<float*>(p.out) + (size_t)row * p.N + ch) =
+                    make_float4(fmaf(gg.x, v[0], rr.x), fmaf(gg.y, v[1], rr.y), fmaf(gg.z, v[2], rr.z), fmaf(gg.w, v[3], rr.w));
+            } else {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) v[k] = vd_act(v[k], p.act);
+                if (p.epi == VD_EPI_SPLIT) {
+                    vd_store_split4(reinterpret_cast<bf16x8*>(p.out), p.N >> 5, orow, ch, v);
+                } else {
+                    float* o = reinterpret_cast<float*>(p.out) + ((size_t)view * p.N + ch) * opixn + opix;
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) o[(size_t)k * opixn] = v[k];
+                }
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// key/value summary and apply (exact fp32 products)
+// ---------------------------------------------------------------------------------------------------------------------------------
+// kv [NV * n, 1536] fp32: columns 0..767 = elu(Wk .) + 1, 768..1535 = Wv .   Workgroup (slab, head, view); wave = 16 rows d of KV_h.
+__global__ __launch_bounds__(256) void vd_kv_partial_kernel(const float* __restrict__ kv, float* __restrict__ part, int n, int per_slab) {
+    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, g = lane >> 4;
+    const int slab = (int)blockIdx.x, h = (int)blockIdx.y, view = (int)blockIdx.z, nslab = (int)gridDim.x;
+    const int t0 = slab * per_slab, t1 = t0 + per_slab < n ? t0 + per_slab : n;
+    const float* base = kv + (size_t)view * n * (2 * VD_C) + h * VD_HD;
+    f32x4 acc[4];
+#pragma unroll
+    for (int mb = 0; mb < 4; ++mb) acc[mb] = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
+    float ks = 0.0f;
+    for (int t = t0; t < t1; t += 4) {
+        const int tok = t + g;
+        const bool ok = tok < t1;
+        const float* row = base + (size_t)(ok ? tok : t0) * (2 * VD_C);
+        const float kval = ok ? row[16 * wave + li] : 0.0f;
+        ks += kval;
+#pragma unroll
+        for (int mb = 0; mb < 4; ++mb) {
+            const float vval = ok ? row[VD_C + 16 * mb + li] : 0.0f;
+            acc[mb] = __builtin_amdgcn_mfma_f32_16x16x4f32(kval, vval, acc[mb], 0, 0, 0);
+        }
+    }
+    ks += __shfl_xor(ks, 16);
+    ks += __shfl_xor(ks, 32);
+    float* dst = part + (((size_t)view * nslab + slab) * VD_HEADS + h) * VD_KVPART;
+#pragma unroll
+    for (int mb = 0; mb < 4; ++mb)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) dst[(16 * wave + 4 * g + r) * VD_HD + 16 * mb + li] = acc[mb][r];
+    if (g == 0) dst[VD_HD * VD_HD + 16 * wave + li] = ks;
+}
+
+__global__ __launch_bounds__(256) void vd_kv_reduce_kernel(const float* __restrict__ part, float* __restrict__ out, int nslab) {
+    const int e = (int)blockIdx.x * 256 + (int)threadIdx.x, h = (int)blockIdx.y, view = (int)blockIdx.z;
+    if (e >= VD_KVPART) return;
+    float s = 0.0f;
+    for (int sl = 0; sl < nslab; ++sl) s += part[(((size_t)view * nslab + sl) * VD_HEADS + h) * VD_KVPART + e];
+    out[((size_t)view * VD_HEADS + h) * VD_KVPART + e] = s;
+}
+
+// q [NV * n, 768] fp32 (elu + 1 applied), summary [NV / kv_div][12][KV_h | ksum_h] -> a packed-split [NV * n, 768].
+// Workgroup (256-token chunk, head, view); a wave holds KV_h (d = 16 g + s on the MFMA k index) and takes 4 x 16 tokens.
+__global__ __launch_bounds__(256) void vd_apply_kernel(const float* __restrict__ q, const float* __restrict__ summary, bf16x8* __restrict__ out, int n,
+                                                       int kv_div) {
+    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, g = lane >> 4;
+    const int h = (int)blockIdx.y, view = (int)blockIdx.z;
+    const int tw = ((int)blockIdx.x * 4 + wave) * 64;
+    if (tw >= n) return;                                           // wave-uniform; no workgroup barrier
+    const float* sm = summary + ((size_t)(view / kv_div) * VD_HEADS + h) * VD_KVPART;
+    float a[4][16], kz[16];
+#pragma unroll
+    for (int s = 0; s < 16; ++s) {
+        kz[s] = sm[VD_HD * VD_HD + 16 * g + s];
+#pragma unroll
+        for (int mb = 0; mb < 4; ++mb) a[mb][s] = sm[(16 * g + s) * VD_HD + 16 * mb + li];
+    }
+#pragma unroll 1
+    for (int tb = 0; tb < 4; ++tb) {
+        const int tok = tw + 16 * tb + li;
+        if (tw + 16 * tb >= n) break;                              // wave-uniform
+        const bool ok = tok < n;
+        const float* qr = q + ((size_t)view * n + (ok ? tok : 0)) * VD_C + h * VD_HD + 16 * g;
+        float qv[16];
+#pragma unroll
+        for (int s4 = 0; s4 < 4; ++s4) {
+            const float4 t = *reinterpret_cast<const float4*>(qr + 4 * s4);
+            qv[4 * s4 + 0] = t.x; qv[4 * s4 + 1] = t.y; qv[4 * s4 + 2] = t.z; qv[4 * s4 + 3] = t.w;
+        }
+        f32x4 acc[4], den = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+        for (int mb = 0; mb < 4; ++mb) acc[mb] = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+        for (int s = 0; s < 16; ++s) {
+#pragma unroll
+            for (int mb = 0; mb < 4; ++mb) acc[mb] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[mb][s], qv[s], acc[mb], 0, 0, 0);
+            den = __builtin_amdgcn_mfma_f32_16x16x4f32(kz[s], qv[s], den, 0, 0, 0);
+        }
+        if (!ok) continue;
+        const float z = den[0] + 1e-6f;
+#pragma unroll
+        for (int mb = 0; mb < 4; ++mb) {
+            const float v[4] = {acc[mb][0] / z, acc[mb][1] / z, acc[mb][2] / z, acc[mb][3] / z};
+            vd_store_split4(out, VD_C / 32, view * n + tok, h * VD_HD + 16 * mb + 4 * g, v);
+        }
+    }
+}
+
+static int vd_slabs(int n) {
+    const int s = (int)ceil_div(n, 64);
+    return s < VD_MAX_SLABS ? s : VD_MAX_SLABS;
+}
+
+static int vd_launch_gemm(const VdGemmArgs& p, int classes, hipStream_t st) {
+    const int nrep = p.M <= 32 ? 1 : (p.M <= 2048 ? 2 : 4);
+    const size_t lds = (size_t)(2 * nrep * 256 + 2048) * 16;
+    const dim3 grid(ceil_div(p.M, 32 * nrep), p.Npad / VD_TN, classes);
+    // more than 48 KB of dynamic LDS needs the attribute, once per kernel and device
+    static bool raised[3][64] = {};
+    int dev = 0;
+    hipGetDevice(&dev);
+#define MVS_VD_GO(NR, SLOT) \
+    if (nrep == NR) { \
+        if (lds > 48 * 1024 && !(dev >= 0 && dev < 64 && raised[SLOT][dev])) { \
+            hipFuncSetAttribute(reinterpret_cast<const void*>(&vd_gemm_kernel<NR>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
+            if (dev >= 0 && dev < 64) raised[SLOT][dev] = true; \
+        } \
+        hipLaunchKernelGGL((vd_gemm_kernel<NR>), grid, dim3(256), lds, st, p); \
+    }
+    MVS_VD_GO(1, 0) MVS_VD_GO(2, 1) MVS_VD_GO(4, 2)
+#undef MVS_VD_GO
+    return check_launch("vd_gemm_kernel");
+}
+
+}  // namespace mvs
+
+using namespace mvs;
+
+extern "C" size_t mvs_vitdec_packed_bytes(long long rows, int channels) {
+    if (rows < 1 || channels < 32 || channels % 32) return 0;
+    return (size_t)((rows + 15) / 16) * 16 * (size_t)channels * 4;
+}
+
+extern "C" size_t mvs_vitdec_summary_bytes(int NV) { return NV < 1 ? 0 : (size_t)NV * VD_HEADS * VD_KVPART * sizeof(float); }
+
+extern "C" size_t mvs_vitdec_kv_workspace_bytes(int NV, int n) {
+    if (NV < 1 || n < 1) return 0;
+    return (size_t)NV * vd_slabs(n) * VD_HEADS * VD_KVPART * sizeof(float);
+}
+
+extern "C" int mvs_vitdec_rows_fwd(const void* in, int in_dtype, long long in_batch_stride, long long in_view_stride, long long in_row_stride,
+                                   int in_v0, int in_views, const float* prev, const float* prev_value, const float* mix_w, const float* mix_b,
+                                   float* x, void* x_packed, int out_V, int out_v0, const float* ln_w, const float* ln_b, void* xn_packed,
+                                   int NV, int n, int channels, void* stream) {
+    if (channels != VD_C) {
+        set_error("mvs_vitdec_rows_fwd: built for rows of 768 channels (decoder_cfg d_model) [module.py:306]; got %d", channels);
+        return MVS_ERR_UNSUPPORTED;
+    }
+    if (!in || NV < 1 || n < 1 || (long long)NV * n >= (1LL << 24) || in_views < 1 || NV % in_views || in_v0 < 0 || out_v0 < 0 ||
+        out_V < out_v0 + in_views || in_row_stride < VD_C || (prev && !prev_value) || (!mix_w != !mix_b) || (xn_packed && (!ln_w || !ln_b)) ||
+        (!x && !x_packed && !xn_packed) || in_dtype < MVS_DTYPE_F32 || in_dtype > MVS_DTYPE_F16) {
+        set_error("mvs_vitdec_rows_fwd: bad arguments");
+        return MVS_ERR_ARG;
+    }
+    VdRowsArgs a{in, in_dtype, in_batch_stride, in_view_stride, in_row_stride, in_v0, in_views, prev, prev_value, mix_w, mix_b, x,
+                 reinterpret_cast<bf16x8*>(x_packed), ln_w, ln_b, reinterpret_cast<bf16x8*>(xn_packed), NV * n, n, out_V, out_v0};
+    const dim3 grid(ceil_div((long long)NV * n, 4));
+    hipStream_t st = (hipStream_t)stream;
+    if (in_dtype == MVS_DTYPE_F32) hipLaunchKernelGGL((vd_rows_kernel<MVS_DTYPE_F32>), grid, dim3(256), 0, st, a);
+    else if (in_dtype == MVS_DTYPE_BF16) hipLaunchKernelGGL((vd_rows_kernel<MVS_DTYPE_BF16>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((vd_rows_kernel<MVS_DTYPE_F16>), grid, dim3(256), 0, st, a);
+    return check_launch("vd_rows_kernel");
+}
+
+extern "C" int mvs_vitdec_linear_fwd(const void* a_packed, const void* w_packed, const float* bias, const float* gamma, const float* residual,
+                                     void* y, int M, int K, int N, int epilogue, int elu_cols, void* stream) {
+    const bool shape = (K == VD_C && (N == VD_C || N == 2 * VD_C || N == VD_HID)) || (K == VD_HID && N == VD_C);
+    if (!shape || epilogue < VD_EPI_F32 || epilogue > VD_EPI_SPLIT) {
+        set_error("mvs_vitdec_linear_fwd: built for the CrossBlock linears at d_model 768 (K -> N = 768 -> 768 | 1536 | 3072, 3072 -> 768) with "
+                  "epilogue 0 (fp32, elu + 1 on the leading columns), 1 (residual + gamma (. + bias)) or 2 (packed-split GELU(. + bias)) "
+                  "[block.py:294-329]; got K = %d, N = %d, epilogue %d", K, N, epilogue);
+        return MVS_ERR_UNSUPPORTED;
+    }
+    if (!a_packed || !w_packed || !y || M < 1 || M >= (1 << 24) || elu_cols < 0 || elu_cols > N || elu_cols % 4 ||
+        (epilogue == VD_EPI_RESID && (!gamma || !residual || !bias))) {
+        set_error("mvs_vitdec_linear_fwd: bad arguments");
+        return MVS_ERR_ARG;
+    }
+    VdGemmArgs p{};
+    p.a = reinterpret_cast<const bf16x8*>(a_packed);
+    p.w = reinterpret_cast<const bf16x8*>(w_packed);
+    p.bias = bias; p.gamma = gamma; p.res = residual; p.out = y;
+    p.M = M; p.K = K; p.N = N; p.Npad = N;
+    p.a_mode = VD_A_ROWS; p.epi = epilogue; p.act = epilogue == VD_EPI_SPLIT ? VD_ACT_GELU : VD_ACT_NONE; p.elu_cols = elu_cols;
+    p.C = K; p.H = 1; p.W = 1;
+    return vd_launch_gemm(p, 1, (hipStream_t)stream);
+}
+
+// layer 0: proj = Conv2d(768, 256, 3, padding 1); 1 / 2: upsampler0 / 1 = ConvTranspose2d(256, 128 | 128, 64, 4, stride 2, padding 1);
+// BatchNorm folded into (w_packed, bias), SiLU.  x packed-split tokens [NV * H * W, Cin]; y packed-split tokens of the output map
+// (planar = 0) or planar fp32 [NV, Cout, Ho, Wo] (planar = 1).
+extern "C" int mvs_vitdec_conv_fwd(const void* x_packed, const void* w_packed, const float* bias, void* y, int layer, int planar, int NV, int H,
+                                   int W, void* stream) {
+    if (layer < 0 || layer > 2) {
+        set_error("mvs_vitdec_conv_fwd: built for layer 0 (proj 768 -> 256, 3x3), 1 (upsampler0 256 -> 128) and 2 (upsampler1 128 -> 64, both "
+                  "ConvTranspose2d 4x4 stride 2 padding 1) [module.py:316-321]; got layer %d", layer);
+        return MVS_ERR_UNSUPPORTED;
+    }
+    if (!x_packed || !w_packed || !bias || !y || NV < 1 || H < 1 || W < 1 || H > 32767 || W > 32767 || (long long)NV * H * W >= (1LL << 22)) {
+        set_error("mvs_vitdec_conv_fwd: bad arguments");
+        return MVS_ERR_ARG;
+    }
+    static const int cin[3] = {VD_C, 256, 128}, cout[3] = {256, 128, 64}, taps[3] = {9, 4, 4};
+    VdGemmArgs p{};
+    p.a = reinterpret_cast<const bf16x8*>(x_packed);
+    p.w = reinterpret_cast<const bf16x8*>(w_packed);
+    p.bias = bias; p.out = y;
+    p.M = NV * H * W; p.K = taps[layer] * cin[layer]; p.N = cout[layer]; p.Npad = (cout[layer] + VD_TN - 1) / VD_TN * VD_TN;
+    p.a_mode = layer == 0 ? VD_A_CONV3 : VD_A_DECONV; p.epi = planar ? VD_EPI_PLANAR : VD_EPI_SPLIT; p.act = VD_ACT_SILU;
+    p.C = cin[layer]; p.H = H; p.W = W;
+    p.w_class = (size_t)(p.K / 32) * (p.Npad / 16) * 128;
+    return vd_launch_gemm(p, layer == 0 ? 1 : 4, (hipStream_t)stream);
+}
+
+extern "C" int mvs_vitdec_kv_fwd(const float* kv, void* workspace, size_t workspace_bytes, float* summary, int NV, int n, int channels,
+                                 void* stream) {
+    if (channels != 2 * VD_C) {
+        set_error("mvs_vitdec_kv_fwd: built for 12 heads of 64 channels: kv = [NV * n, 1536] (elu(k) + 1 | v) [attention.py:268-281]; got %d columns",
+                  channels);
+        return MVS_ERR_UNSUPPORTED;
+    }
+    if (!kv || !workspace || !summary || NV < 1 || NV > 65535 || n < 1 || (long long)NV * n >= (1LL << 24)) {
+        set_error("mvs_vitdec_kv_fwd: bad arguments");
+        return MVS_ERR_ARG;
+    }
+    if (workspace_bytes < mvs_vitdec_kv_workspace_bytes(NV, n)) {
+        set_error("mvs_vitdec_kv_fwd: workspace smaller than mvs_vitdec_kv_workspace_bytes");
+        return MVS_ERR_ARG;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const int slabs = vd_slabs(n), per_slab = ((int)ceil_div(n, slabs) + 3) / 4 * 4;
+    hipLaunchKernelGGL(vd_kv_partial_kernel, dim3(slabs, VD_HEADS, NV), dim3(256), 0, st, kv, reinterpret_cast<float*>(workspace), n, per_slab);
+    int rc = check_launch("vd_kv_partial_kernel");
+    if (rc != MVS_OK) return rc;
+    hipLaunchKernelGGL(vd_kv_reduce_kernel, dim3(ceil_div(VD_KVPART, 256), VD_HEADS, NV), dim3(256), 0, st, reinterpret_cast<const float*>(workspace),
+                       summary, slabs);
+    return check_launch("vd_kv_reduce_kernel");
+}
+
+extern "C" int mvs_vitdec_apply_fwd(const float* q, const float* summary, void* a_packed, int NV, int n, int kv_div, int channels, void* stream) {
+    if (channels != VD_C) {
+        set_error("mvs_vitdec_apply_fwd: built for 12 heads of 64 channels: q = [NV * n, 768] [attention.py:281-284]; got %d columns", channels);
+        return MVS_ERR_UNSUPPORTED;
+    }
+    if (!q || !summary || !a_packed || NV < 1 || NV > 65535 || n < 1 || kv_div < 1 || (long long)NV * n >= (1LL << 24)) {
+        set_error("mvs_vitdec_apply_fwd: bad arguments");
+        return MVS_ERR_ARG;
+    }
+    hipLaunchKernelGGL(vd_apply_kernel, dim3(ceil_div(n, 256), VD_HEADS, NV), dim3(256), 0, (hipStream_t)stream, q, summary,
+                       reinterpret_cast<bf16x8*>(a_packed), n, kv_div);
+    return check_launch("vd_apply_kernel");
+}

@@ -241,6 +241,151 @@ def fmt_smooth(x: torch.Tensor, w_packed: torch.Tensor) -> torch.Tensor:
     return out
 
 
+VITDEC_EPI_F32, VITDEC_EPI_RESID, VITDEC_EPI_GELU_SPLIT = 0, 1, 2
+VITDEC_PROJ, VITDEC_UP0, VITDEC_UP1 = 0, 1, 2
+_VITDEC_CONV = {VITDEC_PROJ: (768, 256, 9, 1), VITDEC_UP0: (256, 128, 4, 4), VITDEC_UP1: (128, 64, 4, 4)}     # Cin, Cout, taps, classes
+
+
+def _base_ptr(t: torch.Tensor):
+    """Address of element 0 of a tensor that may be strided (the device checks of ptr() on a one-element view of it)."""
+    return ptr(t.as_strided((1,), (1,)))
+
+
+def _vitdec_packed(t: Optional[torch.Tensor], rows: int, channels: int, what: str) -> None:
+    want = lib().mvs_vitdec_packed_bytes(rows, channels)
+    if t is None or t.dtype != torch.uint8 or t.dim() != 1 or t.numel() != want or not t.is_contiguous():
+        raise ValueError("%s must be a packed-split uint8 tensor of mvs_vitdec_packed_bytes(%d, %d) = %d bytes; got %s"
+                         % (what, rows, channels, want, None if t is None else (t.dtype, tuple(t.shape))))
+
+
+def _vitdec_vec(t: Optional[torch.Tensor], n: int, what: str, like: torch.Tensor) -> None:
+    if t is None or t.dtype != torch.float32 or t.numel() != n or not t.is_contiguous() or t.device != like.device:
+        raise ValueError("%s must be a contiguous fp32 vector of %d elements on %s; got %s"
+                         % (what, n, like.device, None if t is None else (t.dtype, tuple(t.shape), t.device)))
+
+
+def vitdec_rows(inp: torch.Tensor, v0: int, views: int, *, prev: Optional[torch.Tensor] = None, prev_value: Optional[torch.Tensor] = None,
+                mix: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, ln: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
+                want_x: bool = True, packed_into: Optional[torch.Tensor] = None, want_packed: bool = False, out_V: Optional[int] = None,
+                out_v0: int = 0):
+    """Row pass of the ViT decoder.  inp [B, Vall, n, 768] (fp32 / bf16 / fp16; ANY batch / view / row stride,
+    the 768 channels contiguous: it is read in place, nothing is copied): the rows of views v0 .. v0 + views - 1, M = B views n.
+    value = [prev_value * prev [M, 768] +] inp [-> LayerNorm(mix, eps 1e-6)].  Returns (x fp32 [M, 768] or None, x packed-split or None,
+    packed-split LayerNorm(ln, eps 1e-5)(x) or None).  The packed x goes to row (b * out_V + out_v0 + j) * n + t of `packed_into`
+    (default: a fresh buffer with out_V = views)."""
+    if inp.dim() != 4 or inp.shape[3] != 768 or inp.stride(3) != 1 or inp.dtype not in _lib.DTYPE_CODE or inp.stride(2) < 768 \
+            or inp.stride(0) < 0 or inp.stride(1) < 0:
+        raise ValueError("vitdec_rows takes [B, V, n, 768] fp32 / bf16 / fp16 with contiguous channels and rows that do not overlap (row stride >= 768); got %s %s strides %s"
+                         % (inp.dtype, tuple(inp.shape), tuple(inp.stride())))
+    B, Vall, n = inp.shape[:3]
+    if not (0 <= v0 and views >= 1 and v0 + views <= Vall and n >= 1):
+        raise ValueError("views %d .. %d of %d" % (v0, v0 + views - 1, Vall))
+    M = B * views * n
+    if prev is not None:
+        if prev.dtype != torch.float32 or tuple(prev.shape) != (M, 768) or not prev.is_contiguous():
+            raise ValueError("prev must be contiguous fp32 [%d, 768]; got %s %s" % (M, prev.dtype, tuple(prev.shape)))
+        _vitdec_vec(prev_value, 1, "prev_value", inp)
+    for pair, what in ((mix, "mix"), (ln, "ln")):
+        if pair is not None:
+            _vitdec_vec(pair[0], 768, what + " weight", inp)
+            _vitdec_vec(pair[1], 768, what + " bias", inp)
+    L = lib()
+    out_V = views if out_V is None else int(out_V)
+    xp = packed_into
+    if want_packed or xp is not None:
+        if out_v0 < 0 or out_V < out_v0 + views:
+            raise ValueError("out_V %d cannot hold views %d .. %d" % (out_V, out_v0, out_v0 + views - 1))
+        if xp is None:
+            xp = torch.empty(L.mvs_vitdec_packed_bytes(B * out_V * n, 768), dtype=torch.uint8, device=inp.device)
+        _vitdec_packed(xp, B * out_V * n, 768, "packed_into")
+    if not (want_x or xp is not None or ln is not None):
+        raise ValueError("vitdec_rows: nothing to compute")
+    x = torch.empty(M, 768, dtype=torch.float32, device=inp.device) if want_x else None
+    xn = torch.empty(L.mvs_vitdec_packed_bytes(M, 768), dtype=torch.uint8, device=inp.device) if ln is not None else None
+    check(L.mvs_vitdec_rows_fwd(_base_ptr(inp), _lib.DTYPE_CODE[inp.dtype], inp.stride(0), inp.stride(1), inp.stride(2), int(v0), int(views),
+                                ptr(prev), ptr(prev_value) if prev is not None else None, ptr(mix[0]) if mix else None,
+                                ptr(mix[1]) if mix else None, ptr(x), ptr(xp), out_V, int(out_v0), ptr(ln[0]) if ln else None,
+                                ptr(ln[1]) if ln else None, ptr(xn), B * views, n, 768, stream_of(inp)), "mvs_vitdec_rows_fwd")
+    return x, xp, xn
+
+
+def vitdec_linear(a_packed: torch.Tensor, M: int, w_packed: torch.Tensor, K: int, N: int, epilogue: int, *, bias: Optional[torch.Tensor] = None,
+                  gamma: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None, elu_cols: int = 0) -> torch.Tensor:
+    """y = epilogue(a W^T): a packed-split [M, K], w_packed = packing.pack_linear_bf16x3(W [N, K]).  VITDEC_EPI_F32 -> fp32 [M, N] with
+    elu(.) + 1 on columns < elu_cols; VITDEC_EPI_RESID -> fp32 residual + gamma * (. + bias); VITDEC_EPI_GELU_SPLIT -> packed-split
+    GELU(. + bias)."""
+    _vitdec_packed(a_packed, M, K, "a_packed")
+    if w_packed.dtype != torch.bfloat16 or w_packed.numel() != 2 * K * N or not w_packed.is_contiguous():
+        raise ValueError("w_packed must come from packing.pack_linear_bf16x3(W [%d, %d]): %d bf16 elements, got %s %d"
+                         % (N, K, 2 * K * N, w_packed.dtype, w_packed.numel()))
+    if bias is not None:
+        _vitdec_vec(bias, N, "bias", a_packed)
+    if epilogue == VITDEC_EPI_RESID:
+        _vitdec_vec(bias, N, "bias", a_packed)
+        _vitdec_vec(gamma, N, "gamma", a_packed)
+        if residual is None or residual.dtype != torch.float32 or tuple(residual.shape) != (M, N) or not residual.is_contiguous():
+            raise ValueError("residual must be contiguous fp32 [%d, %d]" % (M, N))
+    if epilogue == VITDEC_EPI_GELU_SPLIT:
+        out = torch.empty(lib().mvs_vitdec_packed_bytes(M, N), dtype=torch.uint8, device=a_packed.device)
+    else:
+        out = torch.empty(M, N, dtype=torch.float32, device=a_packed.device)
+    check(lib().mvs_vitdec_linear_fwd(ptr(a_packed), ptr(w_packed), ptr(bias), ptr(gamma), ptr(residual), ptr(out), int(M), int(K), int(N),
+                                      int(epilogue), int(elu_cols), stream_of(a_packed)), "mvs_vitdec_linear_fwd")
+    return out
+
+
+def vitdec_kv(kv: torch.Tensor, NV: int, n: int) -> torch.Tensor:
+    """Key/value summary: kv fp32 [NV * n, 1536] (elu(k) + 1 | v) -> fp32 [NV, 12, 64 * 64 + 64] = per head KV_h [d][m] | ksum_h [d],
+    from exact fp32 products, per-slab partials added in a fixed order (no atomics: bit-identical run to run)."""
+    if kv.dtype != torch.float32 or kv.dim() != 2 or kv.shape[0] != NV * n or not kv.is_contiguous():
+        raise ValueError("kv must be contiguous fp32 [NV * n, 1536]; got %s %s" % (kv.dtype, tuple(kv.shape)))
+    L = lib()
+    ws_bytes = L.mvs_vitdec_kv_workspace_bytes(NV, n)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=kv.device)
+    out = torch.empty(NV, 12, 64 * 64 + 64, dtype=torch.float32, device=kv.device)
+    check(L.mvs_vitdec_kv_fwd(ptr(kv), ptr(ws), ws_bytes, ptr(out), NV, n, kv.shape[1], stream_of(kv)), "mvs_vitdec_kv_fwd")
+    return out
+
+
+def vitdec_apply(q: torch.Tensor, summary: torch.Tensor, NV: int, n: int, kv_div: int = 1) -> torch.Tensor:
+    """a = (q . KV_h) / (q . ksum_h + 1e-6) per head: q fp32 [NV * n, 768] (elu + 1 applied); view i uses summary[i // kv_div] ->
+    packed-split [NV * n, 768]."""
+    if q.dtype != torch.float32 or q.dim() != 2 or q.shape[0] != NV * n or not q.is_contiguous():
+        raise ValueError("q must be contiguous fp32 [NV * n, 768]; got %s %s" % (q.dtype, tuple(q.shape)))
+    if summary.dtype != torch.float32 or summary.dim() != 3 or tuple(summary.shape[1:]) != (12, 4160) or not summary.is_contiguous() \
+            or kv_div < 1 or summary.shape[0] * kv_div < NV:
+        raise ValueError("summary must be vitdec_kv's fp32 [NVkv, 12, 4160] with NVkv * kv_div >= NV; got %s, kv_div %d, NV %d"
+                         % (tuple(summary.shape), kv_div, NV))
+    out = torch.empty(lib().mvs_vitdec_packed_bytes(NV * n, 768), dtype=torch.uint8, device=q.device)
+    check(lib().mvs_vitdec_apply_fwd(ptr(q), ptr(summary), ptr(out), NV, n, int(kv_div), q.shape[1], stream_of(q)), "mvs_vitdec_apply_fwd")
+    return out
+
+
+def vitdec_conv(x_packed: torch.Tensor, w_packed: torch.Tensor, bias: torch.Tensor, layer: int, NV: int, H: int, W: int,
+                planar: bool = False) -> torch.Tensor:
+    """proj (VITDEC_PROJ: Conv2d 768 -> 256, 3x3) / upsampler0, upsampler1 (VITDEC_UP0 / UP1: ConvTranspose2d 4x4 stride 2 padding 1) with
+    folded BatchNorm and SiLU on packed-split tokens of the [NV, H, W] map -> packed-split tokens of the output map, or planar fp32
+    [NV, Cout, Ho, Wo].  (w_packed, bias) = packing.pack_vitdec_conv / pack_vitdec_deconv."""
+    if layer in _VITDEC_CONV:
+        cin, cout, taps, classes = _VITDEC_CONV[layer]
+        _vitdec_packed(x_packed, NV * H * W, cin, "x_packed")
+        want = classes * taps * cin * ((cout + 127) // 128 * 128) * 2
+        if w_packed.dtype != torch.bfloat16 or w_packed.numel() != want or not w_packed.is_contiguous():
+            raise ValueError("w_packed must come from packing.pack_vitdec_%s: %d bf16 elements, got %s %d"
+                             % ("conv" if layer == VITDEC_PROJ else "deconv", want, w_packed.dtype, w_packed.numel()))
+        _vitdec_vec(bias, cout, "bias", x_packed)
+        s = 1 if layer == VITDEC_PROJ else 2
+        if planar:
+            out = torch.empty(NV, cout, s * H, s * W, dtype=torch.float32, device=x_packed.device)
+        else:
+            out = torch.empty(lib().mvs_vitdec_packed_bytes(NV * s * H * s * W, cout), dtype=torch.uint8, device=x_packed.device)
+    else:
+        out = torch.empty(1, dtype=torch.uint8, device=x_packed.device)       # the library refuses the layer
+    check(lib().mvs_vitdec_conv_fwd(ptr(x_packed), ptr(w_packed), ptr(bias), ptr(out), int(layer), 1 if planar else 0, NV, H, W,
+                                    stream_of(x_packed)), "mvs_vitdec_conv_fwd")
+    return out
+
+
 def _feat(t) -> Tuple[torch.Tensor, int]:
     if isinstance(t, PackedFeatures):
         return t, _lib.DTYPE_CODE[t.dtype]

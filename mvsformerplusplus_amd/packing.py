@@ -248,3 +248,80 @@ def pack_fmt_block(sd: Dict[str, torch.Tensor]) -> Tuple[torch.Tensor, torch.Ten
     v = torch.cat([sd[k].detach().float().cpu().reshape(-1) for k in FMT_VECTORS])
     assert w.numel() == 12288 * 8 and v.numel() == 768
     return w, v
+
+
+# ---- CrossVITDecoder (csrc/vitdec_kernels.hip) ----------------------------------------------------------
+def pack_tokens_split(x: torch.Tensor) -> torch.Tensor:
+    """x [M, C] fp32 (C % 32 == 0) -> the PACKED-SPLIT row operand of the vitdec GEMMs as a bf16 1-D tensor, rows zero-padded to a
+    multiple of 16:  packed[row >> 4][k >> 5][hi|lo][lane = ((k >> 3) & 3) * 16 + (row & 15)][k & 7].  The kernels write this layout
+    themselves; this host form is for tests and tools."""
+    m, c = x.shape
+    assert c % 32 == 0, (m, c)
+    mp = (m + 15) // 16 * 16
+    full = torch.zeros(mp, c, dtype=torch.float32, device=x.device)
+    full[:m] = x.float()
+    full = full.reshape(mp // 16, 16, c // 32, 4, 8).permute(0, 2, 3, 1, 4)                                       # [rb, step, g, li, e]
+    return _split_bf16(full).permute(1, 2, 0, 3, 4, 5).contiguous().reshape(-1)                                   # [rb, step, 2, g, li, e]
+
+
+def unpack_tokens_split(p: torch.Tensor, m: int, c: int) -> torch.Tensor:
+    """The inverse of pack_tokens_split (hi + lo in fp32) -> [m, c]; p may be the uint8 buffer a kernel wrote."""
+    if p.dtype == torch.uint8:
+        p = p.view(torch.bfloat16)
+    mp = (m + 15) // 16 * 16
+    f = p.float().reshape(mp // 16, c // 32, 2, 4, 16, 8)
+    return (f[:, :, 0] + f[:, :, 1]).permute(0, 3, 1, 2, 4).reshape(mp, c)[:m].contiguous()
+
+
+VITDEC_VECTORS = ("norm1.weight", "norm1.bias", "attn.proj.bias", "ls1.gamma", "norm2.weight", "norm2.bias", "mlp.fc1.bias", "mlp.fc2.bias",
+                  "ls2.gamma")
+
+
+def pack_vitdec_block(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """One CrossBlock at d_model 768 (keys relative to the block) -> {"q", "kv" ([k_proj; v_proj]), "proj", "fc1", "fc2"}: each
+    pack_linear_bf16x3, plus the fp32 vectors of VITDEC_VECTORS under their own names."""
+    mats = {"q": sd["attn.q_proj.weight"], "kv": torch.cat([sd["attn.k_proj.weight"], sd["attn.v_proj.weight"]], 0),
+            "proj": sd["attn.proj.weight"], "fc1": sd["mlp.fc1.weight"], "fc2": sd["mlp.fc2.weight"]}
+    want = {"q": (768, 768), "kv": (1536, 768), "proj": (768, 768), "fc1": (3072, 768), "fc2": (768, 3072)}
+    assert {k: tuple(v.shape) for k, v in mats.items()} == want, {k: tuple(v.shape) for k, v in mats.items()}
+    out = {k: pack_linear_bf16x3(v.detach().float().cpu()) for k, v in mats.items()}
+    for k in VITDEC_VECTORS:
+        out[k] = sd[k].detach().float().cpu().reshape(-1).contiguous()
+    return out
+
+
+def _fold_conv_bn(w: torch.Tensor, b: torch.Tensor, bn: Dict[str, torch.Tensor], out_dim: int):
+    """Conv (with bias) + eval BatchNorm -> (w * scale, (b - mean) * scale + beta), computed in fp64."""
+    scale = bn["weight"].double() / torch.sqrt(bn["running_var"].double() + float(bn.get("eps", BN_EPS)))
+    shape = [1] * w.dim()
+    shape[out_dim] = -1
+    return (w.double() * scale.reshape(shape)).float(), ((b.double() - bn["running_mean"].double()) * scale + bn["bias"].double()).float()
+
+
+def pack_vitdec_conv(w: torch.Tensor, b: torch.Tensor, bn: Dict[str, torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
+    """proj: Conv2d weight [Cout, Cin, 3, 3] + bias + BatchNorm -> (pack_linear_bf16x3 of the [Cout, 9 Cin] matrix whose column is
+    (ky * 3 + kx) * Cin + c, folded bias [Cout])."""
+    wf, bf = _fold_conv_bn(w.detach().float().cpu(), b.detach().float().cpu(), {k: (v.detach().cpu() if torch.is_tensor(v) else v) for k, v in bn.items()}, 0)
+    cout, cin = wf.shape[:2]
+    assert cout % 128 == 0 and cin % 64 == 0 and tuple(wf.shape[2:]) == (3, 3), tuple(wf.shape)
+    return pack_linear_bf16x3(wf.permute(0, 2, 3, 1).reshape(cout, 9 * cin).contiguous()), bf.contiguous()
+
+
+def pack_vitdec_deconv(w: torch.Tensor, b: torch.Tensor, bn: Dict[str, torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
+    """upsampler: ConvTranspose2d(4, stride 2, padding 1) weight [Cin, Cout, 4, 4] + bias + BatchNorm -> (the four parity classes
+    cls = 2 py + px one after the other, each pack_linear_bf16x3 of the [Cout padded to 128, 4 Cin] matrix whose column is
+    (2 ay + ax) * Cin + c and holds w[c][co][1 - py + 2 ay][1 - px + 2 ax] - output (2 y + py, 2 x + px) reads input (y + py - ay,
+    x + px - ax) -, folded bias [Cout])."""
+    wf, bf = _fold_conv_bn(w.detach().float().cpu(), b.detach().float().cpu(), {k: (v.detach().cpu() if torch.is_tensor(v) else v) for k, v in bn.items()}, 1)
+    cin, cout = wf.shape[:2]
+    assert cin % 64 == 0 and cout % 4 == 0 and tuple(wf.shape[2:]) == (4, 4), tuple(wf.shape)
+    npad = (cout + 127) // 128 * 128
+    chunks = []
+    for cls in range(4):
+        py, px = cls >> 1, cls & 1
+        m = torch.zeros(npad, 4, cin, dtype=torch.float32)
+        for ay in range(2):
+            for ax in range(2):
+                m[:cout, 2 * ay + ax] = wf[:, :, 1 - py + 2 * ay, 1 - px + 2 * ax].t()
+        chunks.append(pack_linear_bf16x3(m.reshape(npad, 4 * cin)))
+    return torch.cat(chunks), bf.contiguous()

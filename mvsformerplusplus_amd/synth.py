@@ -222,7 +222,7 @@ def seeded_state_dict(shapes: Dict[str, Tuple[int, ...]], seed: int) -> Dict[str
             for s in shp[1:]:
                 fan_in *= s
             a = rs.standard_normal(size=shp) * math.sqrt(2.0 / max(fan_in, 1))
-        out[k] = torch.from_numpy(a.astype(np.float32))
+        out[k] = torch.from_numpy(np.asarray(a, dtype=np.float32))           # (a 0-d shape gives a numpy scalar)
     return out
 
 
