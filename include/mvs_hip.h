@@ -5,7 +5,9 @@
  * The reference (maybeLx/MVSFormerPlusPlus @ 2025-01-14) is pure Python/PyTorch and has no
  * FFI of its own; the seam a maintainer binds is the set of Python callables cited next to each
  * entry point below (file:line relative to the reference tree).  INTEGRATION.md shows the ctypes
- * stub and the `patch_model()` swap.
+ * stub and the `patch_model()` swap.  The feature side of the network has its own sections further
+ * down: the FPN, FMT_with_pathway, the ViT feature decoder and the DINOv2 ViT-B/14 backbone
+ * (`patch_fpn`, `patch_fmt`, `patch_vit_decoder`, `patch_vit`; `patch_all` composes the five swaps).
  *
  * Calling convention
  *   - every pointer is a DEVICE pointer unless its name ends in _host
@@ -612,6 +614,35 @@ int mvs_vitdec_kv_fwd(const float* kv, void* workspace, size_t workspace_bytes, 
 int mvs_vitdec_apply_fwd(const float* q, const float* summary, void* a_packed, int NV, int n, int kv_div, int channels, void* stream);
 int mvs_vitdec_conv_fwd(const void* x_packed, const void* w_packed, const float* bias, void* y, int layer, int planar, int NV, int H, int W,
                         void* stream);
+
+/* ==== DINOv2 ViT-B/14 backbone: forward_interval_features ==============================================
+ * models/dino/dinov2.py vit_base(patch_size=14) with the shipped dino_cfg: 14 x 14 patch embedding + interpolated position embedding,
+ * pre-norm blocks (LayerNorm eps 1e-6, qkv with bias, softmax attention over the n + 1 tokens of a view with 12 heads of 64, LayerScale,
+ * fc1 - GELU (erf) - fc2).  The residual stream is fp32 [NV, npad, 768]: every view padded to npad = n + 1 rounded up to a multiple of
+ * 32 rows (row 0 = class token, rows 1 .. n = patches row-major, the rest finite padding that is masked as keys).  Packed-split
+ * operands and three-term products as in the decoder above; proj / fc1 / fc2 run on mvs_vitdec_linear_fwd with M = NV * npad.
+ * mvs_vit_rows_fwd: mvs_vitdec_rows_fwd with the eps of the ln_w / ln_b LayerNorm as an argument (the ViT's norm1 / norm2: 1e-6).
+ * mvs_vit_patches_fwd: image [NV, 3, 14 gh, 14 gw] (fp32 / bf16 / fp16, read in place with its four element strides) -> packed-split
+ *   [NV gh gw, 640]: column c * 196 + ky * 14 + kx, columns 588 .. 639 zero.
+ * mvs_vit_embed_fwd: x rows 1 .. n = patches W^T + bias + pos[1 + patch] (w_packed = packing.pack_vit_patch_embed, pos fp32 [n + 1, 768] =
+ *   the interpolated position table), row 0 = cls_pos (cls_token + pos[0]), rows n + 1 .. npad - 1 = 0.  Two launches.
+ * mvs_vit_qkv_fwd: xn W^T + bias (768 -> 2304) -> the attention operands, mvs_vit_qkv_bytes(NV, npad) bytes: per (view, head) q * q_scale
+ *   | k as packed-split rows of 64 channels, then v transposed: vt[key >> 5][d >> 4][hi|lo][lane = g * 16 + (d & 15)][e] with
+ *   key & 31 = 16 (e >> 2) + 4 g + (e & 3).  q_scale = softmax scale * log2(e).
+ * mvs_vit_attention_fwd: softmax(q k^T) v per (view, head) over keys 0 .. ntok - 1 (online softmax in fp32, exp2; no atomics, no split
+ *   over the keys: bit-identical run to run) -> packed-split [NV * npad, 768], the row operand of attn.proj.                        */
+size_t mvs_vit_qkv_bytes(int NV, int npad);
+int mvs_vit_rows_fwd(const void* in, int in_dtype, long long in_batch_stride, long long in_view_stride, long long in_row_stride, int in_v0,
+                     int in_views, const float* prev, const float* prev_value, const float* mix_w, const float* mix_b, float* x,
+                     void* x_packed, int out_V, int out_v0, const float* ln_w, const float* ln_b, float ln_eps, void* xn_packed, int NV, int n,
+                     int channels, void* stream);
+int mvs_vit_patches_fwd(const void* img, int dtype, long long batch_stride, long long channel_stride, long long row_stride,
+                        long long col_stride, void* a_packed, int NV, int gh, int gw, int patch, int in_chans, void* stream);
+int mvs_vit_embed_fwd(const void* a_packed, const void* w_packed, const float* bias, const float* pos, const float* cls_pos, float* x, int NV,
+                      int n, int npad, int channels, void* stream);
+int mvs_vit_qkv_fwd(const void* xn_packed, const void* w_packed, const float* bias, void* qkv, int NV, int npad, float q_scale, int channels,
+                    void* stream);
+int mvs_vit_attention_fwd(const void* qkv, void* a_packed, int NV, int ntok, int npad, int heads, int head_dim, void* stream);
 
 /* ---- layout helpers for the nn.Module-level API (NCDHW <-> channel-last) -------------------------*/
 int mvs_ncdhw_to_cl(const float* x, float* y_cl, int B, int C, int D, int H, int W, void* stream);

@@ -141,6 +141,12 @@ SIGNATURES = {
     "mvs_vitdec_kv_fwd": (_i, [_vp, _vp, _sz, _vp, _i, _i, _i, _vp]),
     "mvs_vitdec_apply_fwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "mvs_vitdec_conv_fwd": (_i, [_vp] * 4 + [_i] * 5 + [_vp]),
+    "mvs_vit_qkv_bytes": (_sz, [_i, _i]),
+    "mvs_vit_rows_fwd": (_i, [_vp, _i, C.c_longlong, C.c_longlong, C.c_longlong, _i, _i] + [_vp] * 6 + [_i, _i, _vp, _vp, _f, _vp, _i, _i, _i, _vp]),
+    "mvs_vit_patches_fwd": (_i, [_vp, _i] + [C.c_longlong] * 4 + [_vp, _i, _i, _i, _i, _i, _vp]),
+    "mvs_vit_embed_fwd": (_i, [_vp] * 6 + [_i] * 4 + [_vp]),
+    "mvs_vit_qkv_fwd": (_i, [_vp] * 4 + [_i, _i, _f, _i, _vp]),
+    "mvs_vit_attention_fwd": (_i, [_vp, _vp] + [_i] * 5 + [_vp]),
     "mvs_ncdhw_to_cl": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "mvs_cl_to_ncdhw": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
 }

@@ -27,7 +27,10 @@ FILE_FLAGS = {"transformer_kernels.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1", 
               # sigmoid): VGPR accumulators save 40 v_accvgpr moves per row and wave (18 % of the kernel's non-MFMA VALU instructions)
               # -fno-honor-nans: ReLU on an MFMA result is then ONE v_max_f32 (with NaNs honoured the compiler first canonicalises the
               # accumulator, a second v_max per value: 8 of 63 VALU per row and wave)
-              "vis_kernels.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1", "-fno-honor-nans"]}
+              "vis_kernels.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1", "-fno-honor-nans"],
+              # vit_attention_kernels: the score accumulators go straight into the softmax and come back as the next product's operand, the
+              # output accumulators are rescaled by VALU code every key step; masked scores are -inf and a step's max is finite
+              "vit_attention_kernels.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1", "-fno-honor-nans"]}
 
 
 def _digest():

@@ -14,19 +14,23 @@
 //
 // Kernels:
 //   1. vd_rows_kernel: one wave per token row.  [prev_value * prev +] input row (fp32 / bf16 / fp16, any batch / view / row stride)
-//      [-> LayerNorm eps 1e-6 (norm_layers)] -> x fp32 and / or packed-split(x) and / or packed-split(LayerNorm eps 1e-5 (x)).
+//      [-> LayerNorm eps 1e-6 (norm_layers)] -> x fp32 and / or packed-split(x) and / or packed-split(LayerNorm eps ln_eps (x)).
 //      prev_value is read from device memory.
 //   2. vd_gemm_kernel<NREP>: Y = epilogue(A W^T).  Workgroup = 2 x 2 waves, wave = 16 NREP tokens x 64 channels, tile 32 NREP x 128,
 //      K in chunks of 64 through LDS (both operands), the next chunk's global loads in flight during the MFMAs.  The row operand is
 //      read in place (linear layers), through a 3x3 window (proj: implicit GEMM, K = 9 x 768) or through the 2x2 window of one
 //      parity class of ConvTranspose2d(4, stride 2, padding 1) (upsampler0 / 1: K = 4 x Cin, blockIdx.z = class).  Epilogues: fp32
-//      (elu + 1 on the leading columns), residual + gamma * (. + bias), packed-split act(. + bias), planar fp32 silu(. + bias).
+//      (elu + 1 on the leading columns), residual + gamma * (. + bias), packed-split act(. + bias), planar fp32 silu(. + bias), and for
+//      the ViT backbone QKV (the attention operands of vit_split.h) and EMBED (+ bias + position row).
 //   3. vd_kv_partial_kernel + vd_kv_reduce_kernel: KV_h = sum_s k_s (x) v_s and ksum_h = sum_s k_s from exact fp32 products
 //      (v_mfma_f32_16x16x4_f32); per-slab partials added in slab order by the second launch: no atomics, bit-identical run to run.
 //   4. vd_apply_kernel: a = (q . KV_h) / (q . ksum_h + 1e-6) on the exact fp32 MFMA, KV_h held in registers -> packed-split.
+//   5. ViT backbone: vt_patches_kernel (14 x 14 x 3 patches of an image -> packed-split [M, 640]) and vt_cls_kernel (class rows, zeroed
+//      padding rows); its GEMMs and LayerNorm rows are kernels 1 and 2, its attention core is vit_attention_kernels.hip.
 // Rows past the end and window positions outside the map read as zero from a branch, never from an out-of-range load.
 #include "mvs_common.h"
 #include "split_format.h"
+#include "vit_split.h"
 
 namespace mvs {
 
@@ -37,7 +41,7 @@ constexpr int VD_KVPART = VD_HD * VD_HD + VD_HD;      // floats of one (view, he
 constexpr int VD_MAX_SLABS = 16;
 
 enum { VD_A_ROWS = 0, VD_A_CONV3 = 1, VD_A_DECONV = 2 };
-enum { VD_EPI_F32 = 0, VD_EPI_RESID = 1, VD_EPI_SPLIT = 2, VD_EPI_PLANAR = 3 };
+enum { VD_EPI_F32 = 0, VD_EPI_RESID = 1, VD_EPI_SPLIT = 2, VD_EPI_PLANAR = 3, VD_EPI_QKV = 4, VD_EPI_EMBED = 5 };
 enum { VD_ACT_NONE = 0, VD_ACT_GELU = 1, VD_ACT_SILU = 2 };
 
 __device__ __forceinline__ float vd_elu1(float t) { return t > 0.0f ? t + 1.0f : expf(t); }                      // elu(t) + 1
@@ -45,19 +49,6 @@ __device__ __forceinline__ float vd_act(float t, int act) {
     if (act == VD_ACT_GELU) return 0.5f * t * (1.0f + erff(t * 0.70710678118654752440f));
     if (act == VD_ACT_SILU) return t / (1.0f + expf(-t));
     return t;
-}
-
-// four consecutive channels ch .. ch + 3 (ch % 4 == 0) of row `orow` into a packed-split tensor of `steps` k-steps per row
-__device__ __forceinline__ void vd_store_split4(bf16x8* buf, int steps, int orow, int ch, const float (&v)[4]) {
-    __bf16 h[4], l[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        h[j] = (__bf16)v[j];
-        l[j] = (__bf16)(v[j] - (float)h[j]);
-    }
-    char* dst = reinterpret_cast<char*>(buf + (((size_t)(orow >> 4) * steps + (ch >> 5)) * 2) * 64 + ((ch >> 3) & 3) * 16 + (orow & 15)) + (ch & 4) * 2;
-    *reinterpret_cast<u32x2*>(dst) = (u32x2){pack_bf16x2(h[0], h[1]), pack_bf16x2(h[2], h[3])};
-    *reinterpret_cast<u32x2*>(dst + 64 * 16) = (u32x2){pack_bf16x2(l[0], l[1]), pack_bf16x2(l[2], l[3])};
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -74,10 +65,11 @@ struct VdRowsArgs {
     const float* mix_b;
     float* x;                    // [M, 768] fp32 (nullable)
     bf16x8* xp;                  // packed-split(x) at row ((b * out_V + out_v0 + j) * n + t) (nullable)
-    const float* ln_w;           // LayerNorm (eps 1e-5) -> xn packed-split at row r (nullable)
+    const float* ln_w;           // LayerNorm (eps ln_eps) -> xn packed-split at row r (nullable)
     const float* ln_b;
     bf16x8* xn;
     int M, n, out_V, out_v0;
+    float ln_eps;                // of the ln_w / ln_b LayerNorm: 1e-5 in the decoder, 1e-6 in the ViT backbone
 };
 
 __device__ __forceinline__ float vd_wave_sum(float s) {
@@ -156,7 +148,7 @@ __global__ __launch_bounds__(256) void vd_rows_kernel(VdRowsArgs a) {
     }
     if (a.xn) {
         float y[3][4];
-        vd_row_norm(v, a.ln_w, a.ln_b, 1e-5f, lane, y);
+        vd_row_norm(v, a.ln_w, a.ln_b, a.ln_eps, lane, y);
 #pragma unroll
         for (int j = 0; j < 3; ++j) vd_store_split4(a.xn, VD_C / 32, r, 4 * (lane + 64 * j), y[j]);
     }
@@ -174,8 +166,10 @@ struct VdGemmArgs {
     void* out;
     int M, K, N, Npad;
     int a_mode, epi, act, elu_cols;
-    int C, H, W;                 // windows: channels per tap, the source map; PLANAR: H W = pixels per view
+    int C, H, W;                 // windows: channels per tap, the source map; PLANAR: H W = pixels per view; QKV: W = rows per view (npad);
+                                 // EMBED: H = patches per view, W = rows per view of the residual stream, res = position rows [H + 1, N]
     size_t w_class;
+    float q_scale;               // QKV: the leading 768 columns (q) are multiplied by it
 };
 
 // The staged rows of one work-item, decomposed ONCE per workgroup: `base` = first source row of the row's view (windows) or the row itself
@@ -337,6 +331,21 @@ __global__ __launch_bounds__(256) void vd_gemm_kernel(VdGemmArgs p) {
                 const float4 rr = *reinterpret_cast<const float4*>(p.res + (size_t)row * p.N + ch);
                 *reinterpret_cast<float4*>(reinterpret_cast<float*>(p.out) + (size_t)row * p.N + ch) =
                     make_float4(fmaf(gg.x, v[0], rr.x), fmaf(gg.y, v[1], rr.y), fmaf(gg.z, v[2], rr.z), fmaf(gg.w, v[3], rr.w));
+            } else if (p.epi == VD_EPI_QKV) {
+                // q (x q_scale) | k -> packed-split rows of 64 channels per (view, head); v -> transposed (vit_split.h)
+                const int vw = row / p.W, t = row - vw * p.W, part = ch / VD_C, c = ch - part * VD_C;
+                bf16x8* sec = reinterpret_cast<bf16x8*>(p.out) + vit_qkv_section(vw, c >> 6, part, p.W);
+                if (part == 0) {
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) v[k] *= p.q_scale;
+                }
+                if (part < 2) vd_store_split4(sec, VD_HD / 32, t, c & 63, v);
+                else vit_store_vt4(sec, t, c & 63, v);
+            } else if (p.epi == VD_EPI_EMBED) {
+                const int vw = row / p.H, patch = row - vw * p.H;
+                const float4 pp = *reinterpret_cast<const float4*>(p.res + (size_t)(patch + 1) * p.N + ch);
+                *reinterpret_cast<float4*>(reinterpret_cast<float*>(p.out) + ((size_t)vw * p.W + patch + 1) * p.N + ch) =
+                    make_float4(v[0] + pp.x, v[1] + pp.y, v[2] + pp.z, v[3] + pp.w);
             } else {
 #pragma unroll
                 for (int k = 0; k < 4; ++k) v[k] = vd_act(v[k], p.act);
@@ -442,6 +451,50 @@ __global__ __launch_bounds__(256) void vd_apply_kernel(const float* __restrict__
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------
+// ViT backbone: patch gather, class / padding rows
+// ---------------------------------------------------------------------------------------------------------------------------------
+constexpr int VT_PATCH = 14, VT_K = 3 * VT_PATCH * VT_PATCH, VT_KPAD = 640;       // 588 zero-padded to the GEMM's chunk of 64
+
+struct VtPatchArgs {
+    const void* img;             // [NV, 3, 14 gh, 14 gw], read in place: element (v, c, y, x) at v sb + c sc + y sy + x sx
+    long long sb, sc, sy, sx;
+    bf16x8* out;                 // packed-split [NV gh gw, 640]: column c * 196 + ky * 14 + kx (the order of the convolution's weight)
+    int M, gh, gw;
+};
+
+template <int DT>
+__global__ __launch_bounds__(256) void vt_patches_kernel(VtPatchArgs a) {
+    typedef typename FeatT<DT>::type T;
+    const long long i = (long long)blockIdx.x * 256 + (int)threadIdx.x;
+    if (i >= (long long)a.M * (VT_KPAD / 4)) return;
+    const int row = (int)(i / (VT_KPAD / 4)), k0 = (int)(i - (long long)row * (VT_KPAD / 4)) * 4;
+    const int n = a.gh * a.gw, view = row / n, patch = row - view * n, py = patch / a.gw, px = patch - py * a.gw;
+    const T* src = reinterpret_cast<const T*>(a.img) + (size_t)view * a.sb;
+    float v[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int k = k0 + j;
+        v[j] = 0.0f;
+        if (k < VT_K) {
+            const int c = k / (VT_PATCH * VT_PATCH), rem = k - c * (VT_PATCH * VT_PATCH), ky = rem / VT_PATCH, kx = rem - ky * VT_PATCH;
+            v[j] = to_f32(src[(size_t)c * a.sc + (size_t)(py * VT_PATCH + ky) * a.sy + (size_t)(px * VT_PATCH + kx) * a.sx]);
+        }
+    }
+    vd_store_split4(a.out, VT_KPAD / 32, row, k0, v);
+}
+
+// row 0 of every view = cls_pos (cls_token + pos[0]); rows ntok .. npad - 1 = 0 (finite padding: masked as keys, never read as results)
+__global__ __launch_bounds__(256) void vt_cls_kernel(const float* __restrict__ cls_pos, float* __restrict__ x, int NV, int ntok, int npad) {
+    const int slots = 1 + npad - ntok;
+    const int i = (int)blockIdx.x * 256 + (int)threadIdx.x;
+    if (i >= NV * slots * (VD_C / 4)) return;
+    const int c4 = i % (VD_C / 4), rs = i / (VD_C / 4), view = rs / slots, slot = rs - view * slots;
+    const int row = slot == 0 ? 0 : ntok + slot - 1;
+    const float4 v = slot == 0 ? *reinterpret_cast<const float4*>(cls_pos + 4 * c4) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    *reinterpret_cast<float4*>(x + ((size_t)view * npad + row) * VD_C + 4 * c4) = v;
+}
+
 static int vd_slabs(int n) {
     const int s = (int)ceil_div(n, 64);
     return s < VD_MAX_SLABS ? s : VD_MAX_SLABS;
@@ -484,28 +537,45 @@ extern "C" size_t mvs_vitdec_kv_workspace_bytes(int NV, int n) {
     return (size_t)NV * vd_slabs(n) * VD_HEADS * VD_KVPART * sizeof(float);
 }
 
-extern "C" int mvs_vitdec_rows_fwd(const void* in, int in_dtype, long long in_batch_stride, long long in_view_stride, long long in_row_stride,
-                                   int in_v0, int in_views, const float* prev, const float* prev_value, const float* mix_w, const float* mix_b,
-                                   float* x, void* x_packed, int out_V, int out_v0, const float* ln_w, const float* ln_b, void* xn_packed,
-                                   int NV, int n, int channels, void* stream) {
+static int vd_rows(const char* who, const void* in, int in_dtype, long long in_batch_stride, long long in_view_stride, long long in_row_stride,
+                   int in_v0, int in_views, const float* prev, const float* prev_value, const float* mix_w, const float* mix_b, float* x,
+                   void* x_packed, int out_V, int out_v0, const float* ln_w, const float* ln_b, float ln_eps, void* xn_packed, int NV, int n,
+                   int channels, void* stream) {
     if (channels != VD_C) {
-        set_error("mvs_vitdec_rows_fwd: built for rows of 768 channels (decoder_cfg d_model) [module.py:306]; got %d", channels);
+        set_error("%s: built for rows of 768 channels (decoder_cfg d_model) [module.py:306]; got %d", who, channels);
         return MVS_ERR_UNSUPPORTED;
     }
     if (!in || NV < 1 || n < 1 || (long long)NV * n >= (1LL << 24) || in_views < 1 || NV % in_views || in_v0 < 0 || out_v0 < 0 ||
         out_V < out_v0 + in_views || in_row_stride < VD_C || (prev && !prev_value) || (!mix_w != !mix_b) || (xn_packed && (!ln_w || !ln_b)) ||
-        (!x && !x_packed && !xn_packed) || in_dtype < MVS_DTYPE_F32 || in_dtype > MVS_DTYPE_F16) {
-        set_error("mvs_vitdec_rows_fwd: bad arguments");
+        (!x && !x_packed && !xn_packed) || in_dtype < MVS_DTYPE_F32 || in_dtype > MVS_DTYPE_F16 || !(ln_eps > 0.0f)) {
+        set_error("%s: bad arguments", who);
         return MVS_ERR_ARG;
     }
     VdRowsArgs a{in, in_dtype, in_batch_stride, in_view_stride, in_row_stride, in_v0, in_views, prev, prev_value, mix_w, mix_b, x,
-                 reinterpret_cast<bf16x8*>(x_packed), ln_w, ln_b, reinterpret_cast<bf16x8*>(xn_packed), NV * n, n, out_V, out_v0};
+                 reinterpret_cast<bf16x8*>(x_packed), ln_w, ln_b, reinterpret_cast<bf16x8*>(xn_packed), NV * n, n, out_V, out_v0, ln_eps};
     const dim3 grid(ceil_div((long long)NV * n, 4));
     hipStream_t st = (hipStream_t)stream;
     if (in_dtype == MVS_DTYPE_F32) hipLaunchKernelGGL((vd_rows_kernel<MVS_DTYPE_F32>), grid, dim3(256), 0, st, a);
     else if (in_dtype == MVS_DTYPE_BF16) hipLaunchKernelGGL((vd_rows_kernel<MVS_DTYPE_BF16>), grid, dim3(256), 0, st, a);
     else hipLaunchKernelGGL((vd_rows_kernel<MVS_DTYPE_F16>), grid, dim3(256), 0, st, a);
     return check_launch("vd_rows_kernel");
+}
+
+extern "C" int mvs_vitdec_rows_fwd(const void* in, int in_dtype, long long in_batch_stride, long long in_view_stride, long long in_row_stride,
+                                   int in_v0, int in_views, const float* prev, const float* prev_value, const float* mix_w, const float* mix_b,
+                                   float* x, void* x_packed, int out_V, int out_v0, const float* ln_w, const float* ln_b, void* xn_packed,
+                                   int NV, int n, int channels, void* stream) {
+    return vd_rows("mvs_vitdec_rows_fwd", in, in_dtype, in_batch_stride, in_view_stride, in_row_stride, in_v0, in_views, prev, prev_value, mix_w,
+                   mix_b, x, x_packed, out_V, out_v0, ln_w, ln_b, 1e-5f, xn_packed, NV, n, channels, stream);
+}
+
+// the same row pass with the eps of the ln_w / ln_b LayerNorm as an argument (the ViT backbone's norm1 / norm2: 1e-6)
+extern "C" int mvs_vit_rows_fwd(const void* in, int in_dtype, long long in_batch_stride, long long in_view_stride, long long in_row_stride,
+                                int in_v0, int in_views, const float* prev, const float* prev_value, const float* mix_w, const float* mix_b,
+                                float* x, void* x_packed, int out_V, int out_v0, const float* ln_w, const float* ln_b, float ln_eps,
+                                void* xn_packed, int NV, int n, int channels, void* stream) {
+    return vd_rows("mvs_vit_rows_fwd", in, in_dtype, in_batch_stride, in_view_stride, in_row_stride, in_v0, in_views, prev, prev_value, mix_w,
+                   mix_b, x, x_packed, out_V, out_v0, ln_w, ln_b, ln_eps, xn_packed, NV, n, channels, stream);
 }
 
 extern "C" int mvs_vitdec_linear_fwd(const void* a_packed, const void* w_packed, const float* bias, const float* gamma, const float* residual,
@@ -595,4 +665,76 @@ extern "C" int mvs_vitdec_apply_fwd(const float* q, const float* summary, void* 
     hipLaunchKernelGGL(vd_apply_kernel, dim3(ceil_div(n, 256), VD_HEADS, NV), dim3(256), 0, (hipStream_t)stream, q, summary,
                        reinterpret_cast<bf16x8*>(a_packed), n, kv_div);
     return check_launch("vd_apply_kernel");
+}
+
+// ---- ViT backbone -----------------------------------------------------------------------------------------
+extern "C" int mvs_vit_patches_fwd(const void* img, int dtype, long long batch_stride, long long channel_stride, long long row_stride,
+                                   long long col_stride, void* a_packed, int NV, int gh, int gw, int patch, int in_chans, void* stream) {
+    if (patch != VT_PATCH || in_chans != 3) {
+        set_error("mvs_vit_patches_fwd: built for 14 x 14 patches of 3 channels (DINOv2 ViT-B/14 patch_embed) [patch_embed.py]; got patch %d, "
+                  "%d channels", patch, in_chans);
+        return MVS_ERR_UNSUPPORTED;
+    }
+    if (!img || !a_packed || NV < 1 || gh < 1 || gw < 1 || (long long)NV * gh * gw >= (1LL << 22) || dtype < MVS_DTYPE_F32 || dtype > MVS_DTYPE_F16 ||
+        batch_stride < 0 || channel_stride < 0 || row_stride < 0 || col_stride < 0) {
+        set_error("mvs_vit_patches_fwd: bad arguments");
+        return MVS_ERR_ARG;
+    }
+    VtPatchArgs a{img, batch_stride, channel_stride, row_stride, col_stride, reinterpret_cast<bf16x8*>(a_packed), NV * gh * gw, gh, gw};
+    const dim3 grid(ceil_div((long long)a.M * (VT_KPAD / 4), 256));
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == MVS_DTYPE_F32) hipLaunchKernelGGL((vt_patches_kernel<MVS_DTYPE_F32>), grid, dim3(256), 0, st, a);
+    else if (dtype == MVS_DTYPE_BF16) hipLaunchKernelGGL((vt_patches_kernel<MVS_DTYPE_BF16>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((vt_patches_kernel<MVS_DTYPE_F16>), grid, dim3(256), 0, st, a);
+    return check_launch("vt_patches_kernel");
+}
+
+// x [NV, npad, 768] fp32: row 0 = cls_pos, rows 1 .. n = patches W^T + bias + pos[1 + patch], rows n + 1 .. npad - 1 = 0
+extern "C" int mvs_vit_embed_fwd(const void* a_packed, const void* w_packed, const float* bias, const float* pos, const float* cls_pos, float* x,
+                                 int NV, int n, int npad, int channels, void* stream) {
+    if (channels != VD_C) {
+        set_error("mvs_vit_embed_fwd: built for embed_dim 768 (DINOv2 ViT-B/14) [dinov2.py:388-398]; got %d", channels);
+        return MVS_ERR_UNSUPPORTED;
+    }
+    if (!a_packed || !w_packed || !bias || !pos || !cls_pos || !x || NV < 1 || n < 1 || npad < n + 1 || npad % VIT_KEY_STEP ||
+        (long long)NV * npad >= (1LL << 22)) {
+        set_error("mvs_vit_embed_fwd: bad arguments (npad = n + 1 tokens per view padded to a multiple of 32)");
+        return MVS_ERR_ARG;
+    }
+    VdGemmArgs p{};
+    p.a = reinterpret_cast<const bf16x8*>(a_packed);
+    p.w = reinterpret_cast<const bf16x8*>(w_packed);
+    p.bias = bias; p.res = pos; p.out = x;
+    p.M = NV * n; p.K = VT_KPAD; p.N = VD_C; p.Npad = VD_C;
+    p.a_mode = VD_A_ROWS; p.epi = VD_EPI_EMBED; p.act = VD_ACT_NONE;
+    p.C = VT_KPAD; p.H = n; p.W = npad;
+    int rc = vd_launch_gemm(p, 1, (hipStream_t)stream);
+    if (rc != MVS_OK) return rc;
+    const int slots = 1 + npad - (n + 1);
+    hipLaunchKernelGGL(vt_cls_kernel, dim3(ceil_div((long long)NV * slots * (VD_C / 4), 256)), dim3(256), 0, (hipStream_t)stream, cls_pos, x, NV,
+                       n + 1, npad);
+    return check_launch("vt_cls_kernel");
+}
+
+// qkv [mvs_vit_qkv_bytes(NV, npad)]: the attention core's operands (vit_split.h) = xn W^T + bias, the q columns times q_scale
+extern "C" int mvs_vit_qkv_fwd(const void* xn_packed, const void* w_packed, const float* bias, void* qkv, int NV, int npad, float q_scale,
+                               int channels, void* stream) {
+    if (channels != VD_C) {
+        set_error("mvs_vit_qkv_fwd: built for embed_dim 768, 12 heads of 64 (DINOv2 ViT-B/14) [attention.py:68-79]; got %d", channels);
+        return MVS_ERR_UNSUPPORTED;
+    }
+    if (!xn_packed || !w_packed || !bias || !qkv || NV < 1 || npad < VIT_KEY_STEP || npad % VIT_KEY_STEP || (long long)NV * npad >= (1LL << 22) ||
+        !(q_scale > 0.0f)) {
+        set_error("mvs_vit_qkv_fwd: bad arguments (npad = tokens per view padded to a multiple of 32)");
+        return MVS_ERR_ARG;
+    }
+    VdGemmArgs p{};
+    p.a = reinterpret_cast<const bf16x8*>(xn_packed);
+    p.w = reinterpret_cast<const bf16x8*>(w_packed);
+    p.bias = bias; p.out = qkv;
+    p.M = NV * npad; p.K = VD_C; p.N = 3 * VD_C; p.Npad = 3 * VD_C;
+    p.a_mode = VD_A_ROWS; p.epi = VD_EPI_QKV; p.act = VD_ACT_NONE;
+    p.C = VD_C; p.H = 1; p.W = npad;
+    p.q_scale = q_scale;
+    return vd_launch_gemm(p, 1, (hipStream_t)stream);
 }

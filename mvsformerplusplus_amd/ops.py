@@ -386,6 +386,101 @@ def vitdec_conv(x_packed: torch.Tensor, w_packed: torch.Tensor, bias: torch.Tens
     return out
 
 
+VIT_KEY_STEP = 32          # the attention core's key step: every view's rows are padded to a multiple of it
+VIT_KPAD = 640             # the patch embedding's K = 588 padded to the GEMM's chunk
+
+
+def vit_npad(ntok: int) -> int:
+    """Rows per view of the ViT's working buffers: ntok = n + 1 tokens rounded up to a multiple of 32."""
+    return (int(ntok) + VIT_KEY_STEP - 1) // VIT_KEY_STEP * VIT_KEY_STEP
+
+
+def vit_rows(x: torch.Tensor, *, ln: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, eps: float = 1e-6,
+             norm: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
+    """Row pass of the ViT backbone on the residual stream x fp32 contiguous [M, 768]: ln -> packed-split LayerNorm(ln, eps)(x) (the row
+    operand of qkv / fc1); norm -> fp32 [M, 768] LayerNorm(norm, eps 1e-6)(x) (the final norm).  Returns (normed or None, packed or None)."""
+    if x.dtype != torch.float32 or x.dim() != 2 or x.shape[1] != 768 or not x.is_contiguous():
+        raise ValueError("vit_rows takes the residual stream: contiguous fp32 [M, 768]; got %s %s" % (x.dtype, tuple(x.shape)))
+    if (ln is None) == (norm is None):
+        raise ValueError("vit_rows: give exactly one of ln (packed-split output) and norm (fp32 output)")
+    for pair, what in ((ln, "ln"), (norm, "norm")):
+        if pair is not None:
+            _vitdec_vec(pair[0], 768, what + " weight", x)
+            _vitdec_vec(pair[1], 768, what + " bias", x)
+    M = x.shape[0]
+    L = lib()
+    y = torch.empty_like(x) if norm is not None else None
+    xn = torch.empty(L.mvs_vitdec_packed_bytes(M, 768), dtype=torch.uint8, device=x.device) if ln is not None else None
+    check(L.mvs_vit_rows_fwd(ptr(x), 0, M * 768, M * 768, 768, 0, 1, None, None, ptr(norm[0]) if norm else None, ptr(norm[1]) if norm else None,
+                             ptr(y), None, 1, 0, ptr(ln[0]) if ln else None, ptr(ln[1]) if ln else None, float(eps), ptr(xn), 1, M, 768,
+                             stream_of(x)), "mvs_vit_rows_fwd")
+    return y, xn
+
+
+def vit_patches(img: torch.Tensor) -> torch.Tensor:
+    """img [NV, 3, 14 gh, 14 gw] (fp32 / bf16 / fp16, ANY strides: read in place) -> the packed-split [NV gh gw, 640] row operand of the
+    patch embedding (column c * 196 + ky * 14 + kx, zero past 588)."""
+    if img.dim() != 4 or img.shape[1] != 3 or img.dtype not in _lib.DTYPE_CODE or img.shape[2] % 14 or img.shape[3] % 14 or min(img.shape) < 1 \
+            or min(img.stride()) < 0:
+        raise ValueError("vit_patches takes an image [NV, 3, H, W] fp32 / bf16 / fp16 with H and W multiples of 14; got %s %s"
+                         % (img.dtype, tuple(img.shape)))
+    NV, _, H, W = img.shape
+    gh, gw = H // 14, W // 14
+    out = torch.empty(lib().mvs_vitdec_packed_bytes(NV * gh * gw, VIT_KPAD), dtype=torch.uint8, device=img.device)
+    check(lib().mvs_vit_patches_fwd(_base_ptr(img), _lib.DTYPE_CODE[img.dtype], img.stride(0), img.stride(1), img.stride(2), img.stride(3),
+                                    ptr(out), NV, gh, gw, 14, 3, stream_of(img)), "mvs_vit_patches_fwd")
+    return out
+
+
+def vit_embed(a_packed: torch.Tensor, w_packed: torch.Tensor, bias: torch.Tensor, pos: torch.Tensor, cls_pos: torch.Tensor, NV: int,
+              n: int) -> torch.Tensor:
+    """The ViT's tokens: fp32 [NV * npad, 768] with npad = vit_npad(n + 1): per view row 0 = cls_pos, rows 1 .. n = patches W^T + bias +
+    pos[1 + patch], the rest zero.  (w_packed, bias) = packing.pack_vit_patch_embed, pos = packing.vit_position_table [n + 1, 768],
+    cls_pos = cls_token + pos[0]."""
+    _vitdec_packed(a_packed, NV * n, VIT_KPAD, "a_packed")
+    if w_packed.dtype != torch.bfloat16 or w_packed.numel() != 2 * VIT_KPAD * 768 or not w_packed.is_contiguous():
+        raise ValueError("w_packed must come from packing.pack_vit_patch_embed: %d bf16 elements, got %s %d"
+                         % (2 * VIT_KPAD * 768, w_packed.dtype, w_packed.numel()))
+    _vitdec_vec(bias, 768, "bias", a_packed)
+    _vitdec_vec(pos, (n + 1) * 768, "pos", a_packed)
+    _vitdec_vec(cls_pos, 768, "cls_pos", a_packed)
+    npad = vit_npad(n + 1)
+    x = torch.empty(NV * npad, 768, dtype=torch.float32, device=a_packed.device)
+    check(lib().mvs_vit_embed_fwd(ptr(a_packed), ptr(w_packed), ptr(bias), ptr(pos), ptr(cls_pos), ptr(x), int(NV), int(n), npad, 768,
+                                  stream_of(a_packed)), "mvs_vit_embed_fwd")
+    return x
+
+
+def vit_qkv(xn_packed: torch.Tensor, w_packed: torch.Tensor, bias: torch.Tensor, NV: int, npad: int, q_scale: float) -> torch.Tensor:
+    """The attention core's operands (uint8, mvs_vit_qkv_bytes(NV, npad)) from xn packed-split [NV * npad, 768]: q * q_scale | k per head
+    as packed-split rows, v transposed.  w_packed = pack_linear_bf16x3(qkv.weight [2304, 768]); q_scale = softmax scale * log2(e)."""
+    if npad < VIT_KEY_STEP or npad % VIT_KEY_STEP:
+        raise ValueError("npad must be a multiple of %d (ops.vit_npad); got %d" % (VIT_KEY_STEP, npad))
+    _vitdec_packed(xn_packed, NV * npad, 768, "xn_packed")
+    if w_packed.dtype != torch.bfloat16 or w_packed.numel() != 2 * 768 * 2304 or not w_packed.is_contiguous():
+        raise ValueError("w_packed must come from packing.pack_linear_bf16x3(qkv.weight [2304, 768]): %d bf16 elements, got %s %d"
+                         % (2 * 768 * 2304, w_packed.dtype, w_packed.numel()))
+    _vitdec_vec(bias, 2304, "bias", xn_packed)
+    out = torch.empty(lib().mvs_vit_qkv_bytes(NV, npad), dtype=torch.uint8, device=xn_packed.device)
+    check(lib().mvs_vit_qkv_fwd(ptr(xn_packed), ptr(w_packed), ptr(bias), ptr(out), int(NV), int(npad), float(q_scale), 768,
+                                stream_of(xn_packed)), "mvs_vit_qkv_fwd")
+    return out
+
+
+def vit_attention(qkv: torch.Tensor, NV: int, ntok: int, npad: int, heads: int = 12, head_dim: int = 64) -> torch.Tensor:
+    """softmax(q k^T) v over the ntok tokens of each view and head (q pre-scaled, scores in log2 units) -> packed-split [NV * npad, 768]."""
+    if npad < VIT_KEY_STEP or npad % VIT_KEY_STEP or not 1 <= ntok <= npad:
+        raise ValueError("vit_attention: 1 <= ntok <= npad, npad a multiple of %d; got ntok %d, npad %d" % (VIT_KEY_STEP, ntok, npad))
+    want = lib().mvs_vit_qkv_bytes(NV, npad)
+    if qkv.dtype != torch.uint8 or qkv.dim() != 1 or qkv.numel() != want or not qkv.is_contiguous():
+        raise ValueError("qkv must be vit_qkv's uint8 tensor of mvs_vit_qkv_bytes(%d, %d) = %d bytes; got %s %s"
+                         % (NV, npad, want, qkv.dtype, tuple(qkv.shape)))
+    out = torch.empty(lib().mvs_vitdec_packed_bytes(NV * npad, 768), dtype=torch.uint8, device=qkv.device)
+    check(lib().mvs_vit_attention_fwd(ptr(qkv), ptr(out), int(NV), int(ntok), int(npad), int(heads), int(head_dim), stream_of(qkv)),
+          "mvs_vit_attention_fwd")
+    return out
+
+
 def _feat(t) -> Tuple[torch.Tensor, int]:
     if isinstance(t, PackedFeatures):
         return t, _lib.DTYPE_CODE[t.dtype]

@@ -325,3 +325,69 @@ def pack_vitdec_deconv(w: torch.Tensor, b: torch.Tensor, bn: Dict[str, torch.Ten
                 m[:cout, 2 * ay + ax] = wf[:, :, 1 - py + 2 * ay, 1 - px + 2 * ax].t()
         chunks.append(pack_linear_bf16x3(m.reshape(npad, 4 * cin)))
     return torch.cat(chunks), bf.contiguous()
+
+
+# ---- DINOv2 ViT-B/14 backbone (csrc/vitdec_kernels.hip, csrc/vit_attention_kernels.hip) ----------------------
+VIT_VECTORS = ("norm1.weight", "norm1.bias", "attn.qkv.bias", "attn.proj.bias", "ls1.gamma", "norm2.weight", "norm2.bias", "mlp.fc1.bias",
+               "mlp.fc2.bias", "ls2.gamma")
+VIT_PATCH_K, VIT_PATCH_KPAD = 588, 640
+
+
+def pack_vit_block(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """One DINOv2 block at embed_dim 768 (keys relative to the block) -> {"qkv" ([2304, 768]: q | k | v, 12 heads of 64 each), "proj", "fc1",
+    "fc2"}: each pack_linear_bf16x3, plus the fp32 vectors of VIT_VECTORS under their own names."""
+    mats = {"qkv": sd["attn.qkv.weight"], "proj": sd["attn.proj.weight"], "fc1": sd["mlp.fc1.weight"], "fc2": sd["mlp.fc2.weight"]}
+    want = {"qkv": (2304, 768), "proj": (768, 768), "fc1": (3072, 768), "fc2": (768, 3072)}
+    assert {k: tuple(v.shape) for k, v in mats.items()} == want, {k: tuple(v.shape) for k, v in mats.items()}
+    out = {k: pack_linear_bf16x3(v.detach().float().cpu()) for k, v in mats.items()}
+    for k in VIT_VECTORS:
+        out[k] = sd[k].detach().float().cpu().reshape(-1).contiguous()
+    return out
+
+
+def pack_vit_patch_embed(w: torch.Tensor, b: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """patch_embed.proj: Conv2d(3, 768, 14, stride 14) weight [768, 3, 14, 14] + bias -> (pack_linear_bf16x3 of the [768, 640] matrix
+    whose column is c * 196 + ky * 14 + kx, columns 588 .. 639 zero: the GEMM's K granularity is 64; bias fp32 [768])."""
+    assert tuple(w.shape) == (768, 3, 14, 14) and tuple(b.shape) == (768,), (tuple(w.shape), tuple(b.shape))
+    m = torch.zeros(768, VIT_PATCH_KPAD, dtype=torch.float32)
+    m[:, :VIT_PATCH_K] = w.detach().float().cpu().reshape(768, VIT_PATCH_K)
+    return pack_linear_bf16x3(m), b.detach().float().cpu().contiguous()
+
+
+def vit_position_table(pos_embed: torch.Tensor, gh: int, gw: int) -> torch.Tensor:
+    """The position rows of a gh x gw patch grid, fp32 [gh gw + 1, 768], by the reference's recipe (dinov2.py interpolate_pos_encoding):
+    row 0 is the class position; the side x side patch table is resized with bicubic F.interpolate called with
+    scale_factor = ((gh + 0.1) / side, (gw + 0.1) / side) - PyTorch maps coordinates with the GIVEN factors, so the same function is
+    called with the same arguments here, nothing is re-derived.  The first factor belongs to the rows of the grid (the image's height,
+    which the reference names `w`).  A square grid of the table's own size returns the table as it is.  Parameter preprocessing:
+    computed once per (grid, parameter version) and cached by the module."""
+    import math
+    import torch.nn.functional as F
+    p = pos_embed.detach().float().cpu()
+    N, dim = p.shape[1] - 1, p.shape[2]
+    if gh * gw == N and gh == gw:
+        return p[0].contiguous()
+    side = int(math.sqrt(N))
+    assert side * side == N, N
+    grid = p[:, 1:].reshape(1, side, side, dim).permute(0, 3, 1, 2)
+    grid = F.interpolate(grid, scale_factor=((gh + 0.1) / math.sqrt(N), (gw + 0.1) / math.sqrt(N)), mode="bicubic")
+    assert tuple(grid.shape[-2:]) == (gh, gw), (tuple(grid.shape), gh, gw)
+    return torch.cat((p[0, :1], grid.permute(0, 2, 3, 1).reshape(gh * gw, dim)), 0).contiguous()
+
+
+def pack_vit_qkv(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, npad: int) -> torch.Tensor:
+    """q, k, v [NV, 12, ntok, 64] fp32 (q already multiplied by scale * log2(e)) -> the operand buffer of the attention core as a uint8
+    1-D tensor: per (view, head) q | k as pack_tokens_split rows (zero-padded to npad, a multiple of 32), then v transposed:
+    vt[key >> 5][d >> 4][hi|lo][lane = g * 16 + (d & 15)][e] with key & 31 = 16 (e >> 2) + 4 g + (e & 3).  The qkv projection's epilogue
+    writes this layout itself; this host form is for tests and tools."""
+    NV, H, ntok, D = q.shape
+    assert H == 12 and D == 64 and npad % 32 == 0 and npad >= ntok and k.shape == q.shape and v.shape == q.shape, (tuple(q.shape), npad)
+    parts = []
+    for view in range(NV):
+        for h in range(H):
+            parts.append(pack_tokens_split(torch.cat([q[view, h].float(), q.new_zeros(npad - ntok, D).float()])))
+            parts.append(pack_tokens_split(torch.cat([k[view, h].float(), k.new_zeros(npad - ntok, D).float()])))
+            vp = torch.cat([v[view, h].float(), v.new_zeros(npad - ntok, D).float()])
+            vt = vp.reshape(npad // 32, 2, 4, 4, 4, 16).permute(0, 4, 2, 5, 1, 3).reshape(npad // 32, 4, 4, 16, 8)   # [ks, db, g, d & 15, e]
+            parts.append(_split_bf16(vt).permute(1, 2, 0, 3, 4, 5).contiguous().reshape(-1))                       # [ks, db, 2, g, d, e]
+    return torch.cat(parts).view(torch.uint8)
