@@ -648,6 +648,20 @@ int mvs_vit_attention_fwd(const void* qkv, void* a_packed, int NV, int ntok, int
 int mvs_ncdhw_to_cl(const float* x, float* y_cl, int B, int C, int D, int H, int W, void* stream);
 int mvs_cl_to_ncdhw(const float* x_cl, float* y, int B, int C, int D, int H, int W, void* stream);
 
+/* ==== the network's glue (DINOv2_mvsformer_model.py:72-88) ===============================================
+ * mvs_resize_bicubic_fwd: img fp32 [N,C,H,W] read in place with its four element strides -> out contiguous fp32 [N,C,h,w] =
+ *   F.interpolate(img, (h, w), mode="bicubic", align_corners=False) without antialiasing: source coordinate (dst + 0.5) * (in / out) - 0.5,
+ *   cubic convolution coefficients with A = -0.75, each of the 4 x 4 tap indices clamped to [0, in - 1].  Any scale, any size >= 1.
+ * mvs_resize_bilinear_add_fwd: out = base + F.interpolate(x, (h, w), mode="bilinear", align_corners=False); base, out contiguous fp32
+ *   [N,C,h,w], x fp32 [N,C,xh,xw] read in place with its strides; source coordinate max(0, (dst + 0.5) * (in / out) - 0.5), the upper
+ *   neighbour clamped.  (xh, xw) == (h, w): out = base + x bit for bit.  out may be base.
+ * The source coordinate is evaluated as an exact rational (floor + once-rounded fraction), not in fp32.  Sizes <= 32768, N * C <= 65535,
+ * strides >= 0.  One launch each, no workspace.                                                                     */
+int mvs_resize_bicubic_fwd(const float* img, long long batch_stride, long long channel_stride, long long row_stride, long long col_stride,
+                           float* out, int N, int C, int H, int W, int h, int w, void* stream);
+int mvs_resize_bilinear_add_fwd(const float* base, const float* x, long long batch_stride, long long channel_stride, long long row_stride,
+                                long long col_stride, float* out, int N, int C, int h, int w, int xh, int xw, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -149,6 +149,8 @@ SIGNATURES = {
     "mvs_vit_attention_fwd": (_i, [_vp, _vp] + [_i] * 5 + [_vp]),
     "mvs_ncdhw_to_cl": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "mvs_cl_to_ncdhw": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "mvs_resize_bicubic_fwd": (_i, [_vp] + [C.c_longlong] * 4 + [_vp] + [_i] * 6 + [_vp]),
+    "mvs_resize_bilinear_add_fwd": (_i, [_vp, _vp] + [C.c_longlong] * 4 + [_vp] + [_i] * 6 + [_vp]),
 }
 
 

@@ -1437,3 +1437,40 @@ def cl_to_ncdhw(x_cl: torch.Tensor) -> torch.Tensor:
     y = torch.empty(B, Cc, D, H, W, dtype=torch.float32, device=x_cl.device)
     check(lib().mvs_cl_to_ncdhw(ptr(x_cl), ptr(y), B, Cc, D, H, W, stream_of(x_cl)), "mvs_cl_to_ncdhw")
     return y
+
+
+def _resize_source(t: torch.Tensor, what: str) -> None:
+    if not torch.is_tensor(t) or t.dim() != 4 or t.dtype != torch.float32 or min(t.shape) < 1 or min(t.stride()) < 0:
+        raise ValueError("%s must be a fp32 tensor [N, C, H, W] with no empty axis; got %s"
+                         % (what, (t.dtype, tuple(t.shape)) if torch.is_tensor(t) else type(t)))
+
+
+def resize_bicubic(img: torch.Tensor, h: int, w: int) -> torch.Tensor:
+    """F.interpolate(img, (h, w), mode="bicubic", align_corners=False) without antialiasing (DINOv2_mvsformer_model.py:76): img fp32
+    [N, C, H, W] with ANY strides (read in place: a [B V, 3, H, W] view of [B, V, 3, H, W] is not copied) -> contiguous fp32 [N, C, h, w].
+    Any scale (taps skip pixels when scaling down by more than 2), any axis length >= 1."""
+    _resize_source(img, "img")
+    h, w = int(h), int(w)
+    if h < 1 or w < 1:
+        raise ValueError("resize_bicubic: the output size must be at least 1 x 1; got %d x %d" % (h, w))
+    N, Cc, H, W = img.shape
+    out = torch.empty(N, Cc, h, w, dtype=torch.float32, device=img.device)
+    check(lib().mvs_resize_bicubic_fwd(_base_ptr(img), img.stride(0), img.stride(1), img.stride(2), img.stride(3), ptr(out), N, Cc, H, W, h, w,
+                                       stream_of(img)), "mvs_resize_bicubic_fwd")
+    return out
+
+
+def resize_bilinear_add(base: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
+    """base + F.interpolate(x, base.shape[-2:], mode="bilinear", align_corners=False) (DINOv2_mvsformer_model.py:80-88): base fp32
+    [N, C, h, w], x fp32 [N, C, h', w'] (any strides) -> a fresh contiguous fp32 [N, C, h, w].  (h', w') == (h, w): base + x bit for bit."""
+    _resize_source(base, "base")
+    _resize_source(x, "x")
+    if x.shape[:2] != base.shape[:2] or x.device != base.device:
+        raise ValueError("resize_bilinear_add: base %s on %s and x %s on %s must agree in N, C and device"
+                         % (tuple(base.shape), base.device, tuple(x.shape), x.device))
+    base = base.contiguous()
+    N, Cc, h, w = base.shape
+    out = torch.empty_like(base)
+    check(lib().mvs_resize_bilinear_add_fwd(ptr(base), _base_ptr(x), x.stride(0), x.stride(1), x.stride(2), x.stride(3), ptr(out), N, Cc, h, w,
+                                            x.shape[2], x.shape[3], stream_of(base)), "mvs_resize_bilinear_add_fwd")
+    return out
