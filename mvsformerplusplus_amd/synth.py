@@ -156,8 +156,11 @@ def true_depth(proj_stage: torch.Tensor, H: int, W: int, dmin: float, dmax: floa
 def make_cascade_inputs(H: int, W: int, V: int, *, numdepth: int = 192, depth_min: float = 425.0,
                         depth_interval: float = 2.65, baseline: float = 25.0, rot_deg: float = 0.0,
                         seed: int = 0, batch: int = 1, feat_dtype=torch.float32,
-                        stage_ch: Tuple[int, ...] = STAGE_CH, device=None) -> Tuple[Dict[str, torch.Tensor], Dict[str, torch.Tensor], torch.Tensor]:
+                        stage_ch: Tuple[int, ...] = STAGE_CH, device=None,
+                        cams: Optional[torch.Tensor] = None) -> Tuple[Dict[str, torch.Tensor], Dict[str, torch.Tensor], torch.Tensor]:
     """(features, proj_matrices, depth_values) for a 4-stage cascade at full resolution HxW.
+
+    ``cams``: full-resolution cameras ``[batch, V, 2, 4, 4]`` to use instead of ``make_cameras`` (the default).
 
     ``depth_values`` mirrors ``general_eval.py:223``: arange(dmin, interval*(nd-0.5)+dmin, interval).
     H and W must be divisible by 64 (SURVEY.md §7 "odd sizes").
@@ -166,8 +169,10 @@ def make_cascade_inputs(H: int, W: int, V: int, *, numdepth: int = 192, depth_mi
     dv = torch.arange(depth_min, depth_interval * (numdepth - 0.5) + depth_min, depth_interval, dtype=torch.float32)
     depth_values = dv[None].repeat(batch, 1)
     dmax = float(dv[-1])
-    cams = make_cameras(V, H, W, baseline=baseline, rot_deg=rot_deg, seed=seed, batch=batch)
-    projs = stage_proj_matrices(cams, len(stage_ch))
+    if cams is None:
+        cams = make_cameras(V, H, W, baseline=baseline, rot_deg=rot_deg, seed=seed, batch=batch)
+    assert tuple(cams.shape) == (batch, V, 2, 4, 4), "cams must be [batch, V, 2, 4, 4]"
+    projs = stage_proj_matrices(cams.float().cpu(), len(stage_ch))
     feats = {}
     # keep the surface away from the ends of the hypothesis range
     lo = depth_min + 0.15 * (dmax - depth_min)

@@ -250,9 +250,7 @@ def case_generic_conv_layers(device):
 
 def case_generic_conv_fuzz(device, n_cases=60, seed=0):
     """Seeded random layer shapes through ops.conv3d_generic (both forms, with / without bias, ReLU, skip) against torch's fp32 convolutions:
-    kernel 1..4 per axis, stride 1..3, padding 0..2, output padding < stride, 1..20 channels, ragged sizes.  Runs on the emulator in the CPU
-    suite; it was written after the session's GPU budget was spent, so the -m gpu suite (which must not carry a case that never ran on the
-    MI355X) does not include it yet - `python -c "import parity_cases as P; P.case_generic_conv_fuzz('cuda', 200, 1)"` from tests/ is the GPU run."""
+    kernel 1..4 per axis, stride 1..3, padding 0..2, output padding < stride, 1..20 channels, ragged sizes."""
     import random
     import torch.nn.functional as F
     rnd = random.Random(seed)
@@ -2017,7 +2015,10 @@ def case_fusion_thresholds_exact(device, h=9, w=37):
 # ---------------------------------------------------------------- section 8f #2: backward of the aggregation, training path
 def case_aggregate_backward(device):
     """mvs_warp_corr_aggregate_bwd against torch autograd through the oracle's warp + correlation + aggregation, for C = G
-    (one channel per group), C = 4 G, a border-heavy camera pair (zero-padding taps) and bf16 features."""
+    (one channel per group), C = 4 G, a border-heavy camera pair (zero-padding taps) and bf16 features.  The 4 x zoom row is compared
+    with fp64 autograd through tests/warp_ref.py instead: there the oracle's own fp32 inverse moves the taps, and its bar is
+    max(the 3e-5 of the other rows, 3 x the oracle's own error against fp64), never more than the 1e-3 it had against the oracle."""
+    import warp_ref as R64
     # last case: the source view sees the scene at 4 x the reference's magnification, so the taps of a 16 x 16 tile spread over
     # ~48 x 64 source pixels - more than the LDS window image holds (the tile scatters straight to global memory)
     for C, G, D, H, W, V, dt, zoom in ((8, 8, 4, 12, 20, 3, torch.float32, 1.0), (32, 8, 6, 10, 16, 4, torch.float32, 1.0),
@@ -2041,19 +2042,29 @@ def case_aggregate_backward(device):
             vis_sum = vis_sum + visr[:, v - 1]
         vol = vol_sum / (vis_sum.unsqueeze(1).unsqueeze(1) + 1e-6)
         (vol * gvol).sum().backward()
+        ref_vol, ref_gf, ref_gv = vol.detach(), f32.grad, visr.grad
+        if zoom != 1.0:
+            f64, v64 = feats.detach().double().requires_grad_(True), vis.detach().double().requires_grad_(True)
+            vol64 = R64.aggregate64(f64, cams, hyp, v64, G)[0]
+            (vol64 * gvol.double()).sum().backward()
+            own = max(float((ref_vol - vol64.detach()).abs().max()), 1.5 * float((ref_gf - f64.grad).abs().max()) / float(f64.grad.abs().max()),
+                      1.5 * float((ref_gv - v64.grad).abs().max()) / float(v64.grad.abs().max()))      # the oracle's own distance from fp64
+            ref_vol, ref_gf, ref_gv = vol64.detach().float(), f64.grad.float(), v64.grad.float()
         # HIP
         fd, code = ops._feat(dev(feats, device))
         hom = ops.compose_homography(dev(cams, device))
         vol_cl, _ = ops.warp_corr_aggregate(fd, code, hom, dev(hyp, device), dev(vis, device), G)
-        # tap positions agree with the oracle's to ~1e-4 px; on white-noise features at 4 x magnification (coordinates up to 400 px)
-        # that is worth 5e-4 of the value range, on the other cases 3e-5
-        tol = 3e-5 if zoom == 1.0 else 1e-3
-        assert (cpu(vol_cl).permute(0, 4, 1, 2, 3) - vol.detach()).abs().max() <= tol
+        # 4 x zoom: the oracle's own taps sit ~1e-4 px off fp64's (coordinates up to 400 px), on white-noise features 1.5e-4 of the value range:
+        # measured against fp64 1.1e-4 on the emulator and on the MI355X, bar 4.6e-4
+        tol = 3e-5 if zoom == 1.0 else min(1e-3, max(3e-5, 3 * own))
+        if zoom != 1.0:
+            print("case_aggregate_backward, 4 x zoom: the oracle's own distance from fp64 %.2e, bar %.2e, volume error %.2e" % (own, tol, float((cpu(vol_cl).permute(0, 4, 1, 2, 3) - ref_vol).abs().max())))
+        assert (cpu(vol_cl).permute(0, 4, 1, 2, 3) - ref_vol).abs().max() <= tol
         gfeat, gvis = ops.warp_corr_aggregate_bwd(fd, code, hom, dev(hyp, device), dev(vis, device), dev(vis.sum(1), device), vol_cl,
                                                   dev(gvol.permute(0, 2, 3, 4, 1).contiguous(), device), G)
-        scale_f, scale_v = float(f32.grad.abs().max()), float(visr.grad.abs().max())
-        assert (cpu(gfeat) - f32.grad).abs().max() <= (tol / 1.5) * scale_f + 1e-6, (C, G, "feature gradient")
-        assert (cpu(gvis) - visr.grad).abs().max() <= (tol / 1.5) * scale_v + 1e-6, (C, G, "visibility gradient", float((cpu(gvis) - visr.grad).abs().max()), scale_v)
+        scale_f, scale_v = float(ref_gf.abs().max()), float(ref_gv.abs().max())
+        assert (cpu(gfeat) - ref_gf).abs().max() <= (tol / 1.5) * scale_f + 1e-6, (C, G, "feature gradient")
+        assert (cpu(gvis) - ref_gv).abs().max() <= (tol / 1.5) * scale_v + 1e-6, (C, G, "visibility gradient", float((cpu(gvis) - ref_gv).abs().max()), scale_v)
         assert float(cpu(gfeat)[:, 1:].abs().sum()) > 0 and float(cpu(gfeat)[:, 0].abs().sum()) > 0
 
 
@@ -2503,3 +2514,358 @@ def case_train_backward_transformer_golden(device):
         ref = torch.as_tensor(fx["g." + name], dtype=torch.float32)            # 0-dim parameters (gamma1 / gamma2) come back as scalars
         errs.append(float((cpu(p.grad) - ref).abs().max() / ref.abs().max().clamp_min(1e-12)))
     assert max(errs) <= 3e-2 and sorted(errs)[len(errs) // 2] <= 5e-4, (max(errs), sorted(errs)[len(errs) // 2])
+
+
+# ---------------------------------------------------------------- the warp / gather kernels on non-DTU camera rigs, against fp64
+# tests/rig_cases.py builds the rigs (90 degree roll, convergent views, a source camera inside the hypothesis range, per-view intrinsics,
+# a far world origin, planes ON a source's camera plane, a batch of two different rigs) and tests/warp_ref.py is the fp64 comparator.  One
+# rule for every value comparison:  kernel error <= max(the project's bar for that output, 3 x the fp32 oracle's own error against fp64
+# on the same voxels) - the oracle term is computed here, the factor 3 covers max-statistics noise between two fp32 evaluations.  Only
+# voxels within depth/32 of a source's camera plane (fp64) are left out of value comparisons; every element of every output must be finite.
+def _rig_check(figs, what, got, ref64, orc32, bar, sel=None, info=()):
+    """One comparison under the rule above; `figs` (the calling case's own) collects what -> [kernel error, the oracle's error, error / allowed]."""
+    got = cpu(got).double()
+    assert got.shape == ref64.shape, (what, got.shape, ref64.shape)
+    assert bool(torch.isfinite(got).all()), (what, info, "non-finite output")
+    d, o = (got - ref64).abs(), (orc32.double() - ref64).abs()
+    if sel is not None:
+        sel = sel.expand_as(d)
+        d, o = d[sel], o[sel]
+    err, oerr = (float(d.max()), float(o.max())) if d.numel() else (0.0, 0.0)
+    fig = figs.setdefault(what, [0.0, 0.0, 0.0])
+    fig[0], fig[1], fig[2] = max(fig[0], err), max(fig[1], oerr), max(fig[2], err / max(bar, 3 * oerr))
+    assert err <= max(bar, 3 * oerr), (what, info, "error %.3g > max(bar %.3g, 3 x the oracle's %.3g)" % (err, bar, oerr))
+    return err, oerr
+
+
+def _print_figures(title, figs):
+    print("\n%s: kernel error vs fp64 | the fp32 oracle's error vs fp64 | worst error / allowed" % title)
+    for k in sorted(figs):
+        print("  %-56s %.2e | %.2e | %.2f" % ((k,) + tuple(figs[k])))
+
+
+def _corner_displacement(hom_a, hom_b, H, W, depths):
+    """Max distance in pixels between the projections of the four image corners under two homographies [..., 3, 4] (fp64), at `depths`."""
+    worst = 0.0
+    for x in (0.0, W - 1.0):
+        for y in (0.0, H - 1.0):
+            for d in depths:
+                q = torch.tensor([x, y, 1.0], dtype=torch.float64)
+                pa = hom_a[..., :3, :3] @ q * d + hom_a[..., :3, 3]
+                pb = hom_b[..., :3, :3] @ q * d + hom_b[..., :3, 3]
+                ua, ub = pa[..., :2] / pa[..., 2:3], pb[..., :2] / pb[..., 2:3]
+                worst = max(worst, float((ua - ub).norm(dim=-1).max()))
+    return worst
+
+
+def _hom12(h):
+    """[..., 12] (R row-major, then t) as the kernels write it -> [..., 3, 4] fp64"""
+    h = cpu(h).double()
+    return torch.cat([h[..., :9].reshape(h.shape[:-1] + (3, 3)), h[..., 9:].unsqueeze(-1)], -1)
+
+
+def case_homography_rigs(device):
+    """ops.compose_homography, ops.cascade_prologue (all four stage scalings of the intrinsics) and ops.homography_from_proj on every rig
+    against warp_ref.homography64: the displacement of the four image corners at both ends of the hypothesis range, in pixels.
+    Bar: max(1e-3 px, 3 x the displacement of the reference's own expression, matmul(src, inverse(ref)) in fp32) - for homography_from_proj,
+    which starts from the composed fp32 projections, both the fp64 value and the oracle's start from those as well.
+    Measured, worst displacement in px at stage scale x1 .. x8 (emulator | MI355X, the oracle's next to it; the oracle runs on the host,
+    so its figure depends on the host's LAPACK):
+      near-world rigs   compose / prologue 8.7e-6 .. 7.0e-5 | 1.6e-5 .. 1.3e-4   oracle 1.1e-5 .. 8.6e-5
+                        from_proj 9.3e-6 | 9.3e-6   its oracle 1.1e-5
+      far-world rigs    compose / prologue 7.3e-5 .. 5.8e-4 | 9.4e-5 .. 7.5e-4   oracle 5.0e-4 .. 4.0e-3 | 9.2e-4 .. 7.4e-3
+                        from_proj 2.9e-6 | 2.9e-6   its oracle 4.6e-4 | 8.9e-4
+    (compose / prologue start from [E, K] and multiply K E in fp32 like the reference; that rounding is their distance from fp64.)"""
+    import rig_cases as RC
+    import warp_ref as R64
+    worst = {}
+    for name, spec in RC.RIGS.items():
+        for H, W in ((24, 40), (20, 70)):
+            s = spec.get("s", 1.0)
+            cams = torch.stack([RC.make_rig(e, H, W, s=s, zoom=spec.get("zoom", 2.0), far=spec.get("far", False), n_views=spec.get("n_views"))
+                                for e in spec["elems"]])
+            depths = (430.0 * s, 930.0 * s)
+            stages = []
+            for k in range(4):
+                p = cams.clone()
+                p[:, :, 1, :2, :] *= 2.0 ** k
+                stages.append(p)
+            homs, _ = ops.cascade_prologue([dev(p, device) for p in stages])
+            for k, p in enumerate(stages):
+                ref = R64.homography64(p)[..., :3, :]
+                P = O.compose_proj(p.reshape(-1, 2, 4, 4)).reshape(p.shape[:2] + (4, 4))
+                orc = torch.matmul(P[:, 1:], torch.inverse(P[:, :1]))[..., :3, :].double()
+                Hk, Wk = H * 2 ** k, W * 2 ** k
+                oerr = _corner_displacement(orc, ref, Hk, Wk, depths)
+                got = {"cascade_prologue": _hom12(homs[k])}
+                if k == 0:
+                    got["compose_homography"] = _hom12(ops.compose_homography(dev(p, device)))
+                    B, V = p.shape[:2]
+                    src_p = P[:, 1:].reshape(-1, 4, 4).contiguous()
+                    ref_p = P[:, :1].expand(B, V - 1, 4, 4).reshape(-1, 4, 4).contiguous()
+                    fp = _hom12(ops.homography_from_proj(dev(src_p, device), dev(ref_p, device))).reshape(B, V - 1, 3, 4)
+                    # this entry point starts from the COMPOSED fp32 projections: its fp64 value is the inverse of those
+                    ref_fp = R64.homography64_from_proj(src_p, ref_p)[..., :3, :].reshape(B, V - 1, 3, 4)
+                    orc_fp = torch.matmul(src_p, torch.inverse(ref_p))[..., :3, :].reshape(B, V - 1, 3, 4).double()
+                    oerr_fp = _corner_displacement(orc_fp, ref_fp, Hk, Wk, depths)       # the oracle from the same composed projections
+                    e = _corner_displacement(fp, ref_fp, Hk, Wk, depths)
+                    assert e <= max(1e-3, 3 * oerr_fp), (name, "homography_from_proj", e, oerr_fp)
+                    worst[("oracle from_proj", bool(spec.get("far")))] = max(worst.get(("oracle from_proj", bool(spec.get("far"))), 0.0), oerr_fp)
+                    worst[("from_proj", bool(spec.get("far")))] = max(worst.get(("from_proj", bool(spec.get("far"))), 0.0), e)
+                for what, h in got.items():
+                    assert bool(torch.isfinite(h).all())
+                    e = _corner_displacement(h, ref, Hk, Wk, depths)
+                    assert e <= max(1e-3, 3 * oerr), (name, what, k, "corner displacement %.3g px, the oracle's %.3g px" % (e, oerr))
+                    key = (what + (" x%d" % 2 ** k), bool(spec.get("far")))
+                    worst[key] = max(worst.get(key, 0.0), e)
+                    worst[("oracle x%d" % 2 ** k, bool(spec.get("far")))] = max(worst.get(("oracle x%d" % 2 ** k, bool(spec.get("far"))), 0.0), oerr)
+    print("\ncase_homography_rigs: worst corner displacement in px, (entry point, far-world rig)")
+    for k in sorted(worst):
+        print("  %-32s %.2e" % (k, worst[k]))
+
+
+def case_warp_rigs(device, name, shape):
+    """homo_warping_3D_with_mask (the plain homo_warp op) on one rig, fp32 and bf16 source features, against warp_ref.warp64.
+    Features: the comparison rule above with the project's 2e-4 (case_warp_golden) as the bar.  The mask may differ from fp64 only where
+    the fp64 |xn| or |yn| is within 1e-4 of 1 or |pz| <= 1e-4 depth; that borderline set holds at most 1 % of the voxels (asserted from
+    fp64; its measure is of order 1e-4).  On the singular rig the features are exactly 0 wherever the fp64 coordinate is beyond 1e4 px.
+    Measured over the 30 cases, max abs error of the warped features vs fp64 (emulator | MI355X, then the oracle's own):
+      near-world rigs 2.4e-4 | 2.1e-4, oracle 1.8e-4 (all three at 16 x 192, where a x 2.1 source coordinate reaches 400 px; 5.4e-5 | 4.8e-5,
+      oracle 9.9e-5 on the smaller shapes);   far-world rigs 5.1e-4 | 4.9e-4, oracle 3.0e-3 | 3.7e-3 (its fp32 inverse)
+    worst error / allowed 0.50 | 0.43; no mask difference outside the borderline set, whose largest share is 5.8e-4."""
+    import rig_cases as RC
+    import warp_ref as R64
+    r = RC.reference(name, shape)
+    cams, hyp, feats = r["cams"], r["hyp"], r["feats"]
+    B, V, C, H, W = feats.shape
+    singular = bool(RC.RIGS[name].get("singular"))
+    ref_p = O.compose_proj(cams[:, 0])
+    figs, worst_share = {}, 0.0
+    for v in range(1, V):
+        w64 = r["warp"][v - 1]
+        src_p = O.compose_proj(cams[:, v])
+        xn, yn = w64["ix"] / (W - 1) * 2 - 1, w64["iy"] / (H - 1) * 2 - 1
+        border = ((xn.abs() - 1).abs() <= 1e-4) | ((yn.abs() - 1).abs() <= 1e-4) | (w64["pz"].abs() <= 1e-4 * hyp.double())
+        counted = border.clone()
+        if singular:
+            counted[:, 3:5] = False                    # the planted planes lie ON the camera plane: borderline by construction
+        share = float(counted.double().mean())
+        assert share <= 0.01, (name, v, "borderline share", share)
+        worst_share = max(worst_share, share)
+        for dt in (torch.float32, torch.bfloat16):
+            src = feats[:, v].to(dt)
+            if dt == torch.float32:
+                ref, orc = w64["warped"], r["warp32"][v - 1][0]
+            else:
+                ref = R64.warp64_hom(src.float(), r["hom64"][:, v - 1], hyp)[0]
+                orc = O.homo_warping_3D_with_mask(src.float(), src_p, ref_p, hyp)[0]
+            w, m = homo_warping_3D_with_mask(dev(src, device), dev(src_p, device), dev(ref_p, device), dev(hyp, device))
+            m = cpu(m)
+            assert not bool(((m != w64["mask"]) & ~border).any()), (name, v, dt, "mask differs from fp64 away from the frame border / camera plane")
+            _rig_check(figs, "warp: features", w, ref, orc, 2e-4, r["inc"][:, v - 1].unsqueeze(1), (name, shape, v, dt))
+            if singular:
+                far = r["far_px"][:, v - 1].unsqueeze(1).expand_as(ref)
+                assert far[:, :, 3].all() == (v == 1), "the planted plane lies on source 1's camera plane: beyond 1e4 px everywhere"
+                assert not far.any() or float(cpu(w)[far].abs().max()) == 0.0, (name, v, "features on the singular planes")
+    _print_figures("case_warp_rigs %s %s (borderline share %.2e)" % (name, shape, worst_share), figs)
+
+
+def _cl(vol):
+    """channel-last [B,D,H,W,G] -> [B,G,D,H,W] on the CPU"""
+    return cpu(vol).float().permute(0, 4, 1, 2, 3)
+
+
+def _gather_rig_outputs(device, feats, cams, hyp, vis, lds):
+    """Every gather pass of one (features, rig) call -> dict of CPU tensors (volumes / correlations as [B,(V-1,)G,D,H,W])."""
+    Gr, hd, vd = 8, dev(hyp, device), dev(vis, device)
+    D = hyp.shape[1]
+    f, code = ops._feat(dev(feats, device))
+    hom = ops.compose_homography(dev(cams, device))
+    out = {"ent": cpu(ops.warp_corr_entropy(f, code, hom, hd, Gr)), "vol": _cl(ops.warp_corr_aggregate(f, code, hom, hd, vd, Gr)[0])}
+    if not lds:
+        return out
+    out["ent_w16"] = cpu(ops.warp_corr_entropy(f, code, hom, hd, Gr, f16_window=True))
+    out["vol_f16"] = _cl(ops.warp_corr_aggregate(f, code, hom, hd, vd, Gr, f16=True)[0])
+    ent_k, corr = ops.warp_corr_entropy_keep(f, code, hom, hd, Gr)
+    out["ent_keep"], out["corr_keep"] = cpu(ent_k), cpu(corr).float().permute(0, 1, 5, 2, 3, 4)
+    out["agg_f16"] = _cl(ops.corr_aggregate(corr, vd))
+    out["agg_f32"] = _cl(ops.corr_aggregate(corr, vd, f16=False))
+    out["agg_split"] = _cl(ops.from_split(ops.corr_aggregate(corr, vd, split=True)))
+    if D > 4:
+        ent_x, corr_x = ops.warp_corr_entropy_keep(f, code, hom, hd, Gr, exact=True)
+        out["ent_exact"], out["corr_exact"] = cpu(ent_x), cpu(corr_x).permute(0, 1, 5, 2, 3, 4)
+        out["agg_exact"] = _cl(ops.corr_aggregate(corr_x, vd, f16=False))
+        out["agg_exact_split"] = _cl(ops.from_split(ops.corr_aggregate(corr_x, vd, split=True)))
+    return out
+
+
+def case_gather_rigs(device, name, shape):
+    """Every gather pass on one (rig, shape) of rig_cases.GATHER_CASES against fp64: warp_corr_entropy (plain and f16_window), warp_corr_aggregate
+    (fp32 and f16), warp_corr_entropy_keep (fp16 and, D > 4, exact), corr_aggregate (f16 / split / fp32) and the octet-tiled fp32 and fp16
+    hand-offs of pack_features - where the shape takes the LDS-staged kernels (W % 8 == 0); the direct-gather kernels otherwise (plain passes).
+    Bars (the project's, or 3 x the oracle's own error): entropy 5e-5; volume and correlations 5e-5 max(1, max|ref|); kept fp16 correlations
+    6e-4 max(1, max|ref|); streamed / gathered fp16 volume 1.2e-3 scale, its fp32 and split forms 6e-4 scale.  The relations of case_gather_variants
+    hold here too (tiled == planar, fp16 tiles == planar fp16 bit for bit, exact streamed == second gather, per-view partial sums == fused),
+    each element of the mixed batch equals its own B = 1 run bit for bit, and on the singular rig the kept correlations are exactly 0
+    wherever the fp64 coordinate is beyond 1e4 px.  A volume voxel is compared where every view's sample is, an entropy pixel where every
+    plane of that view is: none for source 1 of the forward rigs from D = 16 on, where a whole plane hugs its camera plane, so up to D = 8
+    at least a quarter of every view's pixels must be (asserted), which keeps the entropy of the behind-the-camera view value-checked at
+    (16, 8, 24, 40), (32, 8, 12, 32) and, on the direct-gather kernels, (16, 8, 12, 36).
+    zoom1.9 / zoom2.1 run at (8, 4, 12, 160) and (16, 8, 16, 192), where one tile's fp32 window of source 1 fits GL_CAP at 1.9 and exceeds
+    it at 2.1 (rig_cases.rig_conditions asserts it from fp64): both the staged gather and gl_unit's gather from global memory are compared.
+    Measured over the 30 cases, max abs error vs fp64: kernel (emulator | MI355X), then the fp32 oracle's own on the same voxels:
+      near-world rigs   entropy 1.4e-4 | 1.9e-4, oracle 1.1e-4        volume 1.4e-4 | 1.6e-4, oracle 1.8e-4
+                        exact kept correlations 1.9e-4 | 2.3e-4, oracle 1.7e-4     exact streamed volume 1.1e-4 | 1.6e-4, oracle 1.4e-4
+                        kept fp16 correlations 1.9e-3 | 1.9e-3 (one fp16 rounding of values up to 5), oracle 2.6e-4
+                        streamed fp16 volume 2.5e-3 | 2.5e-3, as fp32 / split 1.5e-3 | 1.5e-3       gathered fp16 volume 1.7e-3 | 1.7e-3
+                        (the largest fp32 figures are those of the 192 pixel wide zoom shapes; without them: entropy 4.0e-5 | 8.0e-5, oracle
+                        5.9e-5, volume 5.8e-5 | 8.7e-5, oracle 9.6e-5)
+      far-world rigs    entropy 3.3e-4 | 3.3e-4, oracle 1.7e-3 | 2.3e-3 volume 3.3e-4 | 3.2e-4, oracle 1.8e-3 | 2.2e-3
+                        exact kept correlations 4.7e-4 | 4.5e-4, oracle 2.6e-3 | 2.1e-3  kept fp16 correlations 1.7e-3 | 1.7e-3
+    (the oracle runs on the host: its far-world figures depend on the host's LAPACK inverse).  Worst error / allowed over every comparison
+    0.74 | 0.74 (kept fp16 correlations); fp32 outputs: 0.44 | 0.56.  On the far-world rigs the kernels are 5 x closer to fp64 than the oracle."""
+    import rig_cases as RC
+    import warp_ref as R64
+    r = RC.reference(name, shape)
+    cams, hyp, feats, vis = r["cams"], r["hyp"], r["feats"], r["vis"]
+    B, V, C, H, W = feats.shape
+    D = hyp.shape[1]
+    info, figs = (name, shape), {}
+    f_dev, hd, vd, hom = dev(feats, device), dev(hyp, device), dev(vis, device), ops.compose_homography(dev(cams, device))
+    lds = ops.gather_keeps_correlations(f_dev, 8, hd)
+    assert lds == (W % 8 == 0), (info, "which kernels take this shape")
+    got = _gather_rig_outputs(device, feats, cams, hyp, vis, lds)
+    inc = r["inc"]                                        # [B,V-1,D,H,W]
+    inc_all = inc.all(1)[:, None]                         # volume voxels: every view's sample is comparable
+    inc_px = inc.all(2)                                   # entropy pixels [B,V-1,H,W]: every plane is comparable
+    if D <= 8 and not RC.RIGS[name].get("singular"):      # up to D = 8 every view's entropy is value-checked on a quarter of its pixels
+        assert float(inc_px.double().mean((0, 2, 3)).min()) >= 0.25, (info, "entropy pixels compared per view", inc_px.double().mean((0, 2, 3)))
+    vscale = max(1.0, float(r["vol64"].abs().max()))
+    cscale = max(1.0, float(r["corr64"].abs().max()))
+    inc_c = inc[:, :, None]
+    _rig_check(figs, "gather: entropy", got["ent"], r["ent64"], r["ent32"], 5e-5, inc_px, info)
+    _rig_check(figs, "gather: volume", got["vol"], r["vol64"], r["vol32"], 5e-5 * vscale, inc_all, info)
+    if lds:
+        _rig_check(figs, "gather: entropy, fp16 window", got["ent_w16"], r["ent64_16"], r["ent32_16"], 5e-5, inc_px, info)
+        _rig_check(figs, "gather: entropy, keeping pass", got["ent_keep"], r["ent64_16"], r["ent32_16"], 5e-5, inc_px, info)
+        _rig_check(figs, "gather: kept fp16 correlations", got["corr_keep"], r["corr64_16"], r["corr32_16"], 6e-4 * cscale, inc_c, info)
+        _rig_check(figs, "gather: fp16 volume", got["vol_f16"], r["vol64_16"], r["vol32_16"], 1.2e-3 * vscale, inc_all, info)
+        _rig_check(figs, "gather: streamed fp16 volume", got["agg_f16"], r["vol64_16"], r["vol32_16"], 1.2e-3 * vscale, inc_all, info)
+        _rig_check(figs, "gather: streamed volume, fp32 out", got["agg_f32"], r["vol64_16"], r["vol32_16"], 6e-4 * vscale, inc_all, info)
+        _rig_check(figs, "gather: streamed volume, split out", got["agg_split"], r["vol64_16"], r["vol32_16"], 6e-4 * vscale, inc_all, info)
+        if D > 4:
+            _rig_check(figs, "gather: entropy, exact keeping pass", got["ent_exact"], r["ent64"], r["ent32"], 5e-5, inc_px, info)
+            _rig_check(figs, "gather: exact kept correlations", got["corr_exact"], r["corr64"], r["corr32"], 5e-5 * cscale, inc_c, info)
+            _rig_check(figs, "gather: exact streamed volume", got["agg_exact"], r["vol64"], r["vol32"], 5e-5 * vscale, inc_all, info)
+            _rig_check(figs, "gather: exact streamed volume, split", got["agg_exact_split"], r["vol64"], r["vol32"], 5e-5 * vscale, inc_all, info)
+            assert (got["agg_exact"] - got["vol"]).abs().max() <= 4e-6 * vscale, (info, "exact streamed volume == second gather")
+        if RC.RIGS[name].get("singular"):
+            far = r["far_px"][:, :, None].expand_as(got["corr_keep"])
+            assert far[:, 0, :, 3].all(), "the planted plane projects beyond 1e4 px everywhere"
+            assert float(got["corr_keep"][far].abs().max()) == 0.0 and float(got["corr_exact"][far].abs().max()) == 0.0, (info, "kept correlations on the singular planes")
+        # the octet-tiled hand-offs: fp32 tiles give the planar numbers, fp16 tiles the bits of planar fp16 features
+        pk = ops.pack_features(f_dev)
+        assert torch.equal(cpu(pk.unpack()), feats), "pack_features must be a pure re-layout"
+        ent_t = cpu(ops.warp_corr_entropy(pk, ops._feat(pk)[1], hom, hd, 8))
+        vol_t = _cl(ops.warp_corr_aggregate(pk, ops._feat(pk)[1], hom, hd, vd, 8)[0])
+        _rig_check(figs, "gather: entropy, fp32 tiles", ent_t, r["ent64"], r["ent32"], 5e-5, inc_px, info)
+        _rig_check(figs, "gather: volume, fp32 tiles", vol_t, r["vol64"], r["vol32"], 5e-5 * vscale, inc_all, info)
+        assert (ent_t - got["ent"]).abs().max() <= 1e-6 and (vol_t - got["vol"]).abs().max() <= 1e-6 * vscale, (info, "tiled == planar")
+        fh = dev(feats.half(), device)
+        ft16 = ops.pack_features(fh)
+        assert ft16.dtype == torch.float16
+        e_p, c_p = ops.warp_corr_entropy_keep(fh, ops._feat(fh)[1], hom, hd, 8)
+        e_t, c_t = ops.warp_corr_entropy_keep(ft16, ops._feat(ft16)[1], hom, hd, 8)
+        assert torch.equal(cpu(e_p), cpu(e_t)) and torch.equal(cpu(c_p), cpu(c_t)), (info, "fp16 tiles == planar fp16: keeping pass")
+        v_p = ops.warp_corr_aggregate(fh, ops._feat(fh)[1], hom, hd, vd, 8, f16=True)[0]
+        v_t = ops.warp_corr_aggregate(ft16, ops._feat(ft16)[1], hom, hd, vd, 8, f16=True)[0]
+        assert torch.equal(cpu(v_p), cpu(v_t)), (info, "fp16 tiles == planar fp16: pass 2")
+        w_p = ops.warp_corr_entropy(fh, ops._feat(fh)[1], hom, hd, 8, f16_window=True)
+        w_t = ops.warp_corr_entropy(ft16, ops._feat(ft16)[1], hom, hd, 8, f16_window=True)
+        assert torch.equal(cpu(w_p), cpu(w_t)), (info, "fp16 tiles == planar fp16: plain pass 1")
+        # fp16 tiles against fp64: here the reference view's features are fp16-rounded as well
+        f16 = feats.half().float()
+        _, corr64_h, ent64_h = R64.aggregate64(f16, cams, hyp, vis, 8)
+        _, corr32_h, ent32_h, _ = RC.oracle32(f16, cams, hyp, vis)
+        _rig_check(figs, "gather: entropy, fp16 tiles", e_t, ent64_h, ent32_h, 5e-5, inc_px, info)
+        _rig_check(figs, "gather: kept correlations, fp16 tiles", cpu(c_t).float().permute(0, 1, 5, 2, 3, 4), corr64_h, corr32_h, 6e-4 * cscale, inc_c, info)
+    # per-view partial sums == the fused form
+    f, code = ops._feat(f_dev)
+    parts = [ops.warp_corr_aggregate(f, code, hom, hd, vd, 8, normalise=False, view_begin=v, view_end=v + 1) for v in range(1, V)]
+    both = ops.volume_normalise_(sum(p[0] for p in parts), sum(p[1] for p in parts))
+    assert (_cl(both) - got["vol"]).abs().max() <= 2e-6 * vscale, (info, "partial sums")
+    if B > 1:       # a batch of different rigs: every element equals its own B = 1 run, bit for bit
+        for b in range(B):
+            one = _gather_rig_outputs(device, feats[b:b + 1], cams[b:b + 1], hyp[b:b + 1], vis[b:b + 1], lds)
+            for k in got:
+                assert torch.equal(one[k][0], got[k][b]), (info, "batch element %d differs from its own B = 1 run" % b, k)
+    _print_figures("case_gather_rigs %s %s" % info, figs)
+
+
+def case_aggregate_backward_rigs(device, name, shape):
+    """mvs_warp_corr_aggregate_bwd on roll90 / convergent / zoom (factor 2) / forward against fp64 autograd through warp_ref, at (8, 4, 12, 20)
+    and (32, 6, 10, 16).  Bar: 3e-5 of the gradient's max, or 3 x the error of fp32 autograd through the oracle.  Voxels within depth/32 of
+    a source's camera plane get a zero upstream gradient (a feature gradient sums over voxels, so they cannot be left out afterwards).  At
+    D = 4 the forward rig's source 1 sits at z = 680 instead of 600: at 600 one whole plane of the four lies within depth/32 of its camera
+    plane, which is more than the 10 % the excluded set may hold; two of the four planes are still behind that camera, and the rig
+    conditions are asserted at these shapes too: 25 % of the voxels behind source 1, 0.5 % behind it AND inside its image, the latter also
+    counted among the voxels with a non-zero upstream gradient.
+    Measured over the 8 cases, relative to the gradient's max (emulator | MI355X, then fp32 autograd through the oracle): feature gradient
+    3.0e-6 | 3.0e-6, oracle 2.9e-6; visibility gradient 7.2e-6 | 6.1e-6, oracle 4.2e-6; worst error / allowed 0.24 | 0.20."""
+    import rig_cases as RC
+    import warp_ref as R64
+    C, D, H, W = shape
+    g = torch.Generator().manual_seed(C + D + len(name))
+    zc = 680.0 if (name == "forward" and D == 4) else 600.0
+    cams = RC.make_rig(name, H, W, forward_z=zc)[None]
+    V = cams.shape[1]
+    hyp = RC.make_hyp(D, H, W, 1.0, g)
+    feats = torch.randn(1, V, C, H, W, generator=g)
+    vis = torch.rand(1, V - 1, H, W, generator=g) * 0.9 + 0.05
+    hom64 = R64.homography64(cams)
+    excl = torch.stack([hyp.double() > 32 * R64.project64(hom64[:, v], hyp, H, W)[2].abs() for v in range(V - 1)], 1)
+    for v in range(V - 1):
+        share = float(excl[:, v].double().mean())
+        assert share <= 0.10 and (name == "forward" or share == 0.0), (name, shape, v, "excluded share", share)
+    if name == "forward":      # the conditions of rig_cases.rig_conditions at this shape: the mirrored taps do reach the gradients
+        xn, yn, pz = R64.project64(hom64[:, 0], hyp, H, W)
+        ix, iy = (xn + 1) / 2 * (W - 1), (yn + 1) / 2 * (H - 1)
+        inside = (ix > -1) & (ix < W) & (iy > -1) & (iy < H)
+        assert float((pz <= 0).double().mean()) >= 0.25, "planes behind source 1"
+        assert float(((pz <= 0) & inside).double().mean()) >= 0.005, ("behind source 1 AND inside its image", float(((pz <= 0) & inside).double().mean()))
+        assert float(((pz <= 0) & inside & ~excl[:, 0]).double().mean()) >= 0.005, "... with a non-zero upstream gradient"
+    gvol = torch.randn(1, 8, D, H, W, generator=g) * (~excl.any(1))[:, None]
+    # fp64 autograd through the restatement, and fp32 autograd through the oracle for the bar
+    f64, v64 = feats.double().requires_grad_(True), vis.double().requires_grad_(True)
+    vol64 = R64.aggregate64(f64, cams, hyp, v64, 8)[0]
+    (vol64 * gvol.double()).sum().backward()
+    f32, v32 = feats.clone().requires_grad_(True), vis.clone().requires_grad_(True)
+    ref_p, vol_sum, vis_sum = O.compose_proj(cams[:, 0]), 0.0, 0.0
+    for v in range(1, V):
+        warped, _ = O.homo_warping_3D_with_mask(f32[:, v], O.compose_proj(cams[:, v]), ref_p, hyp)
+        vol_sum = vol_sum + O.group_correlation(f32[:, 0], warped, 8) * v32[:, v - 1].unsqueeze(1).unsqueeze(1)
+        vis_sum = vis_sum + v32[:, v - 1]
+    (vol_sum / (vis_sum.unsqueeze(1).unsqueeze(1) + 1e-6) * gvol).sum().backward()
+    fd, code = ops._feat(dev(feats, device))
+    hom = ops.compose_homography(dev(cams, device))
+    vol_cl, _ = ops.warp_corr_aggregate(fd, code, hom, dev(hyp, device), dev(vis, device), 8)
+    gfeat, gvis = ops.warp_corr_aggregate_bwd(fd, code, hom, dev(hyp, device), dev(vis, device), dev(vis.sum(1), device), vol_cl,
+                                              dev(gvol.permute(0, 2, 3, 4, 1).contiguous(), device), 8)
+    sf, sv = float(f64.grad.abs().max()), float(v64.grad.abs().max())
+    figs = {}
+    _rig_check(figs, "backward: feature gradient / max", cpu(gfeat) / sf, f64.grad / sf, f32.grad / sf, 3e-5, None, (name, shape))
+    _rig_check(figs, "backward: visibility gradient / max", cpu(gvis) / sv, v64.grad / sv, v32.grad / sv, 3e-5, None, (name, shape))
+    assert float(cpu(gfeat)[:, 1:].abs().sum()) > 0 and float(cpu(gfeat)[:, 0].abs().sum()) > 0
+    _print_figures("case_aggregate_backward_rigs %s %s" % (name, shape), figs)
+
+
+def case_cascade_rigs(device, name, conv_precision=None):
+    """A whole CascadeDepthHead at 64 x 128, V = 3, on a near-world rig against O.cascade_forward (the fp32 oracle is the comparator here,
+    so the far-world rigs do not qualify): the bars of case_cascade_vs_oracle - 1e-3 depth rel-L1 per stage and refined, the same
+    confidence bar - with the fp16-tile hand-off leg in the default precision.
+    Measured refined-depth rel-L1 (emulator | MI355X): default precision convergent 3.7e-5 | 3.5e-5, roll90 3.6e-5 | 3.7e-5, zoom 4.1e-5 | 3.9e-5;
+    bf16x3 6.0e-7 .. 8.9e-7 | 5.4e-7 .. 9.8e-7."""
+    import rig_cases as RC
+    r = case_cascade_vs_oracle(device, 64, 128, 3, conv_precision=conv_precision, cams=RC.make_rig(name, 64, 128)[None])
+    print("\ncase_cascade_rigs %s %s: refined depth rel-L1 vs the oracle %.2e" % (name, eff(conv_precision), r))
+    return r

@@ -4,6 +4,7 @@ numbers that count are produced by tests/test_gpu_parity.py on the MI355X."""
 import pytest
 
 import parity_cases as P
+import rig_cases as RC
 from conftest import PRECS, PRECS_ALL          # [None = the product default (the "stagemix" policy), "bf16x3" = the fp32-equivalent mode]
 
 
@@ -260,3 +261,29 @@ def test_fusion_view_limits(emu):
 
 def test_fusion_thresholds_exact(emu):
     P.case_fusion_thresholds_exact(emu)
+
+
+# ---- the warp / gather kernels on non-DTU camera rigs against the fp64 restatement (tests/warp_ref.py, tests/rig_cases.py) ----
+def test_homography_rigs(emu):
+    P.case_homography_rigs(emu)
+
+
+@pytest.mark.parametrize("name,shape", RC.GATHER_CASES, ids=RC.GATHER_IDS)
+def test_warp_rigs(emu, name, shape):
+    P.case_warp_rigs(emu, name, shape)
+
+
+@pytest.mark.parametrize("name,shape", RC.GATHER_CASES, ids=RC.GATHER_IDS)
+def test_gather_rigs(emu, name, shape):
+    P.case_gather_rigs(emu, name, shape)
+
+
+@pytest.mark.parametrize("name,shape", RC.BACKWARD_CASES, ids=RC.BACKWARD_IDS)
+def test_aggregate_backward_rigs(emu, name, shape):
+    P.case_aggregate_backward_rigs(emu, name, shape)
+
+
+@pytest.mark.parametrize("prec", PRECS)
+@pytest.mark.parametrize("name", ["convergent", "roll90", "zoom"])
+def test_cascade_rigs(emu, name, prec):
+    P.case_cascade_rigs(emu, name, prec)

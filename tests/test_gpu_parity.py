@@ -5,6 +5,7 @@ import pytest
 import torch
 
 import parity_cases as P
+import rig_cases as RC
 from conftest import PRECS, PRECS_ALL, rel_l1      # PRECS = [None (the product default: the "stagemix" policy), "bf16x3" (the fp32-equivalent mode)]
 
 pytestmark = pytest.mark.gpu
@@ -374,3 +375,33 @@ def test_device_packing():
 
 def test_train_fp32_configured_head():
     P.case_train_fp32_configured_head(DEV)
+
+
+def test_generic_conv_fuzz():
+    P.case_generic_conv_fuzz(DEV, n_cases=60, seed=0)
+
+
+# ---- the warp / gather kernels on non-DTU camera rigs against the fp64 restatement (tests/warp_ref.py, tests/rig_cases.py) ----
+def test_homography_rigs():
+    P.case_homography_rigs(DEV)
+
+
+@pytest.mark.parametrize("name,shape", RC.GATHER_CASES, ids=RC.GATHER_IDS)
+def test_warp_rigs(name, shape):
+    P.case_warp_rigs(DEV, name, shape)
+
+
+@pytest.mark.parametrize("name,shape", RC.GATHER_CASES, ids=RC.GATHER_IDS)
+def test_gather_rigs(name, shape):
+    P.case_gather_rigs(DEV, name, shape)
+
+
+@pytest.mark.parametrize("name,shape", RC.BACKWARD_CASES, ids=RC.BACKWARD_IDS)
+def test_aggregate_backward_rigs(name, shape):
+    P.case_aggregate_backward_rigs(DEV, name, shape)
+
+
+@pytest.mark.parametrize("prec", PRECS)
+@pytest.mark.parametrize("name", ["convergent", "roll90", "zoom"])
+def test_cascade_rigs(name, prec):
+    P.case_cascade_rigs(DEV, name, prec)
