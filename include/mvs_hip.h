@@ -662,6 +662,22 @@ int mvs_resize_bicubic_fwd(const float* img, long long batch_stride, long long c
 int mvs_resize_bilinear_add_fwd(const float* base, const float* x, long long batch_stride, long long channel_stride, long long row_stride,
                                 long long col_stride, float* out, int N, int C, int h, int w, int xh, int xw, void* stream);
 
+/* ==== a scene's depth inference: the two ends of the per-view loop (general_eval.py:112-131, test.py:266-294) ====
+ * mvs_image_prepare_fwd: src uint8 RGB [h,w,3] (decoded image) -> planar fp32 [3,H,W] = table[c][resized] AND resized uint8 [H,W,3], where
+ *   resized is the 8-bit linear resize of the source with pad_rows replicated rows above and below it (the "tt" edge pad, addressed and never
+ *   materialised) to H x W in OpenCV's fixed-point arithmetic: per axis f = (float)((d + 0.5) * (in / out) - 0.5), s = floor(f), f -= s,
+ *   clamped to [0, in - 1] with f = 0 at both ends, coefficients short(rint((1 - f) * 2048)) and short(rint(f * 2048)), horizontal
+ *   S[s] * a0 + S[s + 1] * a1, vertical (((b0 * (r0 >> 4)) >> 16) + ((b1 * (r1 >> 4)) >> 16) + 2) >> 2; equal sizes give the identity.
+ *   table fp32 [3,256]: the caller's ((u / 255) - mean[c]) / std[c] (ToTensor + Normalize).  planar and resized are plain pointers: a slot of
+ *   a larger buffer is fine.  Sizes <= 32768, 0 <= pad_rows <= 64.
+ * mvs_depth_outputs_pack_fwd: depth, conf (and reg_conf, or NULL) fp32 [H,W] -> staging, 5 H W bytes, 4-byte aligned: fp32 [H,W] the depth
+ *   rows bottom-up (a PFM body), then uint8 [H,W] = uint8(c * 255) truncated and clamped to 0..255 with c = conf, or (conf * 3 + reg_conf) / 4
+ *   as three separately rounded fp32 operations when reg_conf is given.
+ * One launch each, no workspace.                                                                                     */
+int mvs_image_prepare_fwd(const unsigned char* src, int h, int w, int pad_rows, const float* table, float* planar, unsigned char* resized,
+                          int H, int W, void* stream);
+int mvs_depth_outputs_pack_fwd(const float* depth, const float* conf, const float* reg_conf, void* staging, int H, int W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -151,6 +151,8 @@ SIGNATURES = {
     "mvs_cl_to_ncdhw": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "mvs_resize_bicubic_fwd": (_i, [_vp] + [C.c_longlong] * 4 + [_vp] + [_i] * 6 + [_vp]),
     "mvs_resize_bilinear_add_fwd": (_i, [_vp, _vp] + [C.c_longlong] * 4 + [_vp] + [_i] * 6 + [_vp]),
+    "mvs_image_prepare_fwd": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp]),
+    "mvs_depth_outputs_pack_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp]),
 }
 
 

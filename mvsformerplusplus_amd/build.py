@@ -30,7 +30,10 @@ FILE_FLAGS = {"transformer_kernels.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1", 
               "vis_kernels.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1", "-fno-honor-nans"],
               # vit_attention_kernels: the score accumulators go straight into the softmax and come back as the next product's operand, the
               # output accumulators are rescaled by VALU code every key step; masked scores are -inf and a step's max is finite
-              "vit_attention_kernels.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1", "-fno-honor-nans"]}
+              "vit_attention_kernels.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1", "-fno-honor-nans"],
+              # scene_kernels: restates host arithmetic bit for bit ((d + 0.5) * scale - 0.5 in double, (pc * 3 + reg) / 4 in float): every
+              # operation rounds on its own, no fused multiply-add
+              "scene_kernels.hip": ["-ffp-contract=off"]}
 
 
 def _digest():

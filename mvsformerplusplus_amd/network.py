@@ -103,16 +103,41 @@ class DINOv2MVSNet(CascadeDepthHead):
             raise ValueError("%d x %d images at rescale %g leave the ViT less than one 14 x 14 patch (%d x %d)" % (H, W, self.rescale, vit_h, vit_w))
         return V, H, W, vit_h, vit_w
 
-    def feature_maps(self, imgs: torch.Tensor, capture: Optional[dict] = None) -> Dict[str, torch.Tensor]:
+    def vit_levels(self, views: torch.Tensor):
+        """views fp32 [N, 3, H, W] (the network's normalised images) -> the ViT's interval levels, a list of OWNED fp32 [N, n, 768] tensors (the
+        bicubic resize to ``vit_size`` and ``forward_interval_features``, copied out of the ViT's padded buffers).  A view's levels do not
+        depend on which views share the call (tests/test_scene.py proves it bit for bit), so a scene driver computes them once per image
+        and hands them back through ``forward(..., vit_levels=...)`` for every sample the image takes part in."""
+        if not torch.is_tensor(views) or views.dim() != 4:
+            raise ValueError("vit_levels takes views [N, 3, H, W]; got %s" % (tuple(views.shape) if torch.is_tensor(views) else type(views),))
+        _, H, W, vit_h, vit_w = self._check(views.unsqueeze(0))
+        with torch.no_grad():
+            vit_imgs = ops.resize_bicubic(views if views.dtype == torch.float32 else views.float(), vit_h, vit_w)
+            return [t.clone(memory_format=torch.contiguous_format) for t in self.vit.forward_interval_features(vit_imgs)]
+
+    def _check_levels(self, vit_levels, imgs, V, vit_h, vit_w):
+        n = (vit_h // PATCH) * (vit_w // PATCH)
+        levels = list(vit_levels)
+        for t in levels:
+            if not torch.is_tensor(t) or t.dtype != torch.float32 or tuple(t.shape) != (1, V, n, self.vit.embed_dim) or t.device != imgs.device:
+                raise ValueError("vit_levels must be the ViT's interval levels of these views, fp32 [1, %d, %d, %d] on %s each; got %s"
+                                 % (V, n, self.vit.embed_dim, imgs.device, (t.dtype, tuple(t.shape), t.device) if torch.is_tensor(t) else type(t)))
+        return levels
+
+    def feature_maps(self, imgs: torch.Tensor, capture: Optional[dict] = None, vit_levels=None) -> Dict[str, torch.Tensor]:
         """imgs [1, V, 3, H, W] -> the four FMT outputs {"stageK": fp32 [1, V, C, H / 2^(4-K), W / 2^(4-K)]} that feed the cascade.
-        ``capture``: a dict that receives "vit_imgs" (the bicubic output) and "conv31" (after the add) - tests and measurements."""
+        ``capture``: a dict that receives "vit_imgs" (the bicubic output) and "conv31" (after the add) - tests and measurements.
+        ``vit_levels``: the views' ViT levels, [1, V, n, 768] each (``vit_levels`` per view, stacked): the resize and the ViT are skipped."""
         V, H, W, vit_h, vit_w = self._check(imgs)
         with torch.no_grad():
             if imgs.dtype != torch.float32:
                 imgs = imgs.float()
             views = imgs[0]                                                                   # [V, 3, H, W]: a view, whatever the strides
-            vit_imgs = ops.resize_bicubic(views, vit_h, vit_w)
-            levels = [t.unsqueeze(0) for t in self.vit.forward_interval_features(vit_imgs)]   # [1, V, n, 768] views of the ViT's buffers
+            if vit_levels is None:
+                vit_imgs = ops.resize_bicubic(views, vit_h, vit_w)
+                levels = [t.unsqueeze(0) for t in self.vit.forward_interval_features(vit_imgs)]   # [1, V, n, 768] views of the ViT's buffers
+            else:
+                vit_imgs, levels = None, self._check_levels(vit_levels, imgs, V, vit_h, vit_w)
             vit_feat = self.decoder_vit(levels, Fmats=None, vit_shape=[1, V, vit_h // PATCH, vit_w // PATCH, self.vit.embed_dim])
             conv01, conv11, conv21, conv31 = self.encoder(views)
             conv31 = ops.resize_bilinear_add(conv31, vit_feat)
@@ -122,9 +147,10 @@ class DINOv2MVSNet(CascadeDepthHead):
             return self.FMT_module({"stage%d" % (k + 1): f.unsqueeze(0) for k, f in enumerate(feats)})
 
     def forward(self, imgs: torch.Tensor, proj_matrices: Dict[str, torch.Tensor], depth_values: torch.Tensor,
-                tmp: Sequence[float] = (5.0, 5.0, 5.0, 1.0)) -> Dict[str, torch.Tensor]:
+                tmp: Sequence[float] = (5.0, 5.0, 5.0, 1.0), vit_levels=None) -> Dict[str, torch.Tensor]:
         self._check(imgs, tuple(proj_matrices.values()) + (depth_values,))
-        return CascadeDepthHead.forward(self, self.feature_maps(imgs), proj_matrices, depth_values, tmp)
+        feats = self.feature_maps(imgs) if vit_levels is None else self.feature_maps(imgs, vit_levels=vit_levels)
+        return CascadeDepthHead.forward(self, feats, proj_matrices, depth_values, tmp)
 
     def capture(self, *args, **kwargs):
         raise NotImplementedError("DINOv2MVSNet: capture the forward with torch.cuda.graph after one warm call (CascadeDepthHead.capture takes "

@@ -1474,3 +1474,61 @@ def resize_bilinear_add(base: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
     check(lib().mvs_resize_bilinear_add_fwd(ptr(base), _base_ptr(x), x.stride(0), x.stride(1), x.stride(2), x.stride(3), ptr(out), N, Cc, h, w,
                                             x.shape[2], x.shape[3], stream_of(base)), "mvs_resize_bilinear_add_fwd")
     return out
+
+
+# ---- a scene's depth inference: image preparation and output packing (csrc/scene_kernels.hip) ----
+IMAGENET_MEAN, IMAGENET_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
+
+
+def normalise_table(mean: Sequence[float] = IMAGENET_MEAN, std: Sequence[float] = IMAGENET_STD) -> torch.Tensor:
+    """fp32 [3, 256] on the host: ToTensor + Normalize of every byte value, ``((u / 255) - mean[c]) / std[c]`` as torch evaluates it
+    (general_eval.py:29-32), so a lookup is bit-equal to the transform."""
+    u = torch.arange(256, dtype=torch.uint8).to(torch.float32).div(255)
+    m, s = torch.tensor(mean, dtype=torch.float32), torch.tensor(std, dtype=torch.float32)
+    return u[None].sub(m[:, None]).div(s[:, None]).contiguous()
+
+
+def image_prepare(src: torch.Tensor, H: int, W: int, table: torch.Tensor, pad_rows: int = 0, planar: Optional[torch.Tensor] = None,
+                  resized: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """A decoded image, uint8 RGB [h, w, 3], -> (fp32 planar [3, H, W] normalised through ``table``, uint8 [H, W, 3]): ``pad_rows``
+    replicated rows above and below (the "tt" pad of general_eval.py:115-116), the 8-bit linear resize to H x W (OpenCV's fixed-point
+    arithmetic; equal sizes: the identity), ToTensor and Normalize in one pass.  ``planar`` / ``resized``: contiguous tensors of those shapes
+    to write into (a slot of a view cache); fresh ones otherwise."""
+    if not torch.is_tensor(src) or src.dtype != torch.uint8 or src.dim() != 3 or src.shape[2] != 3 or min(src.shape) < 1:
+        raise ValueError("image_prepare: src must be a uint8 tensor [h, w, 3] with no empty axis; got %s"
+                         % ((src.dtype, tuple(src.shape)) if torch.is_tensor(src) else type(src),))
+    H, W, pad_rows = int(H), int(W), int(pad_rows)
+    if H < 1 or W < 1:
+        raise ValueError("image_prepare: the output size must be at least 1 x 1; got %d x %d" % (H, W))
+    if not torch.is_tensor(table) or table.dtype != torch.float32 or tuple(table.shape) != (3, 256) or table.device != src.device:
+        raise ValueError("image_prepare: table must be a fp32 tensor [3, 256] on the image's device (ops.normalise_table())")
+    src, table = src.contiguous(), table.contiguous()
+    if planar is None:
+        planar = torch.empty(3, H, W, dtype=torch.float32, device=src.device)
+    if resized is None:
+        resized = torch.empty(H, W, 3, dtype=torch.uint8, device=src.device)
+    for t, dt, shape, what in ((planar, torch.float32, (3, H, W), "planar"), (resized, torch.uint8, (H, W, 3), "resized")):
+        if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous() or t.device != src.device:
+            raise ValueError("image_prepare: %s must be a contiguous %s tensor %s on the image's device" % (what, dt, list(shape)))
+    check(lib().mvs_image_prepare_fwd(ptr(src), src.shape[0], src.shape[1], pad_rows, ptr(table), ptr(planar), ptr(resized), H, W,
+                                      stream_of(src)), "mvs_image_prepare_fwd")
+    return planar, resized
+
+
+def depth_outputs_pack(depth: torch.Tensor, conf: torch.Tensor, reg_conf: Optional[torch.Tensor] = None,
+                       out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """depth, conf (and stage 4's confidence for --combine_reg_conf) fp32 [H, W] -> uint8 [5 H W]: the depth rows bottom-up as fp32 bytes
+    (the body ``save_pfm`` writes after its flipud), then ``uint8(c * 255)`` with c = conf or (conf * 3 + reg_conf) / 4 (test.py:280-285)."""
+    maps = [("depth", depth), ("conf", conf)] + ([("reg_conf", reg_conf)] if reg_conf is not None else [])
+    for what, t in maps:
+        if not torch.is_tensor(t) or t.dtype != torch.float32 or t.dim() != 2 or min(t.shape) < 1 or t.shape != depth.shape or t.device != depth.device:
+            raise ValueError("depth_outputs_pack: %s must be a fp32 tensor [H, W] with no empty axis, all maps of one size on one device; got %s"
+                             % (what, (t.dtype, tuple(t.shape)) if torch.is_tensor(t) else type(t)))
+    H, W = depth.shape
+    if out is None:
+        out = torch.empty(5 * H * W, dtype=torch.uint8, device=depth.device)
+    elif out.dtype != torch.uint8 or out.numel() != 5 * H * W or not out.is_contiguous() or out.device != depth.device:
+        raise ValueError("depth_outputs_pack: out must be a contiguous uint8 tensor of 5 H W = %d bytes on the maps' device" % (5 * H * W))
+    check(lib().mvs_depth_outputs_pack_fwd(ptr(depth.contiguous()), ptr(conf.contiguous()), ptr(None if reg_conf is None else reg_conf.contiguous()),
+                                           ptr(out), H, W, stream_of(depth)), "mvs_depth_outputs_pack_fwd")
+    return out
