@@ -23,12 +23,12 @@
 //      normaliser are one more GEMM of the block kernel.
 //   2. fmt_block_kernel: one CrossBlock for 32 tokens per wave; packed weights stream from L2 in lane order (164 KB for the four
 //      matrices + the 20 KB key/value operand exceed the LDS; each wave reads them once per 32 tokens).
-//   3. fmt_path_kernel<C>: smooth_k(bilinear(dim_reduction_k(prev)) + lateral), an implicit-GEMM 3x3 in the form of fpn_conv_kernel
-//      whose staging evaluates the merged map for the tile and its halo (align_corners=False, any size ratio, no biases); the merged
-//      map is never written.  fmt_merge_kernel + the same convolution on a planar source are the unfused form.
+//   3. the pathway (reported as fmt_path_kernel): smooth_k(bilinear(dim_reduction_k(prev)) + lateral) = the shared implicit-GEMM 3x3
+//      conv2d_split_kernel<C, C, 3, 1, FtMergeSrc<C>, PlanarSink<false>> (conv2d_split.h) whose staging evaluates the merged map for the tile
+//      and its halo (align_corners=False, any size ratio, no biases); the merged map is never written.  fmt_merge_kernel
+//      (conv2d_source_kernel on FtMergeSrc) + the same convolution on PlanarSrc are the unfused form.
 // Staged positions are clamped to the image explicitly (zero padding from a branch, never from an out-of-range load).
-#include "mvs_common.h"
-#include "split_format.h"
+#include "conv2d_split.h"
 
 namespace mvs {
 
@@ -352,25 +352,11 @@ __global__ __launch_bounds__(256) void fmt_kv_reduce_kernel(const float* __restr
 // ---------------------------------------------------------------------------------------------------------------------------------
 // pathway: smooth_k(bilinear(dim_reduction_k(prev), size of lateral, align_corners=False) + lateral)
 // ---------------------------------------------------------------------------------------------------------------------------------
-constexpr int FT_TH = 4, FT_TW = 64;
-
-template <int C>
-struct FtPlanarSrc {
-    const float* x;
-    int H, W;
-    const float* p;
-    __device__ __forceinline__ void at(int n, int gy, int gx) { p = x + ((size_t)n * C * H + gy) * W + gx; }
-    __device__ __forceinline__ void load8(int c0, float* v) const {
-        const size_t hw = (size_t)H * W;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) v[k] = p[(size_t)(c0 + k) * hw];
-    }
-};
-
 // merged[c] at a pixel of the lateral = lateral[c] + sum_ci w[c][ci] * bilinear(prev[ci]); prev [N, 2C, h, w], lateral [N, C, H, W].
 // The 1x1 and the interpolation are both linear and bias-free: the 2C coarse channels are interpolated once per pixel, then reduced.
 template <int C>
 struct FtMergeSrc {
+    static constexpr int STAGE_OCTETS = 0;
     static constexpr int CP = 2 * C;
     const float* prev;
     const float* lat;
@@ -405,139 +391,6 @@ struct FtMergeSrc {
         }
     }
 };
-
-template <int C>
-struct FtShape {
-    static constexpr int OPT = C / 8, NOCT = 9 * OPT, NSTEP = (NOCT + 3) / 4, MREP = (C + 15) / 16, NREP = FT_TW / 16;
-    static constexpr int IH = FT_TH + 2, IW = FT_TW + 2, NPIX = IH * IW;
-    static constexpr int PLANE = NPIX * 32 + 32;                  // bytes of one octet plane (+ one slot: bank rows differ)
-    static constexpr size_t LDS = (size_t)OPT * PLANE;
-};
-
-// Conv2d(C, C, 3, padding=1, bias=False) on Src; weights = packing.pack_fpn_conv_weights(w, 1) (one pass: C <= 32).  A workgroup owns
-// 4 output rows x 64 columns (one row per wave); the contraction is fpn_conv_kernel's.
-template <int C, class Src>
-__global__ __launch_bounds__(256) void fmt_path_kernel(Src src, const void* __restrict__ wp, float* __restrict__ out, int H, int W, int tiles_x,
-                                                       int ntiles) {
-    typedef FtShape<C> F;
-    constexpr int OPT = F::OPT, NOCT = F::NOCT, NSTEP = F::NSTEP, IW = F::IW, NPIX = F::NPIX, MREP = F::MREP, NREP = F::NREP;
-    HIP_DYNAMIC_SHARED(float4, lds4)
-    char* ldsb = reinterpret_cast<char*>(lds4);
-    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, g = lane >> 4;
-    const int tile = (int)xcd_remap(blockIdx.x, (unsigned)ntiles), n = (int)blockIdx.y;
-    const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
-    const int y0 = ty * FT_TH, x0 = tx * FT_TW;
-
-    // ---- stage: one work-item = one staged pixel, every channel octet; outside the image = zero padding from a branch ----
-    for (int pix = tid; pix < NPIX; pix += 256) {
-        const int iy = pix / IW, ix = pix - iy * IW;
-        const int gy = y0 - 1 + iy, gx = x0 - 1 + ix;
-        const bool inside = gy >= 0 && gy < H && gx >= 0 && gx < W;
-        Src s = src;
-        if (inside) s.at(n, gy, gx);
-#pragma unroll
-        for (int oc = 0; oc < OPT; ++oc) {
-            float v[8];
-            if (inside) {
-                s.load8(oc * 8, v);
-            } else {
-#pragma unroll
-                for (int k = 0; k < 8; ++k) v[k] = 0.0f;
-            }
-            bf16x8 hi, lo;
-            split8(make_float4(v[0], v[1], v[2], v[3]), make_float4(v[4], v[5], v[6], v[7]), hi, lo);
-            char* dst = ldsb + oc * F::PLANE + pix * 32;
-            *reinterpret_cast<bf16x8*>(dst) = hi;
-            *reinterpret_cast<bf16x8*>(dst + 16) = lo;
-        }
-    }
-    __syncthreads();
-
-    f32x4 acc[MREP][NREP];
-#pragma unroll
-    for (int mb = 0; mb < MREP; ++mb)
-#pragma unroll
-        for (int nb = 0; nb < NREP; ++nb) acc[mb][nb] = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
-    // ---- contract: step = four channel octets (one per lane group), octet q = 4 step + g -> (tap, oc) = divmod(q, OPT) ----
-    const bf16x8* wq = reinterpret_cast<const bf16x8*>(wp) + lane;
-#pragma unroll
-    for (int step = 0; step < NSTEP; ++step) {
-        const int q = 4 * step + g;
-        const bool live = q < NOCT;                               // the last step may run past the 9 x OPT octets: zero operand
-        const int tap = live ? q / OPT : 0, oc = live ? q - tap * OPT : 0;
-        const int ky = tap / 3, kx = tap - ky * 3;
-        const char* srcp = ldsb + oc * F::PLANE + ((wave + ky) * IW + li + kx) * 32;
-        bf16x8 ah[MREP], al[MREP], bh[NREP], bl[NREP];
-#pragma unroll
-        for (int mb = 0; mb < MREP; ++mb) {
-            ah[mb] = wq[(size_t)((step * MREP + mb) * 2 + 0) * 64];
-            al[mb] = wq[(size_t)((step * MREP + mb) * 2 + 1) * 64];
-        }
-#pragma unroll
-        for (int nb = 0; nb < NREP; ++nb) {
-            bf16x8 hv = *reinterpret_cast<const bf16x8*>(srcp + nb * 16 * 32);
-            bf16x8 lv = *reinterpret_cast<const bf16x8*>(srcp + nb * 16 * 32 + 16);
-            if (!live) {
-#pragma unroll
-                for (int k = 0; k < 8; ++k) { hv[k] = (__bf16)0.0f; lv[k] = (__bf16)0.0f; }
-            }
-            bh[nb] = hv;
-            bl[nb] = lv;
-        }
-#pragma unroll
-        for (int mb = 0; mb < MREP; ++mb)
-#pragma unroll
-            for (int nb = 0; nb < NREP; ++nb) {
-                acc[mb][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[mb], bh[nb], acc[mb][nb], 0, 0, 0);
-                acc[mb][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[mb], bl[nb], acc[mb][nb], 0, 0, 0);
-                acc[mb][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[mb], bh[nb], acc[mb][nb], 0, 0, 0);
-            }
-    }
-    // ---- epilogue: lane (pixel li, group g) holds output channels 16 mb + 4 g .. + 3 of its pixel; planar fp32 stores ----
-    const int y = y0 + wave;
-    if (y >= H) return;
-    const size_t hw = (size_t)H * W;
-    float* ob = out + (size_t)n * C * hw + (size_t)y * W;
-#pragma unroll
-    for (int nb = 0; nb < NREP; ++nb) {
-        const int xx = x0 + nb * 16 + li;
-        if (xx >= W) continue;
-#pragma unroll
-        for (int mb = 0; mb < MREP; ++mb) {
-            const int co = 16 * mb + 4 * g;
-            if (co >= C) continue;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) ob[(size_t)(co + k) * hw + xx] = acc[mb][nb][k];
-        }
-    }
-}
-
-template <int C>
-__global__ __launch_bounds__(256) void fmt_merge_kernel(FtMergeSrc<C> src, float* __restrict__ out) {
-    const int x = (int)blockIdx.x * 64 + ((int)threadIdx.x & 63), y = (int)blockIdx.y * 4 + ((int)threadIdx.x >> 6), n = (int)blockIdx.z;
-    if (x >= src.W || y >= src.H) return;
-    FtMergeSrc<C> s = src;
-    s.at(n, y, x);
-    const size_t HW = (size_t)src.H * src.W;
-    float* o = out + (size_t)n * C * HW + (size_t)y * src.W + x;
-#pragma unroll
-    for (int c0 = 0; c0 < C; c0 += 8) {
-        float v[8];
-        s.load8(c0, v);
-#pragma unroll
-        for (int k = 0; k < 8; ++k) o[(size_t)(c0 + k) * HW] = v[k];
-    }
-}
-
-template <int C, class Src>
-static int launch_fmt_path(const Src& src, const void* wp, float* out, int N, int H, int W, hipStream_t st, const char* what) {
-    typedef FtShape<C> F;
-    const int tiles_x = (int)ceil_div(W, FT_TW), tiles_y = (int)ceil_div(H, FT_TH);
-    if (F::LDS > 48 * 1024)
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&fmt_path_kernel<C, Src>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)F::LDS);
-    hipLaunchKernelGGL((fmt_path_kernel<C, Src>), dim3(tiles_x * tiles_y, N), dim3(256), F::LDS, st, src, wp, out, H, W, tiles_x, tiles_x * tiles_y);
-    return check_launch(what);
-}
 
 template <int C>
 static FtMergeSrc<C> ft_merge_src(const float* prev, const float* lat, const float* wr, int h, int w, int H, int W) {
@@ -610,7 +463,9 @@ extern "C" int mvs_fmt_path_fwd(const float* prev, const float* lateral, const f
         return MVS_ERR_ARG;
     }
 #define MVS_FMT_GO(CC) \
-    if (C == CC) return launch_fmt_path<CC>(ft_merge_src<CC>(prev, lateral, w_reduce, h, w, H, W), w_packed, y, N, H, W, (hipStream_t)stream, "fmt_path_kernel");
+    if (C == CC) \
+        return launch_conv2d_split<CC, CC, 3, 1>(ft_merge_src<CC>(prev, lateral, w_reduce, h, w, H, W), w_packed, PlanarSink<false>{nullptr, 0, y, nullptr, 0}, N, H, W, \
+                                                 (hipStream_t)stream, "fmt_path_kernel");
     MVS_FMT_LEVELS(MVS_FMT_GO)
 #undef MVS_FMT_GO
     set_error("mvs_fmt_path_fwd: built for the pathway levels 64 -> 32, 32 -> 16, 16 -> 8 (C = 32, 16, 8) [FMT.py:146-152]; got C = %d", C);
@@ -623,12 +478,8 @@ extern "C" int mvs_fmt_merge_fwd(const float* prev, const float* lateral, const 
         set_error("mvs_fmt_merge_fwd: bad arguments");
         return MVS_ERR_ARG;
     }
-    const dim3 grid(ceil_div(W, 64), ceil_div(H, 4), N);
 #define MVS_FMT_MG(CC) \
-    if (C == CC) { \
-        hipLaunchKernelGGL((fmt_merge_kernel<CC>), grid, dim3(256), 0, (hipStream_t)stream, ft_merge_src<CC>(prev, lateral, w_reduce, h, w, H, W), merged); \
-        return check_launch("fmt_merge_kernel"); \
-    }
+    if (C == CC) return launch_conv2d_source<CC, CC / 8>(ft_merge_src<CC>(prev, lateral, w_reduce, h, w, H, W), merged, N, (hipStream_t)stream, "fmt_merge_kernel");
     MVS_FMT_LEVELS(MVS_FMT_MG)
 #undef MVS_FMT_MG
     set_error("mvs_fmt_merge_fwd: built for C = 32, 16, 8 [FMT.py:146-152]; got C = %d", C);
@@ -638,7 +489,9 @@ extern "C" int mvs_fmt_merge_fwd(const float* prev, const float* lateral, const 
 extern "C" int mvs_fmt_smooth_fwd(const float* x, const void* w_packed, float* y, int N, int C, int H, int W, void* stream) {
     if (!x || !w_packed || !y || !ft_path_args("mvs_fmt_smooth_fwd", N, C, H, W)) { set_error("mvs_fmt_smooth_fwd: bad arguments"); return MVS_ERR_ARG; }
 #define MVS_FMT_SM(CC) \
-    if (C == CC) return launch_fmt_path<CC>(FtPlanarSrc<CC>{x, H, W, nullptr}, w_packed, y, N, H, W, (hipStream_t)stream, "fmt_path_kernel");
+    if (C == CC) \
+        return launch_conv2d_split<CC, CC, 3, 1>(PlanarSrc{x, CC, H, W, nullptr}, w_packed, PlanarSink<false>{nullptr, 0, y, nullptr, 0}, N, H, W, (hipStream_t)stream, \
+                                                 "fmt_path_kernel");
     MVS_FMT_LEVELS(MVS_FMT_SM)
 #undef MVS_FMT_SM
     set_error("mvs_fmt_smooth_fwd: built for C = 32, 16, 8 [FMT.py:150-152]; got C = %d", C);

@@ -107,14 +107,14 @@ def pack_conv_weights_bf16x3(w: torch.Tensor, ch: int, split=None) -> torch.Tens
 
 
 def fpn_chunk(cin: int, stride: int) -> int:
-    """Input channels staged per LDS pass by ``fpn_conv_kernel`` (csrc/fpn_kernels.hip FpnShape::CH): all of them up to 32 at stride 1,
+    """Input channels staged per LDS pass by ``conv2d_split_kernel`` (csrc/conv2d_split.h Conv2dShape::CH): all of them up to 32 at stride 1,
     one octet at stride 2 (the 2x wider staged tile).  Cin is first padded to a multiple of 8."""
     cinp = (cin + 7) // 8 * 8
     return min(cinp, 32) if stride == 1 else 8
 
 
 def pack_fpn_conv_weights(w: torch.Tensor, stride: int) -> torch.Tensor:
-    """Conv2d weight [Cout, Cin, k, k] (BN folded) -> the bf16x3 packing of ``fpn_conv_kernel``: Cin zero-padded to a multiple of 8,
+    """Conv2d weight [Cout, Cin, k, k] (BN folded) -> the bf16x3 packing of ``conv2d_split_kernel``: Cin zero-padded to a multiple of 8,
     taps (ky*k + kx) enumerated like the 3-D packer's with kd = 1."""
     cout, cin = w.shape[:2]
     cinp = (cin + 7) // 8 * 8

@@ -101,7 +101,7 @@ def main():
                 finally:
                     _lib._LIB = real
                 torch.cuda.synchronize()
-            ours = ("fmt_block_kernel", "fmt_kv_", "fmt_path_kernel", "fmt_merge_kernel")
+            ours = ("fmt_block_kernel", "fmt_kv_", "conv2d_split_kernel", "conv2d_source_kernel")
             torch_kernels = sum(1 for e in prof.events() if str(getattr(e, "device_type", "")).endswith("CUDA")
                                 and not any(o in e.name for o in ours) and "Memset" not in e.name)
         except Exception as exc:                                                  # the count is a report, never a reason to lose the timings
