@@ -678,6 +678,41 @@ int mvs_image_prepare_fwd(const unsigned char* src, int h, int w, int pad_rows, 
                           int H, int W, void* stream);
 int mvs_depth_outputs_pack_fwd(const float* depth, const float* conf, const float* reg_conf, void* staging, int H, int W, void* stream);
 
+/* ==== the multi-stage depth losses and the validation metrics (models/losses.py, utils.py:156-189) ================
+ * All maps are dense planar fp32: logits / hyp [B,D,H,W], depth / gt / mask [B,H,W] (a pixel counts where mask > 0.5), interval [B].  Every
+ * reduction leaves one partial per workgroup in the workspace and a one-workgroup launch adds them in a fixed order: no floating-point
+ * atomics, bit-identical run to run.  loss fp32 [1] = weight * sum / N and count int32 [1] = N stay on the device; N = 0 gives a NaN loss
+ * (a mean over nothing) and an all-zero gradient.  The backward entry points read the incoming gradient grad_loss [1] and N from device
+ * memory and write their whole output (no memset, no host synchronisation).  B H W < 2^31.
+ * mvs_ce_loss_fwd: per pixel one walk over the depth column (from plane D - 1 down when inverse: the reference's flips are index arithmetic):
+ *   log-sum-exp of the logits, iv[j] = |d[j+1] - d[j]| / 2 with the last interval repeated, the bin = count of d[j] + iv[j] <= gt clamped to
+ *   D - 1, out of range where gt < d[0] - iv[0] or gt > d[D-1] + iv[D-1].  index int32 [B,H,W] = the target plane in STORED order, -1 where
+ *   the pixel is masked out or out of range; lse fp32 [B,H,W].  These 8 bytes per pixel are all the backward needs.  D >= 2.
+ * mvs_ce_loss_bwd: grad_logits = (grad_loss * weight / N) * (exp(logit - lse) - [plane == index]) where index >= 0, else 0.
+ * mvs_reg_loss_fwd / _bwd: smooth L1 (beta 1) of depth / interval[b] against gt / interval[b] (interval NULL: 1); with hyp != NULL every
+ *   pixel's loss is clamped from above by (d_last - d_first) / interval[b], first and last in the walk order, and the gradient passes where
+ *   loss <= range (torch.clamp_max).  The backward recomputes the pixel from the inputs: nothing is kept.
+ * mvs_depth_metrics: est, gt [B,H,W] fp32, mask fp32 (> 0.5) or bytes (mask_bytes: != 0).  T <= MVS_METRICS_MAX_T thresholds and bands, formed
+ *   on the device in fp64 and rounded to fp32: value = base * factor with base = interval ? (double)interval[per_sample ? b : 0] / divisor : 1
+ *   and the host arrays thres / band_lo / band_hi [T] of factors; a NaN band_lo means "no band" (every valid pixel).  Per image: counts int32
+ *   [B, 1 + 2 T] = valid, T counts of |est - gt| > thres, T counts of lo <= err <= hi; sums fp64 [B,T] of the errors inside the bands; means
+ *   fp32 [B + 1, 2 T] = per image T ratios count / valid (no valid pixel: NaN) and T band means (an empty band: 0; no band and no valid
+ *   pixel: NaN), row B = the mean over the images.  Two launches.                                                          */
+#define MVS_METRICS_MAX_T 8
+size_t mvs_loss_workspace_bytes(long long pixels);
+int mvs_ce_loss_fwd(const float* logits, const float* hyp, const float* gt, const float* mask, int inverse, double weight, int* index, float* lse,
+                    void* workspace, size_t workspace_bytes, float* loss, int* count, int B, int D, int H, int W, void* stream);
+int mvs_ce_loss_bwd(const float* logits, const int* index, const float* lse, const float* grad_loss, const int* count, double weight,
+                    float* grad_logits, int B, int D, int H, int W, void* stream);
+int mvs_reg_loss_fwd(const float* depth, const float* gt, const float* mask, const float* interval, const float* hyp, int inverse, double weight,
+                     void* workspace, size_t workspace_bytes, float* loss, int* count, int B, int D, int H, int W, void* stream);
+int mvs_reg_loss_bwd(const float* depth, const float* gt, const float* mask, const float* interval, const float* hyp, int inverse,
+                     const float* grad_loss, const int* count, double weight, float* grad_depth, int B, int D, int H, int W, void* stream);
+size_t mvs_depth_metrics_workspace_bytes(int B, int H, int W, int T);
+int mvs_depth_metrics(const float* est, const float* gt, const void* mask, int mask_bytes, const float* interval, double divisor, int per_sample,
+                      const double* thres, const double* band_lo, const double* band_hi, int T, void* workspace, size_t workspace_bytes,
+                      int* counts, double* sums, float* means, int B, int H, int W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

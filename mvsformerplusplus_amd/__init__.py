@@ -20,10 +20,14 @@ from .vit import DinoVisionTransformer, patch_all, patch_vit, vit_base
 from .network import DINOv2MVSNet, checkpoint_state_dict, patch_network
 from .position_encoding import PositionEncoding3D, get_position_3d
 from .warping import diff_homo_warping_3D_with_mask, homo_warping_3D, homo_warping_3D_with_mask
+from .losses import ce_loss, get_loss, get_multi_stage_losses, reg_loss, simple_loss
+from .metrics import AbsDepthError_metrics, Thres_metrics, ValidationMeter, validation_metrics
 
 __all__ = ["CascadeDepthHead", "patch_model", "StageNet", "Conv3d", "Deconv3d", "ConvBnReLU", "CostRegNet", "CostRegNet3D", "CostRegNet2D",
            "PureTransformerCostReg", "get_position_3d", "PositionEncoding3D", "fusion", "PackedFeatures", "pack_features", "TiledFeatureHead", "FPNEncoder", "FPNDecoder", "patch_fpn",
            "FMT_with_pathway", "patch_fmt", "CrossVITDecoder", "patch_vit_decoder", "DinoVisionTransformer", "vit_base", "patch_vit", "patch_all",
            "DINOv2MVSNet", "patch_network", "checkpoint_state_dict",
            "depth_regression", "conf_regression", "init_range", "init_inverse_range", "schedule_inverse_range", "schedule_range",
-           "homo_warping_3D_with_mask", "homo_warping_3D", "diff_homo_warping_3D_with_mask"]
+           "homo_warping_3D_with_mask", "homo_warping_3D", "diff_homo_warping_3D_with_mask",
+           "get_multi_stage_losses", "get_loss", "ce_loss", "reg_loss", "simple_loss",
+           "Thres_metrics", "AbsDepthError_metrics", "validation_metrics", "ValidationMeter"]

@@ -153,6 +153,13 @@ SIGNATURES = {
     "mvs_resize_bilinear_add_fwd": (_i, [_vp, _vp] + [C.c_longlong] * 4 + [_vp] + [_i] * 6 + [_vp]),
     "mvs_image_prepare_fwd": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp]),
     "mvs_depth_outputs_pack_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp]),
+    "mvs_loss_workspace_bytes": (_sz, [C.c_longlong]),
+    "mvs_ce_loss_fwd": (_i, [_vp, _vp, _vp, _vp, _i, C.c_double, _vp, _vp, _vp, _sz, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "mvs_ce_loss_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, C.c_double, _vp, _i, _i, _i, _i, _vp]),
+    "mvs_reg_loss_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, C.c_double, _vp, _sz, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "mvs_reg_loss_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, C.c_double, _vp, _i, _i, _i, _i, _vp]),
+    "mvs_depth_metrics_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "mvs_depth_metrics": (_i, [_vp, _vp, _vp, _i, _vp, C.c_double, _i, _vp, _vp, _vp, _i, _vp, _sz, _vp, _vp, _vp, _i, _i, _i, _vp]),
 }
 
 

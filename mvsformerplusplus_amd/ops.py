@@ -1532,3 +1532,152 @@ def depth_outputs_pack(depth: torch.Tensor, conf: torch.Tensor, reg_conf: Option
     check(lib().mvs_depth_outputs_pack_fwd(ptr(depth.contiguous()), ptr(conf.contiguous()), ptr(None if reg_conf is None else reg_conf.contiguous()),
                                            ptr(out), H, W, stream_of(depth)), "mvs_depth_outputs_pack_fwd")
     return out
+
+
+# ---- the multi-stage depth losses and the validation metrics (csrc/loss_kernels.hip) ----
+METRICS_MAX_T = 8
+
+
+def _loss_map(t, what: str, fn: str, shape=None) -> torch.Tensor:
+    """A fp32 map [B, H, W] with no empty axis (of `shape` when given) -> contiguous."""
+    if not torch.is_tensor(t) or t.dtype != torch.float32 or t.dim() != 3 or min(t.shape) < 1 or (shape is not None and tuple(t.shape) != tuple(shape)):
+        raise ValueError("%s: %s must be a fp32 tensor %s with no empty axis; got %s"
+                         % (fn, what, "[B, H, W]" if shape is None else list(shape), (t.dtype, tuple(t.shape)) if torch.is_tensor(t) else type(t)))
+    return t.contiguous()
+
+
+def _loss_volume(t, what: str, fn: str, bhw=None) -> torch.Tensor:
+    """A fp32 volume [B, D, H, W] with D >= 2 (over the maps `bhw` when given) -> contiguous."""
+    ok = torch.is_tensor(t) and t.dtype == torch.float32 and t.dim() == 4 and min(t.shape) >= 1 and t.shape[1] >= 2
+    if ok and bhw is not None:
+        ok = (t.shape[0], t.shape[2], t.shape[3]) == tuple(bhw)
+    if not ok:
+        raise ValueError("%s: %s must be a fp32 tensor [B, D, H, W] with D >= 2 that matches the maps; got %s"
+                         % (fn, what, (t.dtype, tuple(t.shape)) if torch.is_tensor(t) else type(t)))
+    return t.contiguous()
+
+
+def _loss_workspace(pixels: int, like: torch.Tensor):
+    nbytes = lib().mvs_loss_workspace_bytes(pixels)
+    if nbytes == 0:
+        raise ValueError("the losses take 1 <= B H W < 2^31 pixels; got %d" % pixels)
+    return torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=like.device), nbytes     # 8-byte aligned; sized from the launch grid
+
+
+def ce_loss_fwd(logits: torch.Tensor, hyp: torch.Tensor, gt: torch.Tensor, mask: torch.Tensor, inverse: bool, weight: float = 1.0):
+    """The "ce" stage loss (losses.py:31-62): logits, hyp fp32 [B,D,H,W], gt, mask fp32 [B,H,W] -> (loss fp32 [1] = weight * mean over the N
+    valid pixels of lse - logit[bin], N int32 [1], index int32 [B,H,W] (the target plane in stored order, -1 = not valid), lse fp32
+    [B,H,W]).  Two launches, no synchronisation; N = 0 gives NaN."""
+    x = _loss_volume(logits, "logits", "ce_loss_fwd")
+    B, D, H, W = x.shape
+    h = _loss_volume(hyp, "hyp", "ce_loss_fwd", (B, H, W))
+    if h.shape[1] != D:
+        raise ValueError("ce_loss_fwd: logits %s and hyp %s differ in D" % (tuple(x.shape), tuple(h.shape)))
+    g, m = _loss_map(gt, "gt", "ce_loss_fwd", (B, H, W)), _loss_map(mask, "mask", "ce_loss_fwd", (B, H, W))
+    ws, nbytes = _loss_workspace(B * H * W, x)
+    index = torch.empty(B, H, W, dtype=torch.int32, device=x.device)
+    lse = torch.empty(B, H, W, dtype=torch.float32, device=x.device)
+    loss = torch.empty(1, dtype=torch.float32, device=x.device)
+    count = torch.empty(1, dtype=torch.int32, device=x.device)
+    check(lib().mvs_ce_loss_fwd(ptr(x), ptr(h), ptr(g), ptr(m), 1 if inverse else 0, float(weight), ptr(index), ptr(lse), ptr(ws), nbytes,
+                                ptr(loss), ptr(count), B, D, H, W, stream_of(x)), "mvs_ce_loss_fwd")
+    return loss, count, index, lse
+
+
+def ce_loss_bwd(logits: torch.Tensor, index: torch.Tensor, lse: torch.Tensor, grad_loss: torch.Tensor, count: torch.Tensor,
+                weight: float = 1.0) -> torch.Tensor:
+    """grad_logits [B,D,H,W] = (grad_loss * weight / N) * (exp(logit - lse) - [plane == index]) where index >= 0, else 0; grad_loss fp32 [1]
+    and N int32 [1] are read on the device.  One launch that writes the whole volume."""
+    x = _loss_volume(logits, "logits", "ce_loss_bwd")
+    B, D, H, W = x.shape
+    if not torch.is_tensor(index) or index.dtype != torch.int32 or tuple(index.shape) != (B, H, W):
+        raise ValueError("ce_loss_bwd: index must be an int32 tensor %s" % [B, H, W])
+    if not torch.is_tensor(count) or count.dtype != torch.int32 or count.numel() != 1:
+        raise ValueError("ce_loss_bwd: count must be an int32 tensor of one element")
+    l = _loss_map(lse, "lse", "ce_loss_bwd", (B, H, W))
+    g = _f32c(grad_loss).reshape(1)
+    grad = torch.empty_like(x)
+    check(lib().mvs_ce_loss_bwd(ptr(x), ptr(index.contiguous()), ptr(l), ptr(g), ptr(count.contiguous()), float(weight), ptr(grad), B, D, H, W,
+                                stream_of(x)), "mvs_ce_loss_bwd")
+    return grad
+
+
+def _reg_inputs(fn, depth, gt, mask, interval, hyp):
+    d = _loss_map(depth, "depth", fn)
+    B, H, W = d.shape
+    g, m = _loss_map(gt, "gt", fn, (B, H, W)), _loss_map(mask, "mask", fn, (B, H, W))
+    if interval is not None:
+        if not torch.is_tensor(interval) or interval.dtype != torch.float32 or tuple(interval.shape) != (B,):
+            raise ValueError("%s: interval must be a fp32 tensor [%d] (one per image) or None" % (fn, B))
+        interval = interval.contiguous()
+    if hyp is not None:
+        hyp = _loss_volume(hyp, "hyp", fn, (B, H, W))
+    return d, g, m, interval, hyp, B, (hyp.shape[1] if hyp is not None else 1), H, W
+
+
+def reg_loss_fwd(depth: torch.Tensor, gt: torch.Tensor, mask: torch.Tensor, interval: Optional[torch.Tensor] = None,
+                 hyp: Optional[torch.Tensor] = None, inverse: bool = False, weight: float = 1.0):
+    """The "reg" stage loss (losses.py:64-97 without log_var; reg_loss, simple_loss): smooth L1 (beta 1) of depth / interval[b] against
+    gt / interval[b] over mask > 0.5 (interval None: 1); hyp [B,D,H,W] given = clip_func "dynamic", every pixel's loss clamped from above by
+    the hypotheses' range / interval[b].  -> (loss fp32 [1] = weight * mean, N int32 [1]).  Two launches; N = 0 gives NaN."""
+    d, g, m, itv, h, B, D, H, W = _reg_inputs("reg_loss_fwd", depth, gt, mask, interval, hyp)
+    ws, nbytes = _loss_workspace(B * H * W, d)
+    loss = torch.empty(1, dtype=torch.float32, device=d.device)
+    count = torch.empty(1, dtype=torch.int32, device=d.device)
+    check(lib().mvs_reg_loss_fwd(ptr(d), ptr(g), ptr(m), ptr(itv), ptr(h), 1 if inverse else 0, float(weight), ptr(ws), nbytes, ptr(loss),
+                                 ptr(count), B, D, H, W, stream_of(d)), "mvs_reg_loss_fwd")
+    return loss, count
+
+
+def reg_loss_bwd(depth: torch.Tensor, gt: torch.Tensor, mask: torch.Tensor, interval: Optional[torch.Tensor], hyp: Optional[torch.Tensor],
+                 inverse: bool, grad_loss: torch.Tensor, count: torch.Tensor, weight: float = 1.0) -> torch.Tensor:
+    """grad_depth [B,H,W] of reg_loss_fwd (recomputed from the inputs; the clamp passes the gradient where loss <= range); grad_loss fp32 [1]
+    and N int32 [1] are read on the device.  One launch that writes the whole map."""
+    d, g, m, itv, h, B, D, H, W = _reg_inputs("reg_loss_bwd", depth, gt, mask, interval, hyp)
+    if not torch.is_tensor(count) or count.dtype != torch.int32 or count.numel() != 1:
+        raise ValueError("reg_loss_bwd: count must be an int32 tensor of one element")
+    go = _f32c(grad_loss).reshape(1)
+    grad = torch.empty_like(d)
+    check(lib().mvs_reg_loss_bwd(ptr(d), ptr(g), ptr(m), ptr(itv), ptr(h), 1 if inverse else 0, ptr(go), ptr(count.contiguous()), float(weight),
+                                 ptr(grad), B, D, H, W, stream_of(d)), "mvs_reg_loss_bwd")
+    return grad
+
+
+def depth_metrics(depth_est: torch.Tensor, depth_gt: torch.Tensor, mask: torch.Tensor, thres: Sequence[float],
+                  bands: Sequence[Optional[Tuple[float, float]]], interval: Optional[torch.Tensor] = None, divisor: float = 1.0,
+                  per_sample: bool = False):
+    """The counts and sums behind Thres_metrics / AbsDepthError_metrics (utils.py:156-189) for T thresholds and T bands per image, in one
+    metrics launch plus its finalize: depth_est, depth_gt fp32 [B,H,W]; mask fp32 (> 0.5) or bool / uint8 (!= 0).  A threshold is
+    ``base * factor`` formed on the device in fp64 and rounded to fp32, base = interval[b if per_sample else 0] / divisor (interval None: 1)
+    and the factors the Python numbers given here; a band of None is "no band".
+    -> (counts int32 [B, 1 + 2 T]: valid, T of err > thres, T of lo <= err <= hi; sums fp64 [B, T] of the errors inside the bands; means
+    fp32 [B + 1, 2 T]: per image T ratios and T band means, row B their mean over the images)."""
+    e = _loss_map(depth_est, "depth_est", "depth_metrics")
+    B, H, W = e.shape
+    g = _loss_map(depth_gt, "depth_gt", "depth_metrics", (B, H, W))
+    if not torch.is_tensor(mask) or tuple(mask.shape) != (B, H, W) or mask.dtype not in (torch.float32, torch.bool, torch.uint8):
+        raise ValueError("depth_metrics: mask must be a fp32, bool or uint8 tensor %s; got %s"
+                         % ([B, H, W], (mask.dtype, tuple(mask.shape)) if torch.is_tensor(mask) else type(mask)))
+    m = mask.contiguous()
+    T = len(thres)
+    if not 1 <= T <= METRICS_MAX_T or len(bands) != T:
+        raise ValueError("depth_metrics: 1 to %d thresholds and as many bands; got %d and %d" % (METRICS_MAX_T, T, len(bands)))
+    if interval is not None:
+        if not torch.is_tensor(interval) or interval.dtype != torch.float32 or interval.dim() != 1 or interval.numel() != B:
+            raise ValueError("depth_metrics: interval must be a fp32 tensor [%d] or None" % B)
+        interval = interval.contiguous()
+    nan = float("nan")
+    th = (C.c_double * T)(*[float(t) for t in thres])
+    lo = (C.c_double * T)(*[nan if b is None else float(b[0]) for b in bands])
+    hi = (C.c_double * T)(*[nan if b is None else float(b[1]) for b in bands])
+    nbytes = lib().mvs_depth_metrics_workspace_bytes(B, H, W, T)
+    if nbytes == 0:
+        raise ValueError("depth_metrics: 1 <= B <= 65535 images and B H W < 2^31 pixels; got %s" % ([B, H, W],))
+    ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=e.device)
+    counts = torch.empty(B, 1 + 2 * T, dtype=torch.int32, device=e.device)
+    sums = torch.empty(B, T, dtype=torch.float64, device=e.device)
+    means = torch.empty(B + 1, 2 * T, dtype=torch.float32, device=e.device)
+    check(lib().mvs_depth_metrics(ptr(e), ptr(g), ptr(m), 0 if m.dtype == torch.float32 else 1, ptr(interval), float(divisor),
+                                  1 if per_sample else 0, C.cast(th, C.c_void_p), C.cast(lo, C.c_void_p), C.cast(hi, C.c_void_p), T, ptr(ws),
+                                  nbytes, ptr(counts), ptr(sums), ptr(means), B, H, W, stream_of(e)), "mvs_depth_metrics")
+    return counts, sums, means
