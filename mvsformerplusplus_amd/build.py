@@ -14,8 +14,13 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(CSRC, "libmvs_hip.so")
 STAMP = os.path.join(CSRC, ".libmvs_hip.stamp")
+# the compiler's per-kernel resource remarks (registers, scratch, LDS, occupancy), one log per translation unit: what
+# scripts/kernel_resources.py and tests/test_kernel_resources.py read.  Untracked, rewritten by every build.
+RESOURCE_LOGS = os.path.join(CSRC, ".kernel_resources")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=on", "-Wno-unused-value"]
+FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=on", "-Wno-unused-value",
+         # remarks only (the generated code is the same): the resource report of every kernel goes to RESOURCE_LOGS
+         "-Rpass-analysis=kernel-resource-usage"]
 # per-file extras.  transformer_kernels: MFMA results are consumed by VALU code right away (scores -> softmax), so the
 # accumulators must live in VGPRs (the default AGPR form costs a v_accvgpr move per value and direction); no NaN can
 # occur in the softmax (masked scores are -inf, never inf - inf), which lets max chains fold into v_max3_f32.
@@ -53,6 +58,8 @@ def build(force=False, verbose=False, extra_flags=(), out=None):
     srcs = sorted(glob.glob(os.path.join(CSRC, "*.hip")))
     objs, procs = [], []
     tag = "" if out is None else "." + os.path.basename(out)
+    logdir = RESOURCE_LOGS + tag
+    os.makedirs(logdir, exist_ok=True)
     for s in srcs:
         o = s[:-4] + tag + ".o"
         cmd = [HIPCC] + FLAGS + FILE_FLAGS.get(os.path.basename(s), []) + list(extra_flags) + ["-c", s, "-o", o]
@@ -62,8 +69,12 @@ def build(force=False, verbose=False, extra_flags=(), out=None):
         log = p.communicate()[0].decode()
         if p.returncode != 0:
             raise RuntimeError("hipcc failed: %s\n%s" % (" ".join(cmd), log))
-        if verbose and log.strip():
-            print(log)
+        with open(os.path.join(logdir, os.path.basename(cmd[-3])[:-4] + ".log"), "w") as f:
+            f.write(log)
+        if verbose:
+            rest = "\n".join(l for l in log.splitlines() if "[-Rpass-analysis=kernel-resource-usage]" not in l)
+            if rest.strip():
+                print(rest)
     subprocess.check_call([HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", out or LIB] + objs)
     for o in objs:
         os.remove(o)

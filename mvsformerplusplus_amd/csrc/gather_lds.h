@@ -73,6 +73,22 @@ constexpr bool gl_direct_v = W16 && TILED && std::is_same<T, _Float16>::value &&
 //   * the "no tap inside the image" sentinel GL_NONE (0xffff, 0xffff) is neutral for the packed minimum as it stands and, after a packed + 1
 //     (which wraps it to 0), for the maximum: no compare / select per plane in the bounding box; its window position is clamped by one
 //     v_min_u32 (the weights are zero: any finite window value will do) instead of an exec-masked branch per plane
+// Four waves per SIMD (LEAN, profiles/gather_four_waves_resources.txt): three launches of the headline path - the C = 8 aggregation
+// pass and the C = 32 / C = 64 keeping passes on planar fp32 features with fp16 windows - sat 14-22 registers above the 128 that let a
+// fourth block of 256 work-items share a CU (LDS already allowed it).  Their unit differs from the general one in where values live, not in
+// what is computed:
+//   * the reference features of an octet come through ONE buffer descriptor (plane c = wave-uniform soffset, the pixel = one 32-bit
+//     voffset) instead of eight 64-bit per-lane addresses that stayed live from unit to unit (up to 16 registers); at C = 8 they are
+//     reloaded per unit (L1 / L2 hits) instead of being held twice, as loaded and as scaled by `wscale`
+//   * the keeping passes accumulate plane by plane with single fused multiply-adds: the packed form the vectoriser builds pairs two
+//     planes and keeps the first one's eight blended channels alive until the second's exist
+//   * the aggregation pass forms its output addresses after the view loop (gl_aggregate_kernel)
+// Every other instantiation compiles exactly as before: LEAN is a template parameter and every difference sits behind `if constexpr`.
+template <int DT, int NOCT, int NS, bool TILED, bool KEEP, bool W16>
+constexpr bool gl_lean_entropy_v = DT == MVS_DTYPE_F32 && !TILED && KEEP && W16 && NOCT >= 4 && NS == NOCT;
+template <int DT, int NOCT, int NS, bool TILED, bool W16>
+constexpr bool gl_lean_aggregate_v = DT == MVS_DTYPE_F32 && !TILED && W16 && NOCT == 1 && NS == 1;
+
 constexpr int GL_SB = 2;           // planar staging: rounds of 256 window positions whose loads are issued back to back before any is consumed
 
 // the four taps of one plane into wv[0..7]: t = 8 halves (4 registers) per tap
@@ -109,7 +125,7 @@ __device__ __forceinline__ void gl_window_put(f32x4* win, int i, const float* v)
     }
 }
 
-template <typename T, int NOCT, bool KEEP_GROUPS, bool TILED, bool W16, bool DIRECT = false>
+template <typename T, int NOCT, bool KEEP_GROUPS, bool TILED, bool W16, bool DIRECT = false, bool LEAN = false>
 __device__ __forceinline__ void gl_unit(const T* __restrict__ src, const T* __restrict__ ref, const Homography& hm, float fx, float fy,
                                         const float* depth, bool active, int H, int W, unsigned HW, unsigned pc, f32x4* win,
                                         unsigned* red, int unit, float wscale, const float* rf_in, float* out) {
@@ -224,7 +240,13 @@ __device__ __forceinline__ void gl_unit(const T* __restrict__ src, const T* __re
             // reference features of this octet: issued ahead of the staging loop so that they land while it runs (C = 8: the
             // caller loaded them once per block)
             float rf[8];
-            if (NOCT > 1) {
+            if constexpr (LEAN) {
+                static_assert(!TILED && sizeof(T) == 4 && !DIRECT, "the lean forms read planar fp32 maps");
+                const __amdgpu_buffer_rsrc_t rrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(ref + oofs), 0, (int)(8u * HW * 4u), 0x00020000);
+#pragma unroll
+                for (int c = 0; c < 8; ++c)
+                    rf[c] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rrs, (int)(pc * 4u), (int)((unsigned)c * HW * 4u), 0));
+            } else if (NOCT > 1) {
                 gl_load8<TILED, T>(ref + oofs, HW, pc, rf);
             } else {
 #pragma unroll
@@ -336,7 +358,10 @@ __device__ __forceinline__ void gl_unit(const T* __restrict__ src, const T* __re
                         for (int j = 0; j < GPO; ++j) {
                             float s = out[(o * GPO + j) * GL_DCH + dd];
 #pragma unroll
-                            for (int c = 0; c < CPG; ++c) s += rf[j * CPG + c] * wv[j * CPG + c];
+                            for (int c = 0; c < CPG; ++c) {
+                                if constexpr (LEAN && NOCT > 1) s = MVS_FMAC(rf[j * CPG + c], wv[j * CPG + c], s);   // the same fma, never paired across planes
+                                else s += rf[j * CPG + c] * wv[j * CPG + c];
+                            }
                             out[(o * GPO + j) * GL_DCH + dd] = s;
                         }
                     } else {
@@ -434,6 +459,7 @@ __global__ __launch_bounds__(256) void gl_entropy_kernel(const void* __restrict_
                                                          int W, int view_begin, int view_end, int vpb, int ntx, int nblk) {
     typedef typename FeatT<DT>::type T;
     constexpr bool DIRECT = gl_direct_v<T, TILED, W16, NOCT, KEEP>;
+    constexpr bool LEAN = gl_lean_entropy_v<DT, NOCT, NS, TILED, KEEP, W16>;
     HIP_DYNAMIC_SHARED(float, smem)
     f32x4* win = reinterpret_cast<f32x4*>(smem);
     unsigned* red = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(smem) + GL_WIN_BYTES);
@@ -474,7 +500,7 @@ __global__ __launch_bounds__(256) void gl_entropy_kernel(const void* __restrict_
                 float acc[8 * GL_DCH];
 #pragma unroll
                 for (int i = 0; i < 8 * GL_DCH; ++i) acc[i] = 0.0f;
-                gl_unit<T, NOCT, true, TILED, W16, DIRECT>(src, ref, hm, t.fx, t.fy, depth, active, H, W, HW, t.pc, win, red, unit, inv_cpg, rf0, acc);
+                gl_unit<T, NOCT, true, TILED, W16, DIRECT, LEAN>(src, ref, hm, t.fx, t.fy, depth, active, H, W, HW, t.pc, win, red, unit, inv_cpg, rf0, acc);
                 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
                 const size_t cbase = (size_t)(b * (V - 1) + (v - 1)) * D * HW + t.pc;
 #pragma unroll
@@ -548,6 +574,7 @@ __global__ __launch_bounds__(256) void gl_aggregate_kernel(const void* __restric
                                                            float* __restrict__ vol, float* __restrict__ vis_sum, int normalise, int V,
                                                            int D, int H, int W, int view_begin, int view_end, int ntx, int nblk) {
     typedef typename FeatT<DT>::type T;
+    constexpr bool LEAN = gl_lean_aggregate_v<DT, NOCT, NS, TILED, W16>;
     HIP_DYNAMIC_SHARED(float, smem)
     f32x4* win = reinterpret_cast<f32x4*>(smem);
     unsigned* red = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(smem) + GL_WIN_BYTES);
@@ -587,13 +614,18 @@ __global__ __launch_bounds__(256) void gl_aggregate_kernel(const void* __restric
     for (int v = view_begin; v < view_end; ++v, ++unit) {
         const Homography hm = gl_load_homography(hom + (size_t)(b * (V - 1) + (v - 1)) * 12);
         const float w = vp[(unsigned)(v - 1) * HW];                                               // cost_volume.py:97
-        gl_unit<T, NOCT, true, TILED, W16, gl_direct_v<T, TILED, W16, NOCT, false>>(feat + (size_t)v * C * HW, ref, hm, t.fx, t.fy, depth, active, H, W, HW, t.pc, win, red, unit, inv_cpg * w, rf0, acc);
+        gl_unit<T, NOCT, true, TILED, W16, gl_direct_v<T, TILED, W16, NOCT, false>, LEAN>(feat + (size_t)v * C * HW, ref, hm, t.fx, t.fy, depth, active, H, W, HW, t.pc, win, red, unit, inv_cpg * w, rf0, acc);
     }
+    // LEAN: the four planes' 64-bit output offsets are formed here, not ahead of the view loop (8 registers live through every unit otherwise):
+    // the plane and pixel index pass through an empty asm statement and come out as new values
+    int d0e = d0;
+    unsigned pce = t.pc;
+    if constexpr (LEAN) asm volatile("" : "+" MVS_OPAQUE_REG(d0e), "+" MVS_OPAQUE_REG(pce));
     if (active) {
         float* vb = vol + (size_t)b * D * HW * 8;
 #pragma unroll
         for (int dd = 0; dd < GL_DCH; ++dd) {
-            if (d0 + dd >= D) continue;
+            if (d0e + dd >= D) continue;
             float r[8];
 #pragma unroll
             for (int g = 0; g < 8; ++g) r[g] = acc[g * GL_DCH + dd] * rdenom;
@@ -604,10 +636,10 @@ __global__ __launch_bounds__(256) void gl_aggregate_kernel(const void* __restric
                 for (int g = 0; g < 8; ++g) hv[g] = (_Float16)fminf(fmaxf(r[g], -65504.0f), 65504.0f);
                 sat::track(sat_amax, r[0], r[1], r[2], r[3]);
                 sat::track(sat_amax, r[4], r[5], r[6], r[7]);
-                *reinterpret_cast<h8*>(reinterpret_cast<_Float16*>(vol) + ((size_t)b * D * HW + (size_t)(unsigned)(d0 + dd) * HW + t.pc) * 8) = hv;
+                *reinterpret_cast<h8*>(reinterpret_cast<_Float16*>(vol) + ((size_t)b * D * HW + (size_t)(unsigned)(d0e + dd) * HW + pce) * 8) = hv;
                 continue;
             }
-            f32x4* o = reinterpret_cast<f32x4*>(vb + ((size_t)(unsigned)(d0 + dd) * HW + t.pc) * 8);
+            f32x4* o = reinterpret_cast<f32x4*>(vb + ((size_t)(unsigned)(d0e + dd) * HW + pce) * 8);
             if (split_out) {                                    // [hi x8 | lo x8] bf16: the same 32 bytes (conv_bf16x3_kernels.hip)
                 unsigned hw[4], lw[4];
 #pragma unroll

@@ -40,6 +40,18 @@ __device__ __forceinline__ float fma_mix_hi(unsigned h2, float w, float acc) {
 }  // namespace mvs
 #define MVS_FMA_MIX_LO(h2, w, acc) mvs::fma_mix_lo(h2, w, acc)
 #define MVS_FMA_MIX_HI(h2, w, acc) mvs::fma_mix_hi(h2, w, acc)
+// acc + a * b as ONE v_fmac_f32 the vectoriser cannot pair with a neighbour's into v_pk_fma_f32 (gather_lds.h, the four-wave forms: the packed
+// form keeps both operands' pairs alive together)
+namespace mvs {
+__device__ __forceinline__ float fmac_single(float a, float b, float acc) {
+    asm("v_fmac_f32 %0, %1, %2" : "+v"(acc) : "v"(a), "v"(b));
+    return acc;
+}
+}  // namespace mvs
+#define MVS_FMAC(a, b, acc) mvs::fmac_single(a, b, acc)
+#endif
+#ifndef MVS_FMAC      // a host emulator that brought its own v_fma_mix forms: the plain expression, contracted or not as every other `s += a * b` of its build
+#define MVS_FMAC(a, b, acc) ((acc) + (a) * (b))
 #endif
 
 namespace mvs {
