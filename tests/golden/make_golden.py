@@ -208,9 +208,9 @@ def pin_weights():
     for path in sorted(glob.glob(os.path.join(HERE, "*.npz"))):
         z = np.load(path, allow_pickle=False)
         for key in z.files:
-            if not key.endswith("keys"):
-                continue
             prefix = key[:-4]
+            if not key.endswith("keys") or not {prefix + "shapes", prefix + "seed"} <= set(z.files) or prefix + "sha256" in z.files:
+                continue                                    # not a manifest, or a fixture that carries its weights' hash itself
             keys = [str(k) for k in z[prefix + "keys"].tolist()]
             shapes = [tuple(json.loads(str(x))) for x in z[prefix + "shapes"].tolist()]
             sd = synth.seeded_state_dict(dict(zip(keys, shapes)), int(z[prefix + "seed"]))
@@ -405,6 +405,28 @@ def f7_transformer():
                                                    height_max=None, width_min=None, width_max=None, normalize=True)
     npz("f7_transformer.npz", x=x, K=K, hyp=hyp, depth_values=dv, position3d=pos, pe_range=torch.stack([hmin, hmax, wmin, wmax]),
         y=net(x, pos), y_nope=net(x, None), cfg=np.array(json.dumps(TRANSFORMER_CFG)), **wman)
+
+
+@torch.no_grad()
+def f31_transformer_batch():
+    """PureTransformerCostReg at B = 2 with the constructor's default cubic patch (down_rate = 4; 12 tokens per item): two intrinsics,
+    per-item hypotheses, get_position_3d's whole-batch ranges, the module with and without positions (tests/test_transformer.py)."""
+    from models.module import PureTransformerCostReg
+    from models.position_encoding import get_position_3d
+    g = torch.Generator().manual_seed(31)
+    cfg = dict(TRANSFORMER_CFG, down_rate=4)
+    net = PureTransformerCostReg(8, **cfg).eval()
+    wman = seed_weights(net, 310)
+    B, D, H, W = 2, 8, 8, 12
+    x = torch.randn(B, 8, D, H, W, generator=g)
+    K = torch.tensor([[[181.0, 0.0, 6.0], [0.0, 181.0, 4.0], [0.0, 0.0, 1.0]], [[150.0, 0.0, 5.5], [0.0, 163.0, 3.0], [0.0, 0.0, 1.0]]])
+    base = torch.stack([1.0 / torch.linspace(1 / 900.0, 1 / 430.0, D), 1.0 / torch.linspace(1 / 700.0, 1 / 500.0, D)])
+    hyp = (base[:, :, None, None] * (1 + 0.02 * torch.rand(B, D, H, W, generator=g))).contiguous()
+    dv = torch.arange(425.0, 2.65 * 191.5 + 425.0, 2.65)[None].repeat(B, 1)
+    pos, hmin, hmax, wmin, wmax = get_position_3d(B, H, W, K, hyp, depth_min=dv.min(), depth_max=dv.max(), height_min=None,
+                                                   height_max=None, width_min=None, width_max=None, normalize=True)
+    npz("f31_transformer_batch.npz", x=x, K=K, hyp=hyp, depth_values=dv, position3d=pos, pe_range=torch.stack([hmin, hmax, wmin, wmax]),
+        y=net(x, pos), y_nope=net(x, None), cfg=np.array(json.dumps(cfg)), **wman)
 
 
 @torch.no_grad()
@@ -762,4 +784,5 @@ if __name__ == "__main__":
     f19_position_encoding()
     f20_feature_heads()
     f21_dropin_network()
+    f31_transformer_batch()
     pin_weights()
