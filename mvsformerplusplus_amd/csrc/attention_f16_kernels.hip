@@ -37,14 +37,13 @@
 // Both are lane-linear: a wave's read is one contiguous 1-KiB run (conflict-free), and a block of KB keys is KB x 32 contiguous bytes of
 // each, so the LDS image is a straight copy made by LDS-DMA (global_load_lds_dwordx4: no VGPRs, no ds_write), double-buffered, one
 // barrier per block.
-#include "mvs_common.h"
+#include "split_format.h"
 #include "attention_f16.h"
 
 namespace mvs {
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 namespace {
 

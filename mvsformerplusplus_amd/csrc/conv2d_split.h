@@ -167,11 +167,7 @@ __global__ __launch_bounds__(256) void conv2d_split_kernel(Src src, const void* 
 #pragma unroll
             for (int mb = 0; mb < MREP; ++mb)
 #pragma unroll
-                for (int nb = 0; nb < NREP; ++nb) {
-                    acc[mb][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[mb], bh[nb], acc[mb][nb], 0, 0, 0);
-                    acc[mb][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[mb], bl[nb], acc[mb][nb], 0, 0, 0);
-                    acc[mb][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[mb], bh[nb], acc[mb][nb], 0, 0, 0);
-                }
+                for (int nb = 0; nb < NREP; ++nb) acc[mb][nb] = mfma3_bf16(ah[mb], al[mb], bh[nb], bl[nb], acc[mb][nb]);
         }
     }
 

@@ -81,6 +81,7 @@ __device__ __forceinline__ void bf_mfma_step(const bf16x8* ah, const bf16x8* al,
                 acc[mb][nb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, ah[mb]), __builtin_bit_cast(f16x8, bh[nb]), acc[mb][nb], 0, 0, 0);
         return;
     }
+    // term-major form of mfma3_bf16: the same three terms in the same order per accumulator (the contract at the top of split_format.h)
 #pragma unroll
     for (int mb = 0; mb < MREP; ++mb)
 #pragma unroll
@@ -850,7 +851,8 @@ __device__ __forceinline__ void bfdf_load_x(const char* px, bf16x8* bh, bf16x8* 
     }
 }
 // one MFMA term of step U for every class that uses the position, class-outer: consecutive MFMAs hit different accumulators
-// TERM (bf_mfma_step's order per accumulator): fp16 0 = w_lo . x, 1 = w_hi . x; split bf16 0 = lo . hi, 1 = hi . lo, 2 = hi . hi
+// TERM (bf_mfma_step's order per accumulator): fp16 0 = w_lo . x, 1 = w_hi . x; split bf16 0 = lo . hi, 1 = hi . lo, 2 = hi . hi (the contract at the
+// top of split_format.h)
 template <class Cfg, int U, int TERM, int CLS>
 __device__ __forceinline__ void bfdf_mfma(const bf16x8* ah, const bf16x8* al, const bf16x8* bh, const bf16x8* bl, f32x4 (*acc)[Cfg::NREP]) {
     using P = BfDeconvF<Cfg>;

@@ -120,11 +120,7 @@ __device__ __forceinline__ void ft_gemm(const bf16x8* __restrict__ wl, int s0, i
             const bf16x8 ah = wl[(size_t)((((s0 + s) * MTOT + mb0 + mb) * 2 + 0) * 64)];
             const bf16x8 al = wl[(size_t)((((s0 + s) * MTOT + mb0 + mb) * 2 + 1) * 64)];
 #pragma unroll
-            for (int nb = 0; nb < FT_NREP; ++nb) {
-                acc[mb][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bh[s][nb], acc[mb][nb], 0, 0, 0);
-                acc[mb][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bl[s][nb], acc[mb][nb], 0, 0, 0);
-                acc[mb][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bh[s][nb], acc[mb][nb], 0, 0, 0);
-            }
+            for (int nb = 0; nb < FT_NREP; ++nb) acc[mb][nb] = mfma3_bf16(ah, al, bh[s][nb], bl[s][nb], acc[mb][nb]);
         }
 }
 
@@ -135,9 +131,6 @@ __device__ __forceinline__ void ft_zero(f32x4 (&acc)[MREP][FT_NREP]) {
 #pragma unroll
         for (int nb = 0; nb < FT_NREP; ++nb) acc[mb][nb] = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
 }
-
-__device__ __forceinline__ float ft_elu1(float t) { return t > 0.0f ? t + 1.0f : expf(t); }                      // elu(t) + 1
-__device__ __forceinline__ float ft_gelu(float t) { return 0.5f * t * (1.0f + erff(t * 0.70710678118654752440f)); }
 
 struct FmtBlockArgs {
     const float* x;          // [N, 64, n]
@@ -171,7 +164,7 @@ __global__ __launch_bounds__(256) void fmt_block_kernel(FmtBlockArgs a) {
 #pragma unroll
         for (int mb = 0; mb < 4; ++mb)
 #pragma unroll
-            for (int k = 0; k < 4; ++k) acc[mb][nb][k] = ft_elu1(acc[mb][nb][k]);
+            for (int k = 0; k < 4; ++k) acc[mb][nb][k] = elu1(acc[mb][nb][k]);
         ft_operand(acc[0][nb], acc[1][nb], bh[0][nb], bl[0][nb]);
         ft_operand(acc[2][nb], acc[3][nb], bh[1][nb], bl[1][nb]);
     }
@@ -221,7 +214,7 @@ __global__ __launch_bounds__(256) void fmt_block_kernel(FmtBlockArgs a) {
 #pragma unroll
             for (int nb = 0; nb < FT_NREP; ++nb)
 #pragma unroll
-                for (int k = 0; k < 4; ++k) hd[mb][nb][k] = ft_gelu(hd[mb][nb][k] + bb[k]);
+                for (int k = 0; k < 4; ++k) hd[mb][nb][k] = gelu_erf(hd[mb][nb][k] + bb[k]);
         }
 #pragma unroll
         for (int nb = 0; nb < FT_NREP; ++nb) {
@@ -283,9 +276,7 @@ __global__ __launch_bounds__(256) void fmt_kv_partial_kernel(const float* __rest
 #pragma unroll
                 for (int nb = 0; nb < FT_NREP; ++nb) {
                     f32x4& d = cb < 4 ? kacc[cb & 3][nb] : vacc[cb & 3][nb];
-                    d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(tl[s][nb], wh, d, 0, 0, 0);
-                    d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(th[s][nb], wo, d, 0, 0, 0);
-                    d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(th[s][nb], wh, d, 0, 0, 0);
+                    d = mfma3_bf16(th[s][nb], tl[s][nb], wh, wo, d);
                 }
             }
         // KV_h[d][m] += sum over four tokens (one per lane group) of k[token][d] v[token][m], exact fp32 products
@@ -296,7 +287,7 @@ __global__ __launch_bounds__(256) void fmt_kv_partial_kernel(const float* __rest
                 const bool ok = t0 + nb * 16 + 4 * g + kk < ntok;
 #pragma unroll
                 for (int h = 0; h < 4; ++h) {
-                    const float kval = ok ? ft_elu1(kacc[h][nb][kk]) : 0.0f;
+                    const float kval = ok ? elu1(kacc[h][nb][kk]) : 0.0f;
                     ks[h] += kval;
                     kv[h] = __builtin_amdgcn_mfma_f32_16x16x4f32(kval, vacc[h][nb][kk], kv[h], 0, 0, 0);
                 }
@@ -343,7 +334,7 @@ __global__ __launch_bounds__(256) void fmt_kv_reduce_kernel(const float* __restr
         else v[e] = (j & 3) == hc ? lds[hc * 16 + d] : 0.0f;
     }
     bf16x8 hi, lo;
-    split8(make_float4(v[0], v[1], v[2], v[3]), make_float4(v[4], v[5], v[6], v[7]), hi, lo);
+    split8(v, hi, lo);
     bf16x8* o = kvop + (size_t)n * FT_KVOP + (size_t)(s * 5 + mb) * 2 * 64 + lane;
     o[0] = hi;
     o[64] = lo;

@@ -25,6 +25,7 @@
 // hypotheses D*HW*4 + entropy n_views*HW*4; pass 2 = the same inputs + visibility + G*D*HW*4 volume write.
 #pragma once
 #include "gather_common.h"
+#include "volume_format.h"
 
 namespace mvs {
 
@@ -622,7 +623,7 @@ __global__ __launch_bounds__(256) void gl_aggregate_kernel(const void* __restric
     unsigned pce = t.pc;
     if constexpr (LEAN) asm volatile("" : "+" MVS_OPAQUE_REG(d0e), "+" MVS_OPAQUE_REG(pce));
     if (active) {
-        float* vb = vol + (size_t)b * D * HW * 8;
+        float* vb = vol + (size_t)b * D * HW * 8;                // the batch element's 32-byte voxels
 #pragma unroll
         for (int dd = 0; dd < GL_DCH; ++dd) {
             if (d0e + dd >= D) continue;
@@ -630,31 +631,12 @@ __global__ __launch_bounds__(256) void gl_aggregate_kernel(const void* __restric
 #pragma unroll
             for (int g = 0; g < 8; ++g) r[g] = acc[g * GL_DCH + dd] * rdenom;
             if (f16_out) {
-                typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-                h8 hv;
-#pragma unroll
-                for (int g = 0; g < 8; ++g) hv[g] = (_Float16)fminf(fmaxf(r[g], -65504.0f), 65504.0f);
-                sat::track(sat_amax, r[0], r[1], r[2], r[3]);
-                sat::track(sat_amax, r[4], r[5], r[6], r[7]);
-                *reinterpret_cast<h8*>(reinterpret_cast<_Float16*>(vol) + ((size_t)b * D * HW + (size_t)(unsigned)(d0e + dd) * HW + pce) * 8) = hv;
+                volume_store8<MVS_VOLUME_F16>(vol, (size_t)b * D * HW + (size_t)(unsigned)(d0e + dd) * HW + pce, r, sat_amax);
                 continue;
             }
-            f32x4* o = reinterpret_cast<f32x4*>(vb + ((size_t)(unsigned)(d0e + dd) * HW + pce) * 8);
-            if (split_out) {                                    // [hi x8 | lo x8] bf16: the same 32 bytes (conv_bf16x3_kernels.hip)
-                unsigned hw[4], lw[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const uint16_t h0 = from_f32<uint16_t>(r[2 * j]), h1 = from_f32<uint16_t>(r[2 * j + 1]);
-                    const uint16_t l0 = from_f32<uint16_t>(r[2 * j] - to_f32(h0)), l1 = from_f32<uint16_t>(r[2 * j + 1] - to_f32(h1));
-                    hw[j] = (unsigned)h0 | ((unsigned)h1 << 16);
-                    lw[j] = (unsigned)l0 | ((unsigned)l1 << 16);
-                }
-                o[0] = f32x4{__builtin_bit_cast(float, hw[0]), __builtin_bit_cast(float, hw[1]), __builtin_bit_cast(float, hw[2]), __builtin_bit_cast(float, hw[3])};
-                o[1] = f32x4{__builtin_bit_cast(float, lw[0]), __builtin_bit_cast(float, lw[1]), __builtin_bit_cast(float, lw[2]), __builtin_bit_cast(float, lw[3])};
-                continue;
-            }
-            o[0] = f32x4{r[0], r[1], r[2], r[3]};
-            o[1] = f32x4{r[4], r[5], r[6], r[7]};
+            const size_t vox = (size_t)(unsigned)(d0e + dd) * HW + pce;
+            if (split_out) volume_store8<MVS_VOLUME_SPLIT>(vb, vox, r, sat_amax);
+            else volume_store8<MVS_VOLUME_F32>(vb, vox, r, sat_amax);
         }
     }
     if (f16_out) sat::commit(sat_amax);

@@ -58,31 +58,7 @@ __global__ __launch_bounds__(256) void corr_aggregate_kernel(const void* __restr
 #pragma unroll
         for (int g = 0; g < 8; ++g) r[g] = acc[dd][g] * rdenom;
         const size_t vox = (size_t)b * D * HW + (size_t)(unsigned)(d0 + dd) * HW + p;
-        if constexpr (FMT == MVS_VOLUME_F16) {
-            h8 hv;
-#pragma unroll
-            for (int g = 0; g < 8; ++g) hv[g] = (_Float16)fminf(fmaxf(r[g], -65504.0f), 65504.0f);
-            sat::track(sat_amax, r[0], r[1], r[2], r[3]);
-            sat::track(sat_amax, r[4], r[5], r[6], r[7]);
-            reinterpret_cast<h8*>(vol)[vox] = hv;
-        } else {
-            f32x4* o = reinterpret_cast<f32x4*>(vol) + vox * 2;
-            if constexpr (FMT == MVS_VOLUME_SPLIT) {             // [hi x8 | lo x8] bf16: the same 32 bytes (conv_bf16x3_kernels.hip)
-                unsigned hw[4], lw[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const uint16_t h0 = from_f32<uint16_t>(r[2 * j]), h1 = from_f32<uint16_t>(r[2 * j + 1]);
-                    const uint16_t l0 = from_f32<uint16_t>(r[2 * j] - to_f32(h0)), l1 = from_f32<uint16_t>(r[2 * j + 1] - to_f32(h1));
-                    hw[j] = (unsigned)h0 | ((unsigned)h1 << 16);
-                    lw[j] = (unsigned)l0 | ((unsigned)l1 << 16);
-                }
-                o[0] = f32x4{__builtin_bit_cast(float, hw[0]), __builtin_bit_cast(float, hw[1]), __builtin_bit_cast(float, hw[2]), __builtin_bit_cast(float, hw[3])};
-                o[1] = f32x4{__builtin_bit_cast(float, lw[0]), __builtin_bit_cast(float, lw[1]), __builtin_bit_cast(float, lw[2]), __builtin_bit_cast(float, lw[3])};
-            } else {
-                o[0] = f32x4{r[0], r[1], r[2], r[3]};
-                o[1] = f32x4{r[4], r[5], r[6], r[7]};
-            }
-        }
+        volume_store8<FMT>(vol, vox, r, sat_amax);
     }
     if constexpr (FMT == MVS_VOLUME_F16) sat::commit(sat_amax);
 }

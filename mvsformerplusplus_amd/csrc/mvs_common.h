@@ -115,6 +115,10 @@ template <> __device__ __forceinline__ uint16_t from_f32<uint16_t>(float v) {   
     return (uint16_t)((c.u + 0x7fffu + ((c.u >> 16) & 1u)) >> 16);
 }
 
+// activations shared by the FMT and ViT-decoder kernels
+__device__ __forceinline__ float elu1(float t) { return t > 0.0f ? t + 1.0f : expf(t); }                          // elu(t) + 1
+__device__ __forceinline__ float gelu_erf(float t) { return 0.5f * t * (1.0f + erff(t * 0.70710678118654752440f)); }
+
 // 3x4 homography of one source view: p = R * [x, y, 1] * depth + t   (warping.py:80-92)
 struct Homography {
     float r[9];

@@ -1,20 +1,58 @@
-// The split activation format (MVS_PREC_BF16X3_SPLIT) and the hi / lo split helpers of the split-bf16 convolution kernels
-// (conv_bf16x3_kernels.hip).
+// The split-bf16 number format: the ONE definition of the fp32-equivalent arithmetic of every bf16 MFMA kernel of this library.
+//
+//   * The split.  A fp32 value x is carried as two bf16 values, hi = bf16(x) and lo = bf16(x - hi), both rounded to nearest even
+//     (the subtraction is exact in fp32); hi + lo carries 16 significand bits of x.
+//   * The product.  a . b is three MFMA terms accumulated in fp32 in THIS order: a_lo . b_hi, a_hi . b_lo, a_hi . b_hi; the fourth,
+//     a_lo . b_lo (2^-16 of the product), is dropped.  The order is part of the arithmetic: fp32 accumulation does not commute.
+//     mfma3_bf16 is the per-accumulator form; kernels that run the terms as three passes over their accumulators (term-major, for
+//     the MFMA dependency distance) keep the same order and say so where they do.
+//   * Two roundings, one result.  split_bf16 rounds with the hardware convert (v_cvt_pk_bf16_f32), split_bf16_bits with integer
+//     arithmetic (from_f32<uint16_t>, mvs_common.h) where the halves are wanted as bit patterns.  Both are round-to-nearest-even and
+//     give the same (hi, lo) bits for every fp32 input that is not a NaN (tests/test_split_format.py holds them to that).
+//   * Host mirrors: packing.split_bf16 (packing.py; ops.to_split and every pack_* function build on it); the fp64 models of the
+//     tests restate the format independently (tests/transformer_ref.py: split_operands).
+// Also here: the split ACTIVATION format (MVS_PREC_BF16X3_SPLIT) of the split-bf16 convolution kernels (conv_bf16x3_kernels.hip).
 #pragma once
 #include "mvs_common.h"
 
 namespace mvs {
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 
+__device__ __forceinline__ void split_bf16(float x, __bf16& hi, __bf16& lo) {
+    hi = (__bf16)x;                                    // round to nearest even (v_cvt_pk_bf16_f32)
+    lo = (__bf16)(x - (float)hi);
+}
+// the same split on bf16 bit patterns, rounded by integer arithmetic
+__device__ __forceinline__ void split_bf16_bits(float x, uint16_t& hi, uint16_t& lo) {
+    hi = from_f32<uint16_t>(x);
+    lo = from_f32<uint16_t>(x - to_f32(hi));
+}
+
+// the vector forms hand split_bf16 the vectors' ELEMENTS (a reference cannot bind to hi[j]): element j of hi is written before lo's is
+// computed, the order of every hand-written site these replace - with copies through temporaries the scheduler moved instructions in
+// five units (profiles/split_single_source_isa.txt)
+__device__ __forceinline__ void split4(const float (&x)[4], bf16x4& hi, bf16x4& lo) {
+    __bf16 *h = reinterpret_cast<__bf16*>(&hi), *l = reinterpret_cast<__bf16*>(&lo);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) split_bf16(x[j], h[j], l[j]);
+}
+__device__ __forceinline__ void split8(const float (&x)[8], bf16x8& hi, bf16x8& lo) {
+    __bf16 *h = reinterpret_cast<__bf16*>(&hi), *l = reinterpret_cast<__bf16*>(&lo);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) split_bf16(x[j], h[j], l[j]);
+}
 __device__ __forceinline__ void split8(const float4& u, const float4& v, bf16x8& hi, bf16x8& lo) {
     const float x[8] = {u.x, u.y, u.z, u.w, v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const __bf16 h = (__bf16)x[j];                 // round to nearest even (v_cvt_pk_bf16_f32)
-        hi[j] = h;
-        lo[j] = (__bf16)(x[j] - (float)h);
-    }
+    split8(x, hi, lo);
+}
+
+// acc += a . b, the three-term product (see the top of this file for the order)
+__device__ __forceinline__ f32x4 mfma3_bf16(const bf16x8& ah, const bf16x8& al, const bf16x8& bh, const bf16x8& bl, f32x4 acc) {
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bh, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bl, acc, 0, 0, 0);
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bh, acc, 0, 0, 0);
 }
 
 // ---- the split activation format (MVS_PREC_BF16X3_SPLIT) ---------------------------------------------------------------
@@ -40,10 +78,7 @@ __device__ __forceinline__ void split_store_quad(float* octet, int g, const floa
     const float x[4] = {v.x, v.y, v.z, v.w};
     __bf16 h[4], l[4];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        h[j] = (__bf16)x[j];
-        l[j] = (__bf16)(x[j] - (float)h[j]);
-    }
+    for (int j = 0; j < 4; ++j) split_bf16(x[j], h[j], l[j]);
     unsigned h0 = pack_bf16x2(h[0], h[1]), h1 = pack_bf16x2(h[2], h[3]), l0 = pack_bf16x2(l[0], l[1]), l1 = pack_bf16x2(l[2], l[3]);
     // rows 1, 3 of the first operand <-> rows 0, 2 of the second: even rows end up with {own hi, partner's hi}, odd rows with
     // {partner's lo, own lo}

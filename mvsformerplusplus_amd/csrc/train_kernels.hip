@@ -9,6 +9,7 @@
 //
 // Everything is channel-last fp32 [N voxels][C], C in {8, 16, 32, 64}.
 #include "conv_cfg.h"
+#include "split_format.h"
 
 namespace mvs {
 
@@ -285,12 +286,6 @@ __global__ __launch_bounds__(256) void conv3d_wgrad_kernel(const float* __restri
 //          tflip = 1: W'[co][ci][tap] = W[ci][co][ntap - 1 - tap]  (the data-gradient form of a stride-1 convolution)
 //   deconv per parity class (pair of classes for Cout = 8), packing.pack_deconv_weights_bf16x3
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void store_split_bf16(float v, uint16_t* hi, uint16_t* lo) {
-    const uint16_t h = from_f32<uint16_t>(v);
-    *hi = h;
-    *lo = from_f32<uint16_t>(v - to_f32(h));
-}
-
 __global__ __launch_bounds__(256) void pack_conv_bf16x3_kernel(const float* __restrict__ w, uint16_t* __restrict__ out, int cout, int cin, int ntap,
                                                                int ch, int tflip, int mrep, int nstep, int total) {
     const int idx = (int)blockIdx.x * 256 + (int)threadIdx.x;
@@ -305,7 +300,7 @@ __global__ __launch_bounds__(256) void pack_conv_bf16x3_kernel(const float* __re
     float v = 0.0f;
     if (tap < ntap && co < cout) v = tflip ? w[((size_t)ci * cout + co) * ntap + (ntap - 1 - tap)] : w[((size_t)co * cin + ci) * ntap + tap];
     uint16_t* base = out + (((size_t)(pass * nstep + step) * mrep + mb) * 2) * 512 + (g * 16 + j) * 8 + e;
-    store_split_bf16(v, base, base + 512);
+    split_bf16_bits(v, base[0], base[512]);
 }
 
 struct DeconvPackPlan {
@@ -341,7 +336,7 @@ __global__ __launch_bounds__(256) void pack_deconv_bf16x3_kernel(const float* __
         }
     }
     uint16_t* base = out + (((size_t)gstep * mrep + mb) * 2) * 512 + (g * 16 + j) * 8 + e;
-    store_split_bf16(v, base, base + 512);
+    split_bf16_bits(v, base[0], base[512]);
 }
 
 // d gamma / d beta as fp32 from the (per group) backward sums

@@ -18,24 +18,12 @@
 //   * pos3d_*             normalised frustum coordinates of every hypothesis voxel (two-pass min/max + write).
 #include <stdlib.h>
 
-#include "mvs_common.h"
+#include "split_format.h"
 #include "attention_f16.h"
 
 namespace mvs {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-
 namespace {
-
-__device__ __forceinline__ void tr_split8(const float* x, bf16x8& hi, bf16x8& lo) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const __bf16 h = (__bf16)x[e];
-        hi[e] = h;
-        lo[e] = (__bf16)(x[e] - (float)h);
-    }
-}
 
 __device__ __forceinline__ float wave_sum_groups(float v) {      // sum over the four lane groups g = lane >> 4
     v += __shfl_xor(v, 16);
@@ -101,7 +89,7 @@ __global__ __launch_bounds__(256) void tr_gemm_kernel(const TrArgs a) {
                 v[0] = u.x; v[1] = u.y; v[2] = u.z; v[3] = u.w; v[4] = w.x; v[5] = w.y; v[6] = w.z; v[7] = w.w;
             }
             bf16x8 hi, lo;
-            tr_split8(v, hi, lo);
+            split8(v, hi, lo);
             *reinterpret_cast<bf16x8*>(ldsb + tk * SB + oc * 32) = hi;
             *reinterpret_cast<bf16x8*>(ldsb + tk * SB + oc * 32 + 16) = lo;
         }
@@ -146,7 +134,7 @@ __global__ __launch_bounds__(256) void tr_gemm_kernel(const TrArgs a) {
                 }
             }
             bf16x8 hi, lo;
-            tr_split8(v, hi, lo);
+            split8(v, hi, lo);
             *reinterpret_cast<bf16x8*>(ldsb + tk * SB + pv * 32) = hi;
             *reinterpret_cast<bf16x8*>(ldsb + tk * SB + pv * 32 + 16) = lo;
         }
@@ -173,6 +161,7 @@ __global__ __launch_bounds__(256) void tr_gemm_kernel(const TrArgs a) {
                 ah[mb] = wq[(size_t)((t * MT + mc + mb) * 2) * 64];
                 al[mb] = wq[(size_t)((t * MT + mc + mb) * 2 + 1) * 64];
             }
+            // term-major form of mfma3_bf16: lo . hi, hi . lo, hi . hi per accumulator (the contract at the top of split_format.h)
 #pragma unroll
             for (int mb = 0; mb < 4; ++mb) acc[mb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[mb], bh, acc[mb], 0, 0, 0);
 #pragma unroll
@@ -237,12 +226,7 @@ __global__ __launch_bounds__(256) void tr_gemm_kernel(const TrArgs a) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) v[r] = which == 0 ? acc[mb][r] * a.qscale : acc[mb][r];
                 bf16x4 hi, lo;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const __bf16 h = (__bf16)v[r];
-                    hi[r] = h;
-                    lo[r] = (__bf16)(v[r] - (float)h);
-                }
+                split4(v, hi, lo);
                 if (which < 2) {
                     __bf16* dst = (which == 0 ? a.q : a.k) + (hb * a.npad + tok) * 32 + 4 * g;
                     *reinterpret_cast<bf16x4*>(dst) = hi;
@@ -431,7 +415,7 @@ __global__ __launch_bounds__(256) void tr_attention_kernel(const __bf16* __restr
 #pragma unroll
                     for (int e = 0; e < 8; ++e) ph[e] = (__bf16)p[e];
                 } else {
-                    tr_split8(p, ph, pl);
+                    split8(p, ph, pl);
                 }
                 o[qt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vlo, ph, o[qt], 0, 0, 0);
                 if (!P1) o[qt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vh, pl, o[qt], 0, 0, 0);

@@ -19,12 +19,9 @@
 // x0 - 1 + c (c = 0..63); an MFMA tile is 16 consecutive columns of one row, wave w owns tile w.
 // Zero padding follows the reference exactly: every layer's OUTPUT is forced to zero outside the image (the next
 // Conv2d pads its input with zeros there), which is not the same as convolving zero-padded entropy.
-#include "mvs_common.h"
+#include "split_format.h"
 
 namespace mvs {
-
-typedef __bf16 vs_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 vs_bf16x4 __attribute__((ext_vector_type(4)));
 
 constexpr int VS_TW = 60;                 // output columns per strip
 constexpr int VS_P = 64;                  // columns per ring row
@@ -71,15 +68,6 @@ __device__ __forceinline__ vs_f16x4 vs_cvt4(const float* v) {
     return __builtin_convertvector((vs_f32x4){v[0], v[1], v[2], v[3]}, vs_f16x4);
 }
 
-__device__ __forceinline__ void vs_split4(const float* v, vs_bf16x4& hi, vs_bf16x4& lo) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const __bf16 h = (__bf16)v[j];
-        hi[j] = h;
-        lo[j] = (__bf16)(v[j] - (float)h);
-    }
-}
-
 // B-operand offset of contraction step t: lane group g>>1 picks the first or second tap of the step (two taps x 16 channels =
 // 32 k-values).  SLOT0 = ring slot of tap row kh = 0 (compile-time: the row loop dispatches on i & 3).
 template <int SLOT0, int POSB>
@@ -90,24 +78,24 @@ __device__ __forceinline__ int vs_step_off(int laneoff, int tapsel, int t) {
     return laneoff + (tapsel ? offB : offA);
 }
 
-struct VsOperand { vs_bf16x8 h, l; };
+struct VsOperand { bf16x8 h, l; };
 template <bool F16>
 __device__ __forceinline__ VsOperand vs_load(const char* p) {
     VsOperand o;
-    o.h = *reinterpret_cast<const vs_bf16x8*>(p);
-    if constexpr (!F16) o.l = *reinterpret_cast<const vs_bf16x8*>(p + 16);
+    o.h = *reinterpret_cast<const bf16x8*>(p);
+    if constexpr (!F16) o.l = *reinterpret_cast<const bf16x8*>(p + 16);
     else o.l = o.h;
     return o;
 }
 
 // one contraction step of one layer: the split-bf16 three-term product or the fp16 two-term product (weights hi + lo)
 template <bool F16>
-__device__ __forceinline__ f32x4 vs_mfma_lo(const vs_bf16x8& wl, const VsOperand& x, f32x4 a) {
+__device__ __forceinline__ f32x4 vs_mfma_lo(const bf16x8& wl, const VsOperand& x, f32x4 a) {
     if constexpr (F16) return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(vs_f16x8, wl), __builtin_bit_cast(vs_f16x8, x.h), a, 0, 0, 0);
     else return __builtin_amdgcn_mfma_f32_16x16x32_bf16(wl, x.h, a, 0, 0, 0);
 }
 template <bool F16>
-__device__ __forceinline__ f32x4 vs_mfma_hi(const vs_bf16x8& wh, const VsOperand& x, f32x4 a) {
+__device__ __forceinline__ f32x4 vs_mfma_hi(const bf16x8& wh, const VsOperand& x, f32x4 a) {
     if constexpr (F16) return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(vs_f16x8, wh), __builtin_bit_cast(vs_f16x8, x.h), a, 0, 0, 0);
     else return __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh, x.h, a, 0, 0, 0);
 }
@@ -118,7 +106,7 @@ __device__ __forceinline__ f32x4 vs_mfma_hi(const vs_bf16x8& wh, const VsOperand
 // scripts/study_weight_precision.py, "visibility CNN one term")
 // `init`: the layer's bias, which rides in the first MFMA's accumulator input instead of four v_add_f32 in the epilogue
 template <int SLOT0, bool F16, bool ONE = false>
-__device__ __forceinline__ f32x4 vs_layer_row(const char* lds_layer, int laneoff, int tapsel, const vs_bf16x8* wh, const vs_bf16x8* wl, f32x4 init) {
+__device__ __forceinline__ f32x4 vs_layer_row(const char* lds_layer, int laneoff, int tapsel, const bf16x8* wh, const bf16x8* wl, f32x4 init) {
     constexpr int POSB = VsL<F16>::POSB;
     f32x4 a0 = {0.0f, 0.0f, 0.0f, 0.0f}, a1 = a0, a2 = init;
     VsOperand cur = vs_load<F16>(lds_layer + vs_step_off<SLOT0, POSB>(laneoff, tapsel, 0));
@@ -139,8 +127,8 @@ __device__ __forceinline__ f32x4 vs_layer_row(const char* lds_layer, int laneoff
 // reads in flight under six MFMAs; one accumulator per layer - the two chains alternate, so a chain's next link is issued two
 // MFMAs (32 cycles) after the previous one
 template <int SLOT2, int SLOT3, bool F16, bool ONE = false>
-__device__ __forceinline__ void vs_two_layer_rows(const char* lds1, const char* lds2, int laneoff, int tapsel, const vs_bf16x8* w2h,
-                                                  const vs_bf16x8* w2l, const vs_bf16x8* w3h, const vs_bf16x8* w3l, f32x4& out2, f32x4& out3) {
+__device__ __forceinline__ void vs_two_layer_rows(const char* lds1, const char* lds2, int laneoff, int tapsel, const bf16x8* w2h,
+                                                  const bf16x8* w2l, const bf16x8* w3h, const bf16x8* w3l, f32x4& out2, f32x4& out3) {
     constexpr int POSB = VsL<F16>::POSB;
     f32x4 a = out2, c = out3;                                   // in: the layers' biases (accumulator init), out: the rows
     VsOperand cb = vs_load<F16>(lds1 + vs_step_off<SLOT2, POSB>(laneoff, tapsel, 0));
@@ -191,10 +179,10 @@ __global__ __launch_bounds__(256) void vis_cnn_kernel(const float* __restrict__ 
     float* vo = vis + (size_t)blockIdx.z * H * W;
 
     // ---- register-resident parameters ----
-    vs_bf16x8 w2h[5], w2l[5], w3h[5], w3l[5];
+    bf16x8 w2h[5], w2l[5], w3h[5], w3l[5];
     {
-        const vs_bf16x8* q2 = reinterpret_cast<const vs_bf16x8*>(wp2) + lane;
-        const vs_bf16x8* q3 = reinterpret_cast<const vs_bf16x8*>(wp3) + lane;
+        const bf16x8* q2 = reinterpret_cast<const bf16x8*>(wp2) + lane;
+        const bf16x8* q3 = reinterpret_cast<const bf16x8*>(wp3) + lane;
 #pragma unroll
         for (int t = 0; t < 5; ++t) {
             w2h[t] = q2[(t * 2) * 64]; w2l[t] = q2[(t * 2 + 1) * 64];
@@ -317,10 +305,10 @@ __global__ __launch_bounds__(256) void vis_cnn_kernel(const float* __restrict__ 
             if constexpr (F16) {
                 *reinterpret_cast<vs_f16x4*>(p) = vs_mask4(vs_cvt4(a), in);
             } else {
-                vs_bf16x4 hi, lo;
-                vs_split4(a, hi, lo);
-                *reinterpret_cast<vs_bf16x4*>(p) = hi;
-                *reinterpret_cast<vs_bf16x4*>(p + 16) = lo;
+                bf16x4 hi, lo;
+                split4(a, hi, lo);
+                *reinterpret_cast<bf16x4*>(p) = hi;
+                *reinterpret_cast<bf16x4*>(p + 16) = lo;
             }
         }
         // ---- B: layer-2 row i-2 from layer-1 rows i-3 .. i-1;  C: layer-3 row i-4 from layer-2 rows i-5 .. i-3 ----
@@ -340,10 +328,10 @@ __global__ __launch_bounds__(256) void vis_cnn_kernel(const float* __restrict__ 
             if constexpr (F16) {
                 *reinterpret_cast<vs_f16x4*>(p) = vs_mask4(vs_cvt4(v), in);
             } else {
-                vs_bf16x4 hi, lo;
-                vs_split4(v, hi, lo);
-                *reinterpret_cast<vs_bf16x4*>(p) = hi;
-                *reinterpret_cast<vs_bf16x4*>(p + 16) = lo;
+                bf16x4 hi, lo;
+                split4(v, hi, lo);
+                *reinterpret_cast<bf16x4*>(p) = hi;
+                *reinterpret_cast<bf16x4*>(p + 16) = lo;
             }
         }
         if (doC) {                                                  // 1x1 + sigmoid

@@ -30,12 +30,6 @@ struct VaArgs {
     int ntok, npad;
 };
 
-__device__ __forceinline__ f32x4 va_mfma3(const bf16x8& ah, const bf16x8& al, const bf16x8& bh, const bf16x8& bl, f32x4 acc) {
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bh, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bl, acc, 0, 0, 0);
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bh, acc, 0, 0, 0);
-}
-
 __global__ __launch_bounds__(256) void va_attention_kernel(VaArgs a) {
     __shared__ float4 lk4[512], lv4[512];
     bf16x8* lk = reinterpret_cast<bf16x8*>(lk4);                   // [key tile 2][k-step 2][hi|lo][64 lanes]
@@ -103,7 +97,7 @@ __global__ __launch_bounds__(256) void va_attention_kernel(VaArgs a) {
             for (int j = 0; j < 2; ++j) {
                 sc[j] = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
-                for (int s = 0; s < 2; ++s) sc[j] = va_mfma3(kh[j][s], kl[j][s], qh[t][s], ql[t][s], sc[j]);
+                for (int s = 0; s < 2; ++s) sc[j] = mfma3_bf16(kh[j][s], kl[j][s], qh[t][s], ql[t][s], sc[j]);
             }
             if (ragged) {
 #pragma unroll
@@ -125,9 +119,10 @@ __global__ __launch_bounds__(256) void va_attention_kernel(VaArgs a) {
                 for (int r = 0; r < 4; ++r) {
                     const float p = __builtin_amdgcn_exp2f(sc[j][r] - mn);
                     sum += p;
-                    const __bf16 h = (__bf16)p;
+                    __bf16 h, lo;
+                    split_bf16(p, h, lo);
                     ph[t][4 * j + r] = h;
-                    pl[t][4 * j + r] = (__bf16)(p - (float)h);
+                    pl[t][4 * j + r] = lo;
                 }
             l[t] = fmaf(l[t], alpha, sum);
 #pragma unroll
@@ -139,7 +134,7 @@ __global__ __launch_bounds__(256) void va_attention_kernel(VaArgs a) {
         for (int db = 0; db < 4; ++db) {
             const bf16x8 vh = lv[(db * 2 + 0) * 64 + lane], vl = lv[(db * 2 + 1) * 64 + lane];
 #pragma unroll
-            for (int t = 0; t < VA_NQ; ++t) o[t][db] = va_mfma3(vh, vl, ph[t], pl[t], o[t][db]);
+            for (int t = 0; t < VA_NQ; ++t) o[t][db] = mfma3_bf16(vh, vl, ph[t], pl[t], o[t][db]);
         }
     }
     if (!active) return;

@@ -10,10 +10,7 @@ namespace mvs {
 __device__ __forceinline__ void vd_store_split4(bf16x8* buf, int steps, int orow, int ch, const float (&v)[4]) {
     __bf16 h[4], l[4];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        h[j] = (__bf16)v[j];
-        l[j] = (__bf16)(v[j] - (float)h[j]);
-    }
+    for (int j = 0; j < 4; ++j) split_bf16(v[j], h[j], l[j]);
     char* dst = reinterpret_cast<char*>(buf + (((size_t)(orow >> 4) * steps + (ch >> 5)) * 2) * 64 + ((ch >> 3) & 3) * 16 + (orow & 15)) + (ch & 4) * 2;
     *reinterpret_cast<u32x2*>(dst) = (u32x2){pack_bf16x2(h[0], h[1]), pack_bf16x2(h[2], h[3])};
     *reinterpret_cast<u32x2*>(dst + 64 * 16) = (u32x2){pack_bf16x2(l[0], l[1]), pack_bf16x2(l[2], l[3])};
@@ -33,10 +30,11 @@ __device__ __forceinline__ void vit_store_vt4(bf16x8* sec, int t, int d, const f
     const int r = t & 31, e = ((r >> 4) << 2) | (r & 3), gg = (r >> 2) & 3;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-        const __bf16 h = (__bf16)v[j];
+        __bf16 h, l;
+        split_bf16(v[j], h, l);
         __bf16* dst = reinterpret_cast<__bf16*>(sec + (((size_t)(t >> 5) * 4 + ((d + j) >> 4)) * 2) * 64 + gg * 16 + ((d + j) & 15)) + e;
         dst[0] = h;
-        dst[64 * 8] = (__bf16)(v[j] - (float)h);
+        dst[64 * 8] = l;
     }
 }
 

@@ -44,9 +44,8 @@ enum { VD_A_ROWS = 0, VD_A_CONV3 = 1, VD_A_DECONV = 2 };
 enum { VD_EPI_F32 = 0, VD_EPI_RESID = 1, VD_EPI_SPLIT = 2, VD_EPI_PLANAR = 3, VD_EPI_QKV = 4, VD_EPI_EMBED = 5 };
 enum { VD_ACT_NONE = 0, VD_ACT_GELU = 1, VD_ACT_SILU = 2 };
 
-__device__ __forceinline__ float vd_elu1(float t) { return t > 0.0f ? t + 1.0f : expf(t); }                      // elu(t) + 1
 __device__ __forceinline__ float vd_act(float t, int act) {
-    if (act == VD_ACT_GELU) return 0.5f * t * (1.0f + erff(t * 0.70710678118654752440f));
+    if (act == VD_ACT_GELU) return gelu_erf(t);
     if (act == VD_ACT_SILU) return t / (1.0f + expf(-t));
     return t;
 }
@@ -286,11 +285,7 @@ __global__ __launch_bounds__(256) void vd_gemm_kernel(VdGemmArgs p) {
 #pragma unroll
             for (int mb = 0; mb < 4; ++mb)
 #pragma unroll
-                for (int nb = 0; nb < NREP; ++nb) {
-                    acc[mb][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[mb], bh[nb], acc[mb][nb], 0, 0, 0);
-                    acc[mb][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[mb], bl[nb], acc[mb][nb], 0, 0, 0);
-                    acc[mb][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[mb], bh[nb], acc[mb][nb], 0, 0, 0);
-                }
+                for (int nb = 0; nb < NREP; ++nb) acc[mb][nb] = mfma3_bf16(ah[mb], al[mb], bh[nb], bl[nb], acc[mb][nb]);
         }
     }
 
@@ -323,7 +318,7 @@ __global__ __launch_bounds__(256) void vd_gemm_kernel(VdGemmArgs p) {
             if (p.epi == VD_EPI_F32) {
                 if (ch < p.elu_cols) {
 #pragma unroll
-                    for (int k = 0; k < 4; ++k) v[k] = vd_elu1(v[k]);
+                    for (int k = 0; k < 4; ++k) v[k] = elu1(v[k]);
                 }
                 *reinterpret_cast<float4*>(reinterpret_cast<float*>(p.out) + (size_t)row * p.N + ch) = make_float4(v[0], v[1], v[2], v[3]);
             } else if (p.epi == VD_EPI_RESID) {

@@ -15,7 +15,7 @@
 //
 // HBM algorithmic bytes per launch: features (1 + n_views) * C*HW*sizeof(T) + hypotheses D*HW*4
 // (+ G*D*HW*4 volume write in pass 2); both kernels are gather/L1-bound, not MFMA work.
-#include "mvs_common.h"
+#include "volume_format.h"
 
 #include <stdlib.h>
 
@@ -417,22 +417,16 @@ __global__ void volume_normalise_kernel(float* __restrict__ vol, const float* __
 // fp32 channel-last volume [.., 8] -> fp16 [.., 8] in a SEPARATE buffer (MVS_PREC_F16X2 U-Net), optionally normalising by the summed
 // visibility first; clamped to the fp16 range.  Out of place: a compacting in-place conversion would race between work-items.
 __global__ void volume_to_f16_kernel(const float* __restrict__ vol, const float* __restrict__ vis_sum, _Float16* __restrict__ out, int D, int HW, size_t nvox) {
-    typedef _Float16 h8 __attribute__((ext_vector_type(8)));
     float sat_amax = 0.0f;                                       // fp16 saturation counter (mvs_common.h)
     for (size_t vox = (size_t)blockIdx.x * blockDim.x + threadIdx.x; vox < nvox; vox += (size_t)gridDim.x * blockDim.x) {
         const float4* q = reinterpret_cast<const float4*>(vol + vox * 8);
         const float4 a = q[0], c = q[1];
         float x[8] = {a.x, a.y, a.z, a.w, c.x, c.y, c.z, c.w};
         const float den = vis_sum != nullptr ? vis_sum[(vox / ((size_t)D * HW)) * HW + vox % HW] + 1e-6f : 1.0f;
-        h8 hv;
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
+        for (int j = 0; j < 8; ++j)
             if (vis_sum != nullptr) x[j] = x[j] / den;
-            hv[j] = (_Float16)fminf(fmaxf(x[j], -65504.0f), 65504.0f);
-        }
-        sat::track(sat_amax, x[0], x[1], x[2], x[3]);
-        sat::track(sat_amax, x[4], x[5], x[6], x[7]);
-        *reinterpret_cast<h8*>(out + vox * 8) = hv;
+        volume_store8<MVS_VOLUME_F16>(out, vox, x, sat_amax);
     }
     sat::commit(sat_amax);
 }
@@ -440,8 +434,9 @@ __global__ void volume_to_f16_kernel(const float* __restrict__ vol, const float*
 // fp32 channel-last volume [.., 8] -> the split activation format of MVS_PREC_BF16X3_SPLIT (per voxel [hi x8 | lo x8] bf16), in
 // place (same 32 bytes per voxel), optionally normalising by the summed visibility first (the view-sharded multi-GPU path)
 __global__ void volume_to_split_kernel(float* __restrict__ vol, const float* __restrict__ vis_sum, int D, int HW, size_t nvox) {
+    float unused = 0.0f;
     for (size_t vox = (size_t)blockIdx.x * blockDim.x + threadIdx.x; vox < nvox; vox += (size_t)gridDim.x * blockDim.x) {
-        float4* q = reinterpret_cast<float4*>(vol + vox * 8);
+        const float4* q = reinterpret_cast<const float4*>(vol + vox * 8);
         const float4 a = q[0], c = q[1];
         float x[8] = {a.x, a.y, a.z, a.w, c.x, c.y, c.z, c.w};
         if (vis_sum != nullptr) {
@@ -449,20 +444,7 @@ __global__ void volume_to_split_kernel(float* __restrict__ vol, const float* __r
 #pragma unroll
             for (int j = 0; j < 8; ++j) x[j] = x[j] / den;
         }
-        unsigned short hi[8], lo[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            hi[j] = from_f32<uint16_t>(x[j]);
-            lo[j] = from_f32<uint16_t>(x[j] - to_f32(hi[j]));
-        }
-        unsigned hw[4], lw[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            hw[j] = (unsigned)hi[2 * j] | ((unsigned)hi[2 * j + 1] << 16);
-            lw[j] = (unsigned)lo[2 * j] | ((unsigned)lo[2 * j + 1] << 16);
-        }
-        q[0] = make_float4(__builtin_bit_cast(float, hw[0]), __builtin_bit_cast(float, hw[1]), __builtin_bit_cast(float, hw[2]), __builtin_bit_cast(float, hw[3]));
-        q[1] = make_float4(__builtin_bit_cast(float, lw[0]), __builtin_bit_cast(float, lw[1]), __builtin_bit_cast(float, lw[2]), __builtin_bit_cast(float, lw[3]));
+        volume_store8<MVS_VOLUME_SPLIT>(vol, vox, x, unused);
     }
 }
 

@@ -10,7 +10,7 @@ from typing import List, Optional, Sequence, Tuple
 
 import torch
 
-from . import _lib
+from . import _lib, packing
 from ._lib import check, lib, ptr, stream_of
 
 
@@ -735,9 +735,7 @@ def to_split(x_cl: torch.Tensor) -> torch.Tensor:
     voxel, C / 8 octets of [hi x8 | lo x8] bf16 with hi = bf16(x), lo = bf16(x - hi)).  Plain torch ops: a test / tooling utility,
     the product path never converts (the kernels' epilogues write the format)."""
     C = x_cl.shape[-1]
-    hi = x_cl.to(torch.bfloat16)
-    lo = (x_cl - hi.float()).to(torch.bfloat16)
-    pair = torch.stack([hi.reshape(*x_cl.shape[:-1], C // 8, 8), lo.reshape(*x_cl.shape[:-1], C // 8, 8)], dim=-2)    # [..., C/8, 2, 8]
+    pair = packing.split_bf16(x_cl.reshape(*x_cl.shape[:-1], C // 8, 8)).movedim(0, -2)                             # [..., C/8, 2, 8]
     return pair.contiguous().view(torch.float32).reshape(x_cl.shape)
 
 

@@ -65,8 +65,9 @@ def pack_deconv_weights(w: torch.Tensor) -> torch.Tensor:
     return full.permute(5, 0, 3, 1, 4, 2).contiguous().reshape(-1)         # [tap, q, mb, g, j, s]
 
 
-def _split_bf16(x: torch.Tensor) -> torch.Tensor:
-    """fp32 [...] -> bf16 [2, ...] with x ~= hi + lo (both round-to-nearest-even), the operand format of the bf16x3 kernels."""
+def split_bf16(x: torch.Tensor) -> torch.Tensor:
+    """fp32 [...] -> bf16 [2, ...] with x ~= hi + lo (both round-to-nearest-even), the operand format of the bf16x3 kernels: the host
+    mirror of split_bf16 / split_bf16_bits in csrc/split_format.h, whose header states the whole contract."""
     hi = x.to(torch.bfloat16)
     lo = (x - hi.float()).to(torch.bfloat16)
     return torch.stack([hi, lo])
@@ -103,7 +104,7 @@ def pack_conv_weights_bf16x3(w: torch.Tensor, ch: int, split=None) -> torch.Tens
     full = torch.zeros(npass, nstep * 4, mrep * 16, 8, dtype=torch.float32, device=w.device)
     full[:, :noct, :cout] = wt
     full = full.reshape(npass, nstep, 4, mrep, 16, 8).permute(0, 1, 3, 2, 4, 5)                              # [pass, step, mb, g, j, e]
-    return (split or _split_bf16)(full).permute(1, 2, 3, 0, 4, 5, 6).contiguous().reshape(-1)                           # [pass, step, mb, 2, g, j, e]
+    return (split or split_bf16)(full).permute(1, 2, 3, 0, 4, 5, 6).contiguous().reshape(-1)                           # [pass, step, mb, 2, g, j, e]
 
 
 def fpn_chunk(cin: int, stride: int) -> int:
@@ -131,7 +132,7 @@ def pack_linear_bf16x3(w: torch.Tensor, split=None) -> torch.Tensor:
     n, k = w.shape
     assert n % 16 == 0 and k % 32 == 0, (n, k)
     full = w.float().reshape(n // 16, 16, k // 32, 4, 8).permute(2, 0, 3, 1, 4)                                # [step, mb, g, j, e]
-    return (split or _split_bf16)(full).permute(1, 2, 0, 3, 4, 5).contiguous().reshape(-1)                                # [step, mb, 2, g, j, e]
+    return (split or split_bf16)(full).permute(1, 2, 0, 3, 4, 5).contiguous().reshape(-1)                                # [step, mb, 2, g, j, e]
 
 
 def patch_embed_matrix(w: torch.Tensor) -> torch.Tensor:
@@ -185,7 +186,7 @@ def pack_deconv_weights_bf16x3(w: torch.Tensor, sd: int, split=None) -> torch.Te
                 if kw == 2:                                                                       # input mx: pw = 0 uses kw = 1 of the same (kd, kh)
                     full[ti * opt:(ti + 1) * opt, 0:8] = wf[:, :, :, t1 - 1].permute(0, 2, 1)
             full = full.reshape(nst, 4, 1, 16, 8).permute(0, 2, 1, 3, 4)
-            chunks.append((split or _split_bf16)(full).permute(1, 2, 0, 3, 4, 5).contiguous().reshape(-1))
+            chunks.append((split or split_bf16)(full).permute(1, 2, 0, 3, 4, 5).contiguous().reshape(-1))
         return torch.cat(chunks)
     for taps in deconv_class_taps(sd):
         noct = len(taps) * opt
@@ -194,7 +195,7 @@ def pack_deconv_weights_bf16x3(w: torch.Tensor, sd: int, split=None) -> torch.Te
         full = torch.zeros(nst * 4, mrep * 16, 8, dtype=torch.float32, device=w.device)
         full[:noct, :cout] = sel
         full = full.reshape(nst, 4, mrep, 16, 8).permute(0, 2, 1, 3, 4)             # [step, mb, g, j, e]
-        chunks.append((split or _split_bf16)(full).permute(1, 2, 0, 3, 4, 5).contiguous().reshape(-1))   # [step, mb, 2, g, j, e]
+        chunks.append((split or split_bf16)(full).permute(1, 2, 0, 3, 4, 5).contiguous().reshape(-1))   # [step, mb, 2, g, j, e]
     return torch.cat(chunks)
 
 
@@ -230,7 +231,7 @@ def pack_fmt_linear(w: torch.Tensor) -> torch.Tensor:
     if npad != n:
         w = torch.cat([w.float(), w.new_zeros(npad - n, k).float()], 0)
     full = w.float().reshape(npad // 16, 16, k // 32, 2, 4, 4).permute(2, 0, 4, 1, 3, 5).reshape(k // 32, npad // 16, 4, 16, 8)  # [step, mb, g, j, e]
-    return _split_bf16(full).permute(1, 2, 0, 3, 4, 5).contiguous().reshape(-1)                                    # [step, mb, 2, g, j, e]
+    return split_bf16(full).permute(1, 2, 0, 3, 4, 5).contiguous().reshape(-1)                                    # [step, mb, 2, g, j, e]
 
 
 FMT_VECTORS = ("norm1.weight", "norm1.bias", "attn.proj.bias", "ls1.gamma", "norm2.weight", "norm2.bias", "mlp.fc1.bias", "mlp.fc2.bias",
@@ -261,7 +262,7 @@ def pack_tokens_split(x: torch.Tensor) -> torch.Tensor:
     full = torch.zeros(mp, c, dtype=torch.float32, device=x.device)
     full[:m] = x.float()
     full = full.reshape(mp // 16, 16, c // 32, 4, 8).permute(0, 2, 3, 1, 4)                                       # [rb, step, g, li, e]
-    return _split_bf16(full).permute(1, 2, 0, 3, 4, 5).contiguous().reshape(-1)                                   # [rb, step, 2, g, li, e]
+    return split_bf16(full).permute(1, 2, 0, 3, 4, 5).contiguous().reshape(-1)                                   # [rb, step, 2, g, li, e]
 
 
 def unpack_tokens_split(p: torch.Tensor, m: int, c: int) -> torch.Tensor:
@@ -389,5 +390,5 @@ def pack_vit_qkv(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, npad: int) -
             parts.append(pack_tokens_split(torch.cat([k[view, h].float(), k.new_zeros(npad - ntok, D).float()])))
             vp = torch.cat([v[view, h].float(), v.new_zeros(npad - ntok, D).float()])
             vt = vp.reshape(npad // 32, 2, 4, 4, 4, 16).permute(0, 4, 2, 5, 1, 3).reshape(npad // 32, 4, 4, 16, 8)   # [ks, db, g, d & 15, e]
-            parts.append(_split_bf16(vt).permute(1, 2, 0, 3, 4, 5).contiguous().reshape(-1))                       # [ks, db, 2, g, d, e]
+            parts.append(split_bf16(vt).permute(1, 2, 0, 3, 4, 5).contiguous().reshape(-1))                       # [ks, db, 2, g, d, e]
     return torch.cat(parts).view(torch.uint8)
