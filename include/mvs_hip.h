@@ -583,6 +583,19 @@ int mvs_fmt_path_fwd(const float* prev, const float* lateral, const float* w_red
 int mvs_fmt_merge_fwd(const float* prev, const float* lateral, const float* w_reduce, float* merged, int N, int C, int h, int w, int H, int W,
                       void* stream);
 int mvs_fmt_smooth_fwd(const float* x, const void* w_packed, float* y, int N, int C, int H, int W, void* stream);
+/* Backward of one pathway level Y = S * M, M = U(W_r prev) + lateral.  d lateral = dM is mvs_fmt_smooth_fwd of
+ * dY with S's taps flipped and its channel axes exchanged.  Weight gradients are per-workgroup fp32 partials in `workspace` (the
+ * *_workspace_bytes queries; 0 = out of range or not built) added in a fixed order: no atomics, bit-identical run to run.
+ * mvs_fmt_path_bwd: d_merged [N,C,H,W] -> d_prev [N,2C,h,w] = W_r^T U^T(dM) and d_w_reduce [C,2C] = sum U^T(dM) (x) prev; U^T gathers
+ *   with the forward's own coordinate function (the exact adjoint; any h, w, H, W >= 1).
+ * mvs_fmt_smooth_wgrad: d_w_smooth [C,C,3,3] = sum_pixels dY (x) M shifted by the tap, exact fp32 products; M is recomputed from
+ *   prev, lateral and w_reduce in the kernel's staging and never written.                                                          */
+size_t mvs_fmt_path_bwd_workspace_bytes(int N, int C, int h, int w);
+int mvs_fmt_path_bwd(const float* d_merged, const float* prev, const float* w_reduce, float* d_prev, float* d_w_reduce, void* workspace,
+                     size_t workspace_bytes, int N, int C, int h, int w, int H, int W, void* stream);
+size_t mvs_fmt_smooth_wgrad_workspace_bytes(int N, int C, int H, int W);
+int mvs_fmt_smooth_wgrad(const float* dy, const float* prev, const float* lateral, const float* w_reduce, float* d_w_smooth, void* workspace,
+                         size_t workspace_bytes, int N, int C, int h, int w, int H, int W, void* stream);
 
 /* ==== CrossVITDecoder: the ViT feature decoder at d_model 768 =========================================
  * models/module.py:273-364 with the shipped decoder_cfg (Linear attention, 12 heads of 64, ffn, pre-norm, LayerScale).  The residual

@@ -133,6 +133,10 @@ SIGNATURES = {
     "mvs_fmt_path_fwd": (_i, [_vp] * 5 + [_i] * 6 + [_vp]),
     "mvs_fmt_merge_fwd": (_i, [_vp] * 4 + [_i] * 6 + [_vp]),
     "mvs_fmt_smooth_fwd": (_i, [_vp] * 3 + [_i] * 4 + [_vp]),
+    "mvs_fmt_path_bwd_workspace_bytes": (_sz, [_i] * 4),
+    "mvs_fmt_path_bwd": (_i, [_vp] * 6 + [_sz] + [_i] * 6 + [_vp]),
+    "mvs_fmt_smooth_wgrad_workspace_bytes": (_sz, [_i] * 4),
+    "mvs_fmt_smooth_wgrad": (_i, [_vp] * 6 + [_sz] + [_i] * 6 + [_vp]),
     "mvs_vitdec_packed_bytes": (_sz, [C.c_longlong, _i]),
     "mvs_vitdec_summary_bytes": (_sz, [_i]),
     "mvs_vitdec_kv_workspace_bytes": (_sz, [_i, _i]),

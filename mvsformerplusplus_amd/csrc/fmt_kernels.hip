@@ -27,6 +27,9 @@
 //      conv2d_split_kernel<C, C, 3, 1, FtMergeSrc<C>, PlanarSink<false>> (conv2d_split.h) whose staging evaluates the merged map for the tile
 //      and its halo (align_corners=False, any size ratio, no biases); the merged map is never written.  fmt_merge_kernel
 //      (conv2d_source_kernel on FtMergeSrc) + the same convolution on PlanarSrc are the unfused form.
+//   4. the pathway's backward (further down): fmt_path_bwd_kernel (the interpolation's adjoint as a gather, d prev,
+//      the partials of d W_r), fmt_smooth_wgrad_kernel (d S on v_mfma_f32_16x16x4_f32 with the merged map re-evaluated in LDS) and
+//      fmt_partial_reduce_kernel (fixed-order sum of the partials).  The blocks' backward is not in this file (training.py).
 // Staged positions are clamped to the image explicitly (zero padding from a branch, never from an out-of-range load).
 #include "conv2d_split.h"
 
@@ -345,6 +348,16 @@ __global__ __launch_bounds__(256) void fmt_kv_reduce_kernel(const float* __restr
 // ---------------------------------------------------------------------------------------------------------------------------------
 // merged[c] at a pixel of the lateral = lateral[c] + sum_ci w[c][ci] * bilinear(prev[ci]); prev [N, 2C, h, w], lateral [N, C, H, W].
 // The 1x1 and the interpolation are both linear and bias-free: the 2C coarse channels are interpolated once per pixel, then reduced.
+// One axis of the interpolation (align_corners=False, F.interpolate(size=...)): fine index gi of a map whose coarse side has n entries,
+// s = (float)n / N -> the first tap i0 and the weight l of the second tap i0 + (i0 < n - 1); the first tap's weight is 1 - l.  The
+// backward gathers with this same function, so that it is the exact adjoint of what the forward evaluated.
+__device__ __forceinline__ void ft_axis(int gi, float s, int n, int& i0, float& l) {
+    const float f = fmaxf(((float)gi + 0.5f) * s - 0.5f, 0.0f);
+    const int i = (int)f;
+    i0 = i < n - 1 ? i : n - 1;
+    l = fminf(f - (float)i0, 1.0f);
+}
+
 template <int C>
 struct FtMergeSrc {
     static constexpr int STAGE_OCTETS = 0;
@@ -358,10 +371,10 @@ struct FtMergeSrc {
     const float* lp;
     __device__ __forceinline__ void at(int n, int gy, int gx) {
         lp = lat + ((size_t)n * C * H + gy) * W + gx;
-        const float fy = fmaxf(((float)gy + 0.5f) * sy - 0.5f, 0.0f), fx = fmaxf(((float)gx + 0.5f) * sx - 0.5f, 0.0f);
-        const int yi = (int)fy, xi = (int)fx;
-        const int y0 = yi < h - 1 ? yi : h - 1, x0 = xi < w - 1 ? xi : w - 1;
-        const float ly = fminf(fy - (float)y0, 1.0f), lx = fminf(fx - (float)x0, 1.0f);
+        int y0, x0;
+        float ly, lx;
+        ft_axis(gy, sy, h, y0, ly);
+        ft_axis(gx, sx, w, x0, lx);
         const int dy = y0 < h - 1 ? w : 0, dx = x0 < w - 1 ? 1 : 0;
         const float* q = prev + (size_t)n * CP * h * w + (size_t)y0 * w + x0;
         const size_t hw = (size_t)h * w;
@@ -401,6 +414,275 @@ static int ft_slabs(int ntok) {
 static bool ft_path_args(const char* what, int N, int C, int H, int W) {
     if (N < 1 || N > 65535 || H < 1 || W < 1 || (long long)N * C * H * W >= (1LL << 40)) { set_error("%s: bad arguments", what); return false; }
     return true;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// pathway backward.  Y = S * M, M = U(W_r prev) + lat.  d lat = dM is the forward convolution with flipped,
+// channel-transposed taps (mvs_fmt_smooth_fwd on repacked weights); the two kernels below give d prev, d W_r and d S.  Weight
+// gradients leave each workgroup as one fp32 partial; fmt_partial_reduce_kernel adds the partials in a fixed order (no atomics).
+// ---------------------------------------------------------------------------------------------------------------------------------
+constexpr int FT_BWD_PIX = 256;               // coarse pixels per workgroup pass of fmt_path_bwd_kernel
+constexpr int FT_RED_SEG = 16;                // segments of consecutive partials per output element in the reduction
+
+// partials (= workgroups) of one launch: bounded, so that the reduction's chains stay short (8192 / C: 256 | 512 | 1024)
+static int ft_bwd_parts(long long work, int C) {
+    const long long cap = 8192 / C;
+    return (int)(work < cap ? work : cap);
+}
+
+// weight with which coarse index c enters fine index gi's two taps (both, where they collapse onto the last entry)
+__device__ __forceinline__ float ft_tap_weight(int gi, float s, int n, int c) {
+    int i0;
+    float l;
+    ft_axis(gi, s, n, i0, l);
+    const int i1 = i0 < n - 1 ? i0 + 1 : i0;
+    return (i0 == c ? 1.0f - l : 0.0f) + (i1 == c ? l : 0.0f);
+}
+
+// fine indices that can name coarse index c: those whose source coordinate lies within (c - 1, c + 1), one more on either side for the
+// rounding of this estimate (ft_tap_weight decides); the clamps of ft_axis at both ends fall inside the clamped range
+__device__ __forceinline__ void ft_fine_range(int c, float inv, int N, int& lo, int& hi) {
+    lo = (int)floorf(((float)c - 0.5f) * inv - 0.5f) - 1;
+    hi = (int)ceilf(((float)c + 1.5f) * inv - 0.5f) + 1;
+    lo = lo < 0 ? 0 : lo;
+    hi = hi > N - 1 ? N - 1 : hi;
+}
+
+// One thread per coarse pixel: dr = U^T(dM) gathered over the fine pixels whose taps name it, d prev = W_r^T dr, and the workgroup's
+// partial of dW_r[c][j] = sum_p dr[c][p] prev[j][p] from LDS copies of dr and (JT channels at a time) prev.  Thread (jl, cg) owns
+// rows cg * CPT .. of column pass * JT + jl.  prev is stored rotated by its channel so that the 32 columns of a wave hit 32 banks.
+template <int C>
+__global__ __launch_bounds__(256) void fmt_path_bwd_kernel(const float* __restrict__ dm, const float* __restrict__ prev, const float* __restrict__ wr,
+                                                           float* __restrict__ dprev, float* __restrict__ part, int H, int W, int h, int w, float sy,
+                                                           float sx, int chunks_per_view, int nchunk) {
+    constexpr int CP = 2 * C, JT = CP < 32 ? CP : 32, NG = FT_BWD_PIX / JT, CPT = (C + NG - 1) / NG, NPASS = CP / JT;
+    HIP_DYNAMIC_SHARED(float4, lds4)
+    float* drs = reinterpret_cast<float*>(lds4);                  // [C][256]
+    float* ps = drs + C * FT_BWD_PIX;                             // [JT][256]
+    const int tid = (int)threadIdx.x, jl = tid % JT, cg = tid / JT;
+    const size_t hw = (size_t)h * w, HW = (size_t)H * W;
+    const float iy = (float)H / (float)h, ix = (float)W / (float)w;
+    float acc[NPASS][CPT];
+#pragma unroll
+    for (int ps_ = 0; ps_ < NPASS; ++ps_)
+#pragma unroll
+        for (int k = 0; k < CPT; ++k) acc[ps_][k] = 0.0f;
+#pragma unroll 1
+    for (int chunk = (int)blockIdx.x; chunk < nchunk; chunk += (int)gridDim.x) {
+        const int n = chunk / chunks_per_view;
+        const size_t p = (size_t)(chunk % chunks_per_view) * FT_BWD_PIX + tid;
+        const bool ok = p < hw;
+        float dr[C];
+#pragma unroll
+        for (int c = 0; c < C; ++c) dr[c] = 0.0f;
+        if (ok) {
+            const int cy = (int)(p / w), cx = (int)(p % w);
+            int ylo, yhi, xlo, xhi;
+            ft_fine_range(cy, iy, H, ylo, yhi);
+            ft_fine_range(cx, ix, W, xlo, xhi);
+            const float* dn = dm + (size_t)n * C * HW;
+#pragma unroll 1
+            for (int gy = ylo; gy <= yhi; ++gy) {
+                const float wy = ft_tap_weight(gy, sy, h, cy);
+                if (wy == 0.0f) continue;
+#pragma unroll 1
+                for (int gx = xlo; gx <= xhi; ++gx) {
+                    const float wgt = wy * ft_tap_weight(gx, sx, w, cx);
+                    if (wgt == 0.0f) continue;
+                    const float* q = dn + (size_t)gy * W + gx;
+#pragma unroll
+                    for (int c = 0; c < C; ++c) dr[c] = fmaf(wgt, q[(size_t)c * HW], dr[c]);
+                }
+            }
+            float* o = dprev + (size_t)n * CP * hw + p;
+#pragma unroll 4
+            for (int j = 0; j < CP; ++j) {
+                float s = 0.0f;
+#pragma unroll
+                for (int c = 0; c < C; ++c) s = fmaf(wr[c * CP + j], dr[c], s);
+                o[(size_t)j * hw] = s;
+            }
+        }
+        __syncthreads();                                          // the previous chunk's readers are done with drs and ps
+#pragma unroll
+        for (int c = 0; c < C; ++c) drs[c * FT_BWD_PIX + tid] = dr[c];
+#pragma unroll
+        for (int pass = 0; pass < NPASS; ++pass) {
+            if (pass) __syncthreads();
+            const float* pn = prev + ((size_t)n * CP + pass * JT) * hw + p;
+#pragma unroll 4
+            for (int j = 0; j < JT; ++j) ps[j * FT_BWD_PIX + ((tid + j) & (FT_BWD_PIX - 1))] = ok ? pn[(size_t)j * hw] : 0.0f;
+            __syncthreads();
+            if (cg * CPT < C) {
+#pragma unroll 4
+                for (int pp = 0; pp < FT_BWD_PIX; ++pp) {
+                    const float pv = ps[jl * FT_BWD_PIX + ((pp + jl) & (FT_BWD_PIX - 1))];
+#pragma unroll
+                    for (int k = 0; k < CPT; ++k) acc[pass][k] = fmaf(drs[(cg * CPT + k) * FT_BWD_PIX + pp], pv, acc[pass][k]);
+                }
+            }
+        }
+    }
+    if (cg * CPT < C) {
+        float* dst = part + (size_t)blockIdx.x * C * CP;
+#pragma unroll
+        for (int pass = 0; pass < NPASS; ++pass)
+#pragma unroll
+            for (int k = 0; k < CPT; ++k) dst[(cg * CPT + k) * CP + pass * JT + jl] = acc[pass][k];
+    }
+}
+
+// dS[co][ci][ky][kx] = sum over pixels of dY[co][y][x] M[ci][y + ky - 1][x + kx - 1] as a GEMM on the exact-fp32 v_mfma_f32_16x16x4_f32:
+// rows = co (16 per block; the upper 8 are zero at C = 8), columns = (ci, tap) = the 9 C weights of one row of S in memory order, K = the
+// pixels of a TH x 64 tile.  The merged map of the tile and its halo is evaluated into LDS by FtMergeSrc, as the forward's staging
+// does (zero outside the image); it is never written to memory.  Wave v owns the column blocks v, v + 4, ..: its accumulators are
+// final for the workgroup, which keeps them over all of its tiles and writes one partial.
+template <int C>
+struct FtWgradShape {
+    static constexpr int TH = C == 32 ? 2 : 4, TW = 64, NPIX = TH * TW;
+    static constexpr int RS = TW + 4, PL = (TH + 2) * RS + 1;     // staged row / channel-plane strides of M
+    static constexpr int DSS = NPIX + 4;                          // channel stride of the staged dY: lane (co, k) reads bank 4 co + k
+    static constexpr int NRB = (C + 15) / 16, NCOL = 9 * C, NCB = (NCOL + 15) / 16, NCBW = (NCB + 3) / 4;
+    static constexpr int LDS = (C * PL + C * DSS) * (int)sizeof(float);
+};
+
+template <int C>
+__global__ __launch_bounds__(256) void fmt_smooth_wgrad_kernel(FtMergeSrc<C> src, const float* __restrict__ dy, float* __restrict__ part, int tiles_x,
+                                                               int tiles_per_view, int ntile) {
+    typedef FtWgradShape<C> F;
+    HIP_DYNAMIC_SHARED(float4, lds4)
+    float* ms = reinterpret_cast<float*>(lds4);                   // [C][TH + 2][RS]
+    float* ds = ms + C * F::PL;                                   // [C][DSS]
+    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, g = lane >> 4;
+    const int H = src.H, W = src.W;
+    int off[F::NCBW];                                             // this lane's column (ci, ky, kx) in the staged tile, -1 past the end
+#pragma unroll
+    for (int t = 0; t < F::NCBW; ++t) {
+        const int col = (wave + 4 * t) * 16 + li, ci = col / 9, tap = col % 9;
+        off[t] = col < F::NCOL ? ci * F::PL + (tap / 3) * F::RS + tap % 3 : -1;
+    }
+    f32x4 acc[F::NRB][F::NCBW];
+#pragma unroll
+    for (int rb = 0; rb < F::NRB; ++rb)
+#pragma unroll
+        for (int t = 0; t < F::NCBW; ++t) acc[rb][t] = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll 1
+    for (int tile = (int)blockIdx.x; tile < ntile; tile += (int)gridDim.x) {
+        const int n = tile / tiles_per_view, tv = tile % tiles_per_view;
+        const int y0 = (tv / tiles_x) * F::TH, x0 = (tv % tiles_x) * F::TW;
+        __syncthreads();                                          // the previous tile's readers are done
+#pragma unroll 1
+        for (int pos = tid; pos < (F::TH + 2) * (F::TW + 2); pos += 256) {
+            const int py = pos / (F::TW + 2), px = pos % (F::TW + 2), gy = y0 - 1 + py, gx = x0 - 1 + px;
+            float* m = ms + py * F::RS + px;
+            if (gy >= 0 && gy < H && gx >= 0 && gx < W) {
+                FtMergeSrc<C> s = src;
+                s.at(n, gy, gx);
+#pragma unroll 1
+                for (int c0 = 0; c0 < C; c0 += 8) {
+                    float v[8];
+                    s.load8(c0, v);
+#pragma unroll
+                    for (int k = 0; k < 8; ++k) m[(c0 + k) * F::PL] = v[k];
+                }
+            } else {
+#pragma unroll
+                for (int c = 0; c < C; ++c) m[c * F::PL] = 0.0f;
+            }
+        }
+#pragma unroll 1
+        for (int e = tid; e < C * F::NPIX; e += 256) {
+            const int c = e / F::NPIX, pix = e % F::NPIX, gy = y0 + pix / F::TW, gx = x0 + pix % F::TW;
+            ds[c * F::DSS + pix] = gy < H && gx < W ? dy[(((size_t)n * C + c) * H + gy) * W + gx] : 0.0f;
+        }
+        __syncthreads();
+#pragma unroll 2
+        for (int q = 0; q < F::NPIX / 4; ++q) {
+            const int pix = 4 * q + g, at = (pix / F::TW) * F::RS + pix % F::TW;
+            float a[F::NRB];
+#pragma unroll
+            for (int rb = 0; rb < F::NRB; ++rb) a[rb] = rb * 16 + li < C ? ds[(rb * 16 + li) * F::DSS + pix] : 0.0f;
+#pragma unroll
+            for (int t = 0; t < F::NCBW; ++t) {
+                if (wave + 4 * t >= F::NCB) continue;             // wave-uniform
+                const float b = off[t] >= 0 ? ms[off[t] + at] : 0.0f;
+#pragma unroll
+                for (int rb = 0; rb < F::NRB; ++rb) acc[rb][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[rb], b, acc[rb][t], 0, 0, 0);
+            }
+        }
+    }
+    // lane (li, g) holds rows 16 rb + 4 g + r of column 16 cb + li
+    float* dst = part + (size_t)blockIdx.x * C * F::NCOL;
+#pragma unroll
+    for (int t = 0; t < F::NCBW; ++t) {
+        const int col = (wave + 4 * t) * 16 + li;
+        if (col >= F::NCOL) continue;
+#pragma unroll
+        for (int rb = 0; rb < F::NRB; ++rb)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int co = rb * 16 + 4 * g + r;
+                if (co < C) dst[co * F::NCOL + col] = acc[rb][t][r];
+            }
+    }
+}
+
+// out[e] = the sum of part[p][e] over the launch's partials in a fixed order: FT_RED_SEG segments of consecutive partials, each added
+// front to back by one thread, then the segment sums front to back.
+__global__ __launch_bounds__(256) void fmt_partial_reduce_kernel(const float* __restrict__ part, float* __restrict__ out, int nparts, int nelem) {
+    HIP_DYNAMIC_SHARED(float4, lds4)
+    float* seg = reinterpret_cast<float*>(lds4);                  // [FT_RED_SEG][16]
+    const int tid = (int)threadIdx.x, e = (int)blockIdx.x * 16 + (tid & 15), s = tid >> 4;
+    const int per = (nparts + FT_RED_SEG - 1) / FT_RED_SEG, p0 = s * per, p1 = p0 + per < nparts ? p0 + per : nparts;
+    float sum = 0.0f;
+    if (e < nelem)
+        for (int p = p0; p < p1; ++p) sum += part[(size_t)p * nelem + e];
+    seg[tid] = sum;
+    __syncthreads();
+    if (tid < 16 && e < nelem) {
+        float t = seg[tid];
+#pragma unroll
+        for (int k = 1; k < FT_RED_SEG; ++k) t += seg[k * 16 + tid];
+        out[e] = t;
+    }
+}
+
+static int ft_reduce_partials(const float* part, float* out, int nparts, int nelem, hipStream_t st) {
+    hipLaunchKernelGGL(fmt_partial_reduce_kernel, dim3(ceil_div(nelem, 16)), dim3(256), 256 * sizeof(float), st, part, out, nparts, nelem);
+    return check_launch("fmt_partial_reduce_kernel");
+}
+
+static bool ft_level_built(int C) { return C == 32 || C == 16 || C == 8; }
+
+static long long ft_path_bwd_chunks(int N, int h, int w) { return (long long)N * (((long long)h * w + FT_BWD_PIX - 1) / FT_BWD_PIX); }
+
+template <int C>
+static long long ft_wgrad_tiles(int N, int H, int W) {
+    return (long long)N * ceil_div(H, FtWgradShape<C>::TH) * ceil_div(W, FtWgradShape<C>::TW);
+}
+
+template <int C>
+static int launch_fmt_path_bwd(const float* dm, const float* prev, const float* wr, float* dprev, float* dwr, float* part, int N, int h, int w, int H,
+                               int W, hipStream_t st) {
+    constexpr int JT = 2 * C < 32 ? 2 * C : 32, LDS = (C + JT) * FT_BWD_PIX * (int)sizeof(float);
+    const int cpv = (int)ceil_div((long long)h * w, FT_BWD_PIX), nchunk = N * cpv, parts = ft_bwd_parts(nchunk, C);
+    if (LDS > 48 * 1024)
+        hipFuncSetAttribute(reinterpret_cast<const void*>(&fmt_path_bwd_kernel<C>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+    hipLaunchKernelGGL((fmt_path_bwd_kernel<C>), dim3(parts), dim3(256), LDS, st, dm, prev, wr, dprev, part, H, W, h, w, (float)h / (float)H,
+                       (float)w / (float)W, cpv, nchunk);
+    const int rc = check_launch("fmt_path_bwd_kernel");
+    return rc != MVS_OK ? rc : ft_reduce_partials(part, dwr, parts, C * 2 * C, st);
+}
+
+template <int C>
+static int launch_fmt_smooth_wgrad(const FtMergeSrc<C>& src, const float* dy, float* ds, float* part, int N, hipStream_t st) {
+    typedef FtWgradShape<C> F;
+    const int tiles_x = (int)ceil_div(src.W, F::TW), tpv = tiles_x * (int)ceil_div(src.H, F::TH), ntile = N * tpv, parts = ft_bwd_parts(ntile, C);
+    if (F::LDS > 48 * 1024)
+        hipFuncSetAttribute(reinterpret_cast<const void*>(&fmt_smooth_wgrad_kernel<C>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)F::LDS);
+    hipLaunchKernelGGL((fmt_smooth_wgrad_kernel<C>), dim3(parts), dim3(256), F::LDS, st, src, dy, part, tiles_x, tpv, ntile);
+    const int rc = check_launch("fmt_smooth_wgrad_kernel");
+    return rc != MVS_OK ? rc : ft_reduce_partials(part, ds, parts, C * F::NCOL, st);
 }
 
 }  // namespace mvs
@@ -486,5 +768,63 @@ extern "C" int mvs_fmt_smooth_fwd(const float* x, const void* w_packed, float* y
     MVS_FMT_LEVELS(MVS_FMT_SM)
 #undef MVS_FMT_SM
     set_error("mvs_fmt_smooth_fwd: built for C = 32, 16, 8 [FMT.py:150-152]; got C = %d", C);
+    return MVS_ERR_UNSUPPORTED;
+}
+
+// ---- pathway backward ----
+static bool ft_bwd_args(const char* what, int N, int C, int h, int w, int H, int W) {
+    if (h < 1 || w < 1 || !ft_path_args(what, N, C, H, W) || (long long)N * 2 * C * h * w >= (1LL << 40)) { set_error("%s: bad arguments", what); return false; }
+    return true;
+}
+
+extern "C" size_t mvs_fmt_path_bwd_workspace_bytes(int N, int C, int h, int w) {
+    if (N < 1 || N > 65535 || h < 1 || w < 1 || !ft_level_built(C) || ft_path_bwd_chunks(N, h, w) > 0x7fffffffLL) return 0;
+    return (size_t)ft_bwd_parts(ft_path_bwd_chunks(N, h, w), C) * C * 2 * C * sizeof(float);
+}
+
+extern "C" int mvs_fmt_path_bwd(const float* d_merged, const float* prev, const float* w_reduce, float* d_prev, float* d_w_reduce, void* workspace,
+                                size_t workspace_bytes, int N, int C, int h, int w, int H, int W, void* stream) {
+    if (!ft_level_built(C)) {
+        set_error("mvs_fmt_path_bwd: built for the pathway levels 64 -> 32, 32 -> 16, 16 -> 8 (C = 32, 16, 8) [FMT.py:146-152]; got C = %d", C);
+        return MVS_ERR_UNSUPPORTED;
+    }
+    if (!d_merged || !prev || !w_reduce || !d_prev || !d_w_reduce || !workspace || !ft_bwd_args("mvs_fmt_path_bwd", N, C, h, w, H, W)) {
+        set_error("mvs_fmt_path_bwd: bad arguments");
+        return MVS_ERR_ARG;
+    }
+    const size_t need = mvs_fmt_path_bwd_workspace_bytes(N, C, h, w);
+    if (!need || workspace_bytes < need) { set_error("mvs_fmt_path_bwd: workspace smaller than mvs_fmt_path_bwd_workspace_bytes"); return MVS_ERR_ARG; }
+#define MVS_FMT_PB(CC) \
+    if (C == CC) return launch_fmt_path_bwd<CC>(d_merged, prev, w_reduce, d_prev, d_w_reduce, reinterpret_cast<float*>(workspace), N, h, w, H, W, (hipStream_t)stream);
+    MVS_FMT_LEVELS(MVS_FMT_PB)
+#undef MVS_FMT_PB
+    return MVS_ERR_UNSUPPORTED;
+}
+
+extern "C" size_t mvs_fmt_smooth_wgrad_workspace_bytes(int N, int C, int H, int W) {
+    if (N < 1 || N > 65535 || H < 1 || W < 1 || !ft_level_built(C)) return 0;
+    const long long tiles = C == 32 ? ft_wgrad_tiles<32>(N, H, W) : C == 16 ? ft_wgrad_tiles<16>(N, H, W) : ft_wgrad_tiles<8>(N, H, W);
+    if (tiles > 0x7fffffffLL) return 0;
+    return (size_t)ft_bwd_parts(tiles, C) * C * 9 * C * sizeof(float);
+}
+
+extern "C" int mvs_fmt_smooth_wgrad(const float* dy, const float* prev, const float* lateral, const float* w_reduce, float* d_w_smooth, void* workspace,
+                                    size_t workspace_bytes, int N, int C, int h, int w, int H, int W, void* stream) {
+    if (!ft_level_built(C)) {
+        set_error("mvs_fmt_smooth_wgrad: built for C = 32, 16, 8 [FMT.py:150-152]; got C = %d", C);
+        return MVS_ERR_UNSUPPORTED;
+    }
+    if (!dy || !prev || !lateral || !w_reduce || !d_w_smooth || !workspace || !ft_bwd_args("mvs_fmt_smooth_wgrad", N, C, h, w, H, W)) {
+        set_error("mvs_fmt_smooth_wgrad: bad arguments");
+        return MVS_ERR_ARG;
+    }
+    const size_t need = mvs_fmt_smooth_wgrad_workspace_bytes(N, C, H, W);
+    if (!need || workspace_bytes < need) { set_error("mvs_fmt_smooth_wgrad: workspace smaller than mvs_fmt_smooth_wgrad_workspace_bytes"); return MVS_ERR_ARG; }
+#define MVS_FMT_WG(CC) \
+    if (C == CC) \
+        return launch_fmt_smooth_wgrad<CC>(ft_merge_src<CC>(prev, lateral, w_reduce, h, w, H, W), dy, d_w_smooth, reinterpret_cast<float*>(workspace), N, \
+                                           (hipStream_t)stream);
+    MVS_FMT_LEVELS(MVS_FMT_WG)
+#undef MVS_FMT_WG
     return MVS_ERR_UNSUPPORTED;
 }

@@ -8,6 +8,10 @@ per reference view), then one fused launch per pathway level for all views.  Out
 are widened once.  Inference only: ``train()`` mode or an input that requires grad raises.  Capturable by ``torch.cuda.graph`` after one
 warm call at the same map size (packed weights and the position table are built and uploaded on first use).  ``patch_fmt(model)`` swaps a model's
 ``FMT_module`` and leaves everything else alone.
+
+``TrainableFMT_with_pathway`` is the same module with autograd: in eval mode on inputs that need no gradient it
+runs the inference path above, otherwise ``training.fmt_forward_train`` - the same forward launches with a hand-written backward per
+block and three HIP launches per pathway level.  ``patch_fmt(model, trainable=True)`` installs it.
 """
 from __future__ import annotations
 
@@ -102,15 +106,16 @@ class FMT(nn.Module):
         for p in self.parameters():
             if p.dim() > 1:
                 nn.init.xavier_uniform_(p)
-        self._pe = {}                      # at most PE_CACHE_ENTRIES tables, oldest dropped first
+        self._pe = {}                      # at most pe_entries tables, oldest dropped first
+        self.pe_entries = PE_CACHE_ENTRIES
 
     def position_encoding(self, H: int, W: int, device) -> torch.Tensor:
         """PositionEncodingSineNorm(64, max_shape=(128, 128)) as a [64, H*W] table, built on the host as the reference builds it (so
-        that no device sin / cos differs from torch's) and cached per (H, W, device) - the last PE_CACHE_ENTRIES sizes; the first
+        that no device sin / cos differs from torch's) and cached per (H, W, device) - the last `pe_entries` sizes; the first
         call at a size builds and uploads the table, so a graph capture needs one warm call at that size first."""
         key = (H, W, str(device))
         if key not in self._pe:
-            while len(self._pe) >= PE_CACHE_ENTRIES:
+            while len(self._pe) >= self.pe_entries:
                 del self._pe[next(iter(self._pe))]
             d = self.d_model
             pe = torch.zeros((d, H, W))
@@ -159,6 +164,10 @@ class FMT_with_pathway(nn.Module):
         ts = [features["stage%d" % s] for s in (1, 2, 3, 4)]
         if self.training or (torch.is_grad_enabled() and any(t.requires_grad for t in ts)):
             raise RuntimeError(_TRAIN_MSG % type(self).__name__)
+        return self._shapes(features)
+
+    def _shapes(self, features: Dict[str, torch.Tensor]):
+        ts = [features["stage%d" % s] for s in (1, 2, 3, 4)]
         B, V = ts[0].shape[:2]
         for t, c in zip(ts, STAGE_CHANNELS):
             if t.dim() != 5 or tuple(t.shape[:3]) != (B, V, c) or t.shape[3] < 1 or t.shape[4] < 1:
@@ -206,10 +215,30 @@ class FMT_with_pathway(nn.Module):
             return outs
 
 
-def patch_fmt(model: nn.Module) -> nn.Module:
+TRAIN_PE_CACHE_ENTRIES = 32    # the shipped multi-scale training list has 25 sizes: 8 tables would be rebuilt on most steps
+
+
+class TrainableFMT_with_pathway(FMT_with_pathway):
+    """FMT_with_pathway with autograd: the same constructor, state-dict keys and configuration refusals.  In eval mode on inputs that
+    need no gradient its forward is the inference path; otherwise it is ``training.fmt_forward_train`` (same outputs, bit for bit)."""
+
+    def __init__(self, base_channel=8, **kwargs):
+        super().__init__(base_channel, **kwargs)
+        self.FMT.pe_entries = TRAIN_PE_CACHE_ENTRIES
+
+    def forward(self, features: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+        ts = [features["stage%d" % s] for s in (1, 2, 3, 4)]
+        if not self.training and not (torch.is_grad_enabled() and any(t.requires_grad for t in ts)):
+            return super().forward(features)
+        from .training import fmt_forward_train
+        return fmt_forward_train(self, features)
+
+
+def patch_fmt(model: nn.Module, trainable: bool = False) -> nn.Module:
     """Swap ``model.FMT_module`` (the reference's FMT_with_pathway) for the native module: parameters carried over by
     ``load_state_dict(strict=True)``, device and train / eval mode preserved.  Everything else is left as it is.  Returns ``model``:
-    ``model = patch_fmt(patch_fpn(patch_model(model)))``."""
+    ``model = patch_fmt(patch_fpn(patch_model(model)))``.  trainable=True installs ``TrainableFMT_with_pathway`` instead of the
+    inference form."""
     old = model.FMT_module
     inner = old.FMT
     cfg = dict(attention_type=getattr(inner, "attention_type", "Linear"), d_model=getattr(inner, "d_model", 64), nhead=getattr(inner, "nhead", 4),
@@ -220,7 +249,7 @@ def patch_fmt(model: nn.Module) -> nn.Module:
     sd = old.state_dict()
     if "FMT.layers.0.mlp.fc1.weight" not in sd or "FMT.layers.0.ls1.gamma" not in sd or "FMT.layers.0.attn.q_proj.weight" not in sd:
         _unsupported("a module without mlp.fc1 / ls1.gamma / attn.q_proj parameters (ffn_type, init_values or the attention class differ)")
-    new = FMT_with_pathway(base_channel=old.smooth_3.out_channels, **cfg)
+    new = (TrainableFMT_with_pathway if trainable else FMT_with_pathway)(base_channel=old.smooth_3.out_channels, **cfg)
     new.load_state_dict(sd, strict=True)
     ref = next(old.parameters())
     model.FMT_module = new.to(ref.device).train(old.training)

@@ -241,6 +241,42 @@ def fmt_smooth(x: torch.Tensor, w_packed: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def _fmt_level_grad(grad: torch.Tensor, lateral_shape, what: str) -> torch.Tensor:
+    grad = _planar32(grad)
+    if tuple(grad.shape) != tuple(lateral_shape):
+        raise ValueError("%s must have the lateral's shape %s; got %s" % (what, tuple(lateral_shape), tuple(grad.shape)))
+    return grad
+
+
+def fmt_path_bwd(d_merged: torch.Tensor, prev: torch.Tensor, w_reduce: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Backward of a pathway level's merge: d_merged [N,C,H,W] (the gradient of bilinear(dim_reduction(prev)) +
+    lateral, which is also the lateral's) -> (d_prev [N,2C,h,w], d_w_reduce [C,2C]) fp32.  The interpolation's adjoint is a gather over
+    the forward's own taps; deterministic (fixed-order reduction, no atomics)."""
+    prev, d_merged, w_reduce, N, C, h, w, H, W = _fmt_level(prev, d_merged, w_reduce)
+    L = lib()
+    ws_bytes = L.mvs_fmt_path_bwd_workspace_bytes(N, C, h, w)
+    ws = torch.empty(max(ws_bytes, 4), dtype=torch.uint8, device=prev.device)
+    d_prev, d_w = torch.empty_like(prev), torch.empty(C, 2 * C, dtype=torch.float32, device=prev.device)
+    check(L.mvs_fmt_path_bwd(ptr(d_merged), ptr(prev), ptr(w_reduce), ptr(d_prev), ptr(d_w), ptr(ws), ws_bytes, N, C, h, w, H, W, stream_of(prev)),
+          "mvs_fmt_path_bwd")
+    return d_prev, d_w
+
+
+def fmt_smooth_wgrad(d_y: torch.Tensor, prev: torch.Tensor, lateral: torch.Tensor, w_reduce: torch.Tensor) -> torch.Tensor:
+    """Weight gradient of a pathway level's smooth_k: d_y [N,C,H,W] -> d_w [C,C,3,3] fp32 = the correlation of
+    d_y with the merged map, which is recomputed from (prev, lateral, w_reduce) inside the kernel and never written.  Exact fp32
+    products; deterministic."""
+    prev, lateral, w_reduce, N, C, h, w, H, W = _fmt_level(prev, lateral, w_reduce)
+    d_y = _fmt_level_grad(d_y, lateral.shape, "d_y")
+    L = lib()
+    ws_bytes = L.mvs_fmt_smooth_wgrad_workspace_bytes(N, C, H, W)
+    ws = torch.empty(max(ws_bytes, 4), dtype=torch.uint8, device=lateral.device)
+    d_w = torch.empty(C, C, 3, 3, dtype=torch.float32, device=lateral.device)
+    check(L.mvs_fmt_smooth_wgrad(ptr(d_y), ptr(prev), ptr(lateral), ptr(w_reduce), ptr(d_w), ptr(ws), ws_bytes, N, C, h, w, H, W,
+                                 stream_of(lateral)), "mvs_fmt_smooth_wgrad")
+    return d_w
+
+
 VITDEC_EPI_F32, VITDEC_EPI_RESID, VITDEC_EPI_GELU_SPLIT = 0, 1, 2
 VITDEC_PROJ, VITDEC_UP0, VITDEC_UP1 = 0, 1, 2
 _VITDEC_CONV = {VITDEC_PROJ: (768, 256, 9, 1), VITDEC_UP0: (256, 128, 4, 4), VITDEC_UP1: (128, 64, 4, 4)}     # Cin, Cout, taps, classes

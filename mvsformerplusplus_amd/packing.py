@@ -238,15 +238,18 @@ FMT_VECTORS = ("norm1.weight", "norm1.bias", "attn.proj.bias", "ls1.gamma", "nor
                "ls2.gamma")
 
 
-def pack_fmt_block(sd: Dict[str, torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
+def pack_fmt_block(sd: Dict[str, torch.Tensor], device="cpu") -> Tuple[torch.Tensor, torch.Tensor]:
     """One CrossBlock of the FMT (keys relative to ``FMT.layers.N.``; d_model 64, hidden 256) -> (packed weights bf16: q_proj | proj | fc1 |
-    fc2 | [k_proj; v_proj], vectors fp32 [768] in the order of FMT_VECTORS): the layout constants FT_W_* / FT_V_* of fmt_kernels.hip."""
+    fc2 | [k_proj; v_proj], vectors fp32 [768] in the order of FMT_VECTORS): the layout constants FT_W_* / FT_V_* of fmt_kernels.hip.
+    Packed on the host by default; device=None packs where the parameters live (plain tensor ops: a training step copies nothing to
+    the host and does not synchronise) and gives the same bits."""
     mats = [sd["attn.q_proj.weight"], sd["attn.proj.weight"], sd["mlp.fc1.weight"], sd["mlp.fc2.weight"],
             torch.cat([sd["attn.k_proj.weight"], sd["attn.v_proj.weight"]], 0)]
     want = [(64, 64), (64, 64), (256, 64), (64, 256), (128, 64)]
     assert [tuple(m.shape) for m in mats] == want, [tuple(m.shape) for m in mats]
-    w = torch.cat([pack_fmt_linear(m.detach().float().cpu()) for m in mats])
-    v = torch.cat([sd[k].detach().float().cpu().reshape(-1) for k in FMT_VECTORS])
+    f32 = (lambda t: t.detach().float()) if device is None else (lambda t: t.detach().float().to(device))
+    w = torch.cat([pack_fmt_linear(f32(m)) for m in mats])
+    v = torch.cat([f32(sd[k]).reshape(-1) for k in FMT_VECTORS])
     assert w.numel() == 12288 * 8 and v.numel() == 768
     return w, v
 

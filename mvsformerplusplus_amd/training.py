@@ -33,6 +33,14 @@ blocks is one autograd node (``TransformerBlockTrain``) whose forward is the inf
 hand-written - the attention core on ``mvs_tr_attention_bwd`` (fp32, no [n, n] tensor), the linears' gradients as plain GEMMs
 (rocBLAS), LayerNorm / GELU / residual-scale gradients as tensor expressions, the FFN hidden layer and the pre-LayerNorm sums
 recomputed; patch embedding / expansion with their LayerNorm3D and `prob` stay PyTorch-ROCm autograd ops.
+
+The feature side receives the cascade's `d features` in ``fmt_forward_train``, the differentiable form of
+``fmt.FMT_with_pathway.forward``: each linear-attention block is one node (``FmtBlockTrain``: forward = the inference launches on weights
+packed on the device, backward hand-written like ``TransformerBlockTrain``'s with only the block's input kept), each pathway level one
+node (``FmtPathLevelTrain``: forward = the fused inference launch; backward = the forward convolution with flipped taps for the
+lateral, ``mvs_fmt_path_bwd`` - the interpolation's exact adjoint as a gather - for the coarse map and the 1x1 weights, and
+``mvs_fmt_smooth_wgrad`` on fp32 MFMA for the 3x3 weights, the merged map recomputed in its staging; no atomics).  The FPN, the ViT and
+its decoder have no training form.
 """
 from __future__ import annotations
 
@@ -41,6 +49,7 @@ from typing import Dict
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
+from torch.autograd.function import once_differentiable
 
 from . import _lib, ops, packing
 
@@ -583,6 +592,177 @@ def transformer_forward_torch(reg, x: torch.Tensor, position3d) -> torch.Tensor:
         t = blk.norm2(t + blk.gamma2 * l2(F.gelu(l1(t))))
     x = t.reshape(B, h, w, d, C).permute(0, 4, 3, 1, 2)
     return reg.prob(_layer_norm_channels(reg.up[0](x), reg.up[1]))
+
+
+# --------------------------------------------------------------------------------------------------
+# FMT_with_pathway (fmt.py): the feature-side module the cascade's `d features` flow into
+# --------------------------------------------------------------------------------------------------
+FMT_BLOCK_PARAMS = ("norm1.weight", "norm1.bias", "attn.q_proj.weight", "attn.k_proj.weight", "attn.v_proj.weight", "attn.proj.weight",
+                    "attn.proj.bias", "ls1.gamma", "norm2.weight", "norm2.bias", "mlp.fc1.weight", "mlp.fc1.bias", "mlp.fc2.weight",
+                    "mlp.fc2.bias", "ls2.gamma")
+
+
+def _tokens(x: torch.Tensor) -> torch.Tensor:
+    """planar [N, 64, ...] -> token-major [N n, 64]"""
+    return x.reshape(x.shape[0], 64, -1).transpose(1, 2).reshape(-1, 64)
+
+
+def _elu1_bwd(d_out, pre, out):
+    """Backward of out = elu(pre) + 1: the derivative is 1 above zero and exp(pre) = out below."""
+    return d_out * torch.where(pre > 0, torch.ones_like(out), out)
+
+
+class FmtBlockTrain(torch.autograd.Function):
+    """One pre-norm CrossBlock with linear attention (fmt.py, tests/fmt_ref.py::block) over N views: x [N,64,h,w] (+ the position table
+    on the first block) -> the same shape.  ref = None: self attention.  ref [N / kv_div, 64, h, w]: cross attention, view i reads the
+    summary of ref[i // kv_div] through this block's own norm1.  Forward = the inference path's launches (fmt_kv + fmt_block) on weights
+    packed on the device from the live parameters, so the outputs are the inference bits.  Kept for the backward: x and ref.  The
+    backward recomputes everything else in fp32 and is hand-written: the linears' gradients are plain GEMMs, LayerNorm / elu / GELU /
+    LayerScale / residual and the linear-attention core (KV_h = sum_s k_s (x) v_s, Z = 1 / (q . sum_s k_s + 1e-6), a = q KV Z) tensor
+    expressions - no autograd graph.  A cross layer's gradient into ref is the sum over the kv_div views that share it."""
+
+    @staticmethod
+    def forward(ctx, x, ref, pe, kv_div, *params):
+        P = [p.detach().float() for p in params]
+        wp, vec = packing.pack_fmt_block(dict(zip(FMT_BLOCK_PARAMS, P)), device=None)
+        x0 = ops._f32c(x.detach())
+        kvt = None if ref is None else ops._f32c(ref.detach())
+        kv = ops.fmt_kv(x0, wp, vec, pe) if kvt is None else ops.fmt_kv(kvt, wp, vec)
+        y = ops.fmt_block(x0, kv, wp, vec, pe, kv_div=kv_div)
+        ctx.save_for_backward(x0, kvt, pe, *P)
+        ctx.kv_div = kv_div
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, d_y):
+        x0p, refp, pe = ctx.saved_tensors[:3]
+        n1w, n1b, wq, wk, wv, wp, bp, g1, n2w, n2b, w1, b1, w2, b2, g2 = ctx.saved_tensors[3:]
+        N, kv_div, eps = x0p.shape[0], ctx.kv_div, 1e-5
+        n = x0p[0, 0].numel()
+        Nr = N // kv_div
+        ln = lambda u, w, b: F.layer_norm(u, (64,), w, b, eps)
+        heads = lambda t, views: t.reshape(Nr, views * n, 4, 16)
+        x0 = _tokens(x0p if pe is None else x0p.reshape(N, 64, n) + pe)
+        dy = _tokens(ops._f32c(d_y))
+        # ---- recompute the forward: attention half (q from the block's tokens, k / v from its own or the reference view's)
+        xn = ln(x0, n1w, n1b)
+        reft = None if refp is None else _tokens(refp)
+        kvn = xn if reft is None else ln(reft, n1w, n1b)
+        qp, kp, v = xn @ wq.t(), kvn @ wk.t(), kvn @ wv.t()
+        q, k = F.elu(qp) + 1, F.elu(kp) + 1
+        qh, kh, vh = heads(q, kv_div), heads(k, 1), heads(v, 1)
+        KV = torch.einsum("bshd,bshm->bhdm", kh, vh)
+        ks = kh.sum(1)
+        Z = 1.0 / (torch.einsum("blhd,bhd->blh", qh, ks) + 1e-6)
+        num = torch.einsum("blhd,bhdm->blhm", qh, KV)
+        a = (num * Z.unsqueeze(-1)).reshape(-1, 64)
+        yp = a @ wp.t() + bp
+        x1 = x0 + g1 * yp
+        # ---- FFN half, forward and backward
+        u = ln(x1, n2w, n2b)
+        pre = u @ w1.t() + b1
+        hdn = F.gelu(pre)
+        y2 = hdn @ w2.t() + b2
+        d_g2, d_y2 = (dy * y2).sum(0), dy * g2
+        d_w2, d_b2 = d_y2.t() @ hdn, d_y2.sum(0)
+        d_pre = (d_y2 @ w2) * (0.5 * (1.0 + torch.erf(pre * 0.7071067811865476)) + pre * torch.exp(-0.5 * pre * pre) * 0.3989422804014327)
+        d_w1, d_b1 = d_pre.t() @ u, d_pre.sum(0)
+        d_x1n, d_n2w, d_n2b = _layer_norm_bwd(d_pre @ w1, x1, n2w, eps)
+        d_x1 = dy + d_x1n
+        # ---- attention half
+        d_g1, d_yp = (d_x1 * yp).sum(0), d_x1 * g1
+        d_wp, d_bp = d_yp.t() @ a, d_yp.sum(0)
+        d_a = heads(d_yp @ wp, kv_div)
+        d_num = d_a * Z.unsqueeze(-1)
+        d_den = -(d_a * num).sum(-1) * Z * Z
+        d_q = torch.einsum("blhm,bhdm->blhd", d_num, KV) + d_den.unsqueeze(-1) * ks.unsqueeze(1)
+        d_KV = torch.einsum("blhd,blhm->bhdm", qh, d_num)
+        d_ks = torch.einsum("blhd,blh->bhd", qh, d_den)
+        d_k = torch.einsum("bhdm,bshm->bshd", d_KV, vh) + d_ks.unsqueeze(1)
+        d_v = torch.einsum("bshd,bhdm->bshm", kh, d_KV).reshape(-1, 64)
+        d_qp, d_kp = _elu1_bwd(d_q.reshape(-1, 64), qp, q), _elu1_bwd(d_k.reshape(-1, 64), kp, k)
+        d_wq, d_wk, d_wv = d_qp.t() @ xn, d_kp.t() @ kvn, d_v.t() @ kvn
+        d_xn, d_kvn = d_qp @ wq, d_kp @ wk + d_v @ wv
+        d_ref = None
+        if reft is None:
+            d_x0n, d_n1w, d_n1b = _layer_norm_bwd(d_xn + d_kvn, x0, n1w, eps)
+        else:
+            d_x0n, d_n1w, d_n1b = _layer_norm_bwd(d_xn, x0, n1w, eps)
+            d_reft, d_n1w_kv, d_n1b_kv = _layer_norm_bwd(d_kvn, reft, n1w, eps)
+            d_n1w, d_n1b = d_n1w + d_n1w_kv, d_n1b + d_n1b_kv
+            d_ref = d_reft.reshape(Nr, n, 64).transpose(1, 2).reshape(refp.shape)
+        d_x = (d_x1 + d_x0n).reshape(N, n, 64).transpose(1, 2).reshape(x0p.shape)
+        return (d_x, d_ref, None, None, d_n1w, d_n1b, d_wq, d_wk, d_wv, d_wp, d_bp, d_g1, d_n2w, d_n2b, d_w1, d_b1, d_w2, d_b2, d_g2)
+
+
+class FmtPathLevelTrain(torch.autograd.Function):
+    """One pathway level Y = S * (U(W_r prev) + lat) for all views (fmt.py, tests/fmt_ref.py::level).  Forward = the fused inference
+    launch (the merged map is never written); kept: prev and lat, which the neighbouring nodes hold anyway.  Backward: d lat = dM on
+    the forward convolution with flipped, channel-transposed taps; d prev and d W_r on mvs_fmt_path_bwd (the interpolation's exact
+    adjoint as a gather); d S on mvs_fmt_smooth_wgrad, which recomputes the merged map in its staging.  No atomics: bit-identical
+    from run to run."""
+
+    @staticmethod
+    def forward(ctx, prev, lat, w_reduce, w_smooth):
+        p, l = ops._f32c(prev.detach()), ops._f32c(lat.detach())
+        wr = w_reduce.detach().float().reshape(w_reduce.shape[0], -1).contiguous()
+        ws = w_smooth.detach().float()
+        ctx.save_for_backward(p, l, wr, ws)
+        ctx.wr_shape = w_reduce.shape
+        return ops.fmt_path(p, l, wr, packing.pack_fpn_conv_weights(ws, 1))
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, d_y):
+        p, l, wr, ws = ctx.saved_tensors
+        d_y = ops._f32c(d_y)
+        d_m = ops.fmt_smooth(d_y, packing.pack_fpn_conv_weights(ws.flip(2, 3).transpose(0, 1), 1))
+        d_prev, d_wr = ops.fmt_path_bwd(d_m, p, wr)
+        return d_prev, d_m, d_wr.reshape(ctx.wr_shape), ops.fmt_smooth_wgrad(d_y, p, l, wr)
+
+
+def fmt_forward_train(module, features: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """FMT_with_pathway.forward with autograd: `module` is an fmt.FMT_with_pathway (train or eval mode; it has no BatchNorm and no
+    dropout, so both compute the same), `features` its stage1..stage4 dictionary of [B, V, 64 | 32 | 16 | 8, ., .] tensors -> the
+    same dictionary of fp32 [B, V, C, H, W] outputs, bit for bit the inference forward's.  One autograd node per launch group
+    (``FmtBlockTrain`` per block and view group, ``FmtPathLevelTrain`` per level), joined by indexing and `cat`.  Gradients reach every
+    input that requires grad, in that input's dtype (fp16 / bf16 inputs are widened once), and the module's 66 parameters.  No double
+    backward."""
+    ts, B, V = module._shapes(features)
+    net = module.FMT
+    names = net.layer_names
+    f1 = ts[0].float()
+    h, w = f1.shape[-2:]
+    pe = net.position_encoding(h, w, f1.device)
+    params = [[blk.get_parameter(k) for k in FMT_BLOCK_PARAMS] for blk in net.layers]
+    # reference view: the self layers only; the tokens after each are the cross layers' keys / values
+    x, refs, first = f1[:, 0], [], pe
+    for i, name in enumerate(names):
+        if name == "self":
+            x = FmtBlockTrain.apply(x, None, first, 1, *params[i])
+            first = None
+            refs.append(x)
+    views = [x.unsqueeze(1)]
+    if V > 1:
+        # every source view of the batch in one node per layer: view b * (V - 1) + j attends to reference view b
+        x, first = f1[:, 1:].reshape(B * (V - 1), 64, h, w), pe
+        for i, name in enumerate(names):
+            if name == "self":
+                x = FmtBlockTrain.apply(x, None, first, 1, *params[i])
+            else:
+                x = FmtBlockTrain.apply(x, refs[i] if len(refs) == len(names) else refs[i // 2], first, V - 1, *params[i])
+            first = None
+        views.append(x.reshape(B, V - 1, 64, h, w))
+    out1 = torch.cat(views, 1)
+    outs = {"stage1": out1}
+    prev = out1.reshape(B * V, 64, h, w)
+    for k in (1, 2, 3):
+        lat = ts[k].float()
+        prev = FmtPathLevelTrain.apply(prev, lat.reshape((B * V,) + tuple(lat.shape[2:])), getattr(module, "dim_reduction_%d" % k).weight,
+                                       getattr(module, "smooth_%d" % k).weight)
+        outs["stage%d" % (k + 1)] = prev.reshape((B, V) + tuple(prev.shape[1:]))
+    return outs
 
 
 _FP32_TRAIN_WARNED = False
