@@ -554,6 +554,41 @@ int mvs_fpn_merge_fwd(const float* prev, const float* lateral, const float* w_in
 int mvs_fpn_merge_conv_fwd(const float* prev, const float* lateral, const float* w_inner, const float* b_inner, const void* w_packed,
                            const float* bias, int act, float* y, int N, int Clat, int Cout, int H, int W, void* stream);
 
+/* ---- FPNDecoder in train mode: out_k = Swish(BatchNorm2d(conv(intra_k) + b)) with batch statistics over
+ * all N H W samples of a channel, and its backward.  The forward convolutions are mvs_fpn_conv_fwd / mvs_fpn_merge_conv_fwd on
+ * un-folded weights with bias = NULL, act 0 (a bias in front of a batch-statistics BatchNorm cancels).  Sums are fp64, left as
+ * per-workgroup partials in `workspace` and added in a fixed order: no atomics, bit-identical run to run.  *_workspace_bytes: 0 = out
+ * of range or not built.
+ * mvs_fpn_bn_swish_fwd: z [N,C,H,W], C <= 64 -> stats [3][C] = mean | biased variance | 1 / sqrt(var + eps) and y = swish(gamma xhat +
+ *   beta); running_mean / running_var (both or neither) take one step of `momentum` with mean + conv_bias (nullable) and the unbiased
+ *   variance, like nn.BatchNorm2d behind a convolution with that bias.
+ * mvs_fpn_bn_swish_bwd: dy, z, stats -> d_beta = sum du, d_gamma = sum du xhat, du = dy (s + u s (1 - s)), u = gamma xhat + beta,
+ *   s = sigmoid(u), and dz = gamma invstd (du - d_beta / M - xhat d_gamma / M), M = N H W.
+ * mvs_fpn_train_conv_fwd: Conv2d(Cin, Cout, k, padding k/2) without bias or activation, the data gradients' instances of the
+ *   convolution (mvs_fpn_train_conv_is_built); w_packed = packing.pack_fpn_conv_weights(w, 1) of the flipped, channel-transposed taps.
+ * mvs_fpn_wgrad: dw [Cout][Cin + ones][k][k] = sum_pixels dy [N,Cout,H,W] (x) x [N,Cin,H,W] shifted by the tap (zero padding), exact fp32
+ *   products (v_mfma_f32_16x16x4_f32).  ones = 1 appends an input channel that is 1 inside the image: dw[:, Cin] is the gradient of a bias
+ *   behind the taps.  Built: (Cout, Cin, k, ones) = (32|16, 64, 3, 0), (64, 64, 1, 0), (64, 32|16, 1, 1), (8, 8, 3, 1).
+ * mvs_fpn_merge_wgrad: the last level's dw [8][64][3][3] with x = up2(prev) + inner(lateral) (mvs_fpn_merge_fwd's map) re-evaluated in
+ *   the kernel's staging and never written.
+ * mvs_fpn_up2_adjoint: d_coarse [N,64,H/2,W/2] = U^T d_fine [N,64,H,W], U = mvs_fpn_merge_fwd's upsample; a gather with the forward's own
+ *   coordinate function (the exact adjoint).  H and W even.                                                                          */
+size_t mvs_fpn_bn_workspace_bytes(int N, int C, int H, int W);
+int mvs_fpn_bn_swish_fwd(const float* z, const float* conv_bias, const float* gamma, const float* beta, float eps, float momentum,
+                         float* running_mean, float* running_var, float* stats, float* y, void* workspace, size_t workspace_bytes, int N, int C,
+                         int H, int W, void* stream);
+int mvs_fpn_bn_swish_bwd(const float* dy, const float* z, const float* stats, const float* gamma, const float* beta, float* dz, float* d_gamma,
+                         float* d_beta, void* workspace, size_t workspace_bytes, int N, int C, int H, int W, void* stream);
+int mvs_fpn_train_conv_is_built(int Cin, int Cout, int k);
+int mvs_fpn_train_conv_fwd(const float* x, const void* w_packed, float* y, int N, int Cin, int Cout, int k, int H, int W, void* stream);
+size_t mvs_fpn_wgrad_workspace_bytes(int N, int Cin, int Cout, int k, int ones, int H, int W);
+int mvs_fpn_wgrad(const float* dy, const float* x, float* dw, void* workspace, size_t workspace_bytes, int N, int Cin, int Cout, int k, int ones,
+                  int H, int W, void* stream);
+size_t mvs_fpn_merge_wgrad_workspace_bytes(int N, int H, int W);
+int mvs_fpn_merge_wgrad(const float* dy, const float* prev, const float* lateral, const float* w_inner, const float* b_inner, float* dw,
+                        void* workspace, size_t workspace_bytes, int N, int H, int W, void* stream);
+int mvs_fpn_up2_adjoint(const float* d_fine, float* d_coarse, int N, int H, int W, void* stream);
+
 /* ==== FMT_with_pathway: stage-1 linear attention + pathway ============================================
  * models/FMT.py:35-206 with the shipped FMT_config (Linear attention, d_model 64, 4 heads, ffn, pre-norm, LayerScale).  Token
  * tensors are the feature maps themselves: planar fp32 [N, 64, n], n = h w.  Split-bf16 three-term MFMA GEMMs (fp32-equivalent);

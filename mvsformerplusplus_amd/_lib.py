@@ -124,6 +124,16 @@ SIGNATURES = {
     "mvs_fpn_conv_fwd": (_i, [_vp, _vp, _vp, _i, _vp] + [_i] * 7 + [_vp]),
     "mvs_fpn_merge_fwd": (_i, [_vp] * 5 + [_i] * 4 + [_vp]),
     "mvs_fpn_merge_conv_fwd": (_i, [_vp] * 6 + [_i, _vp] + [_i] * 5 + [_vp]),
+    "mvs_fpn_bn_workspace_bytes": (_sz, [_i] * 4),
+    "mvs_fpn_bn_swish_fwd": (_i, [_vp] * 4 + [_f, _f] + [_vp] * 5 + [_sz] + [_i] * 4 + [_vp]),
+    "mvs_fpn_bn_swish_bwd": (_i, [_vp] * 9 + [_sz] + [_i] * 4 + [_vp]),
+    "mvs_fpn_train_conv_is_built": (_i, [_i] * 3),
+    "mvs_fpn_train_conv_fwd": (_i, [_vp] * 3 + [_i] * 6 + [_vp]),
+    "mvs_fpn_wgrad_workspace_bytes": (_sz, [_i] * 7),
+    "mvs_fpn_wgrad": (_i, [_vp] * 4 + [_sz] + [_i] * 7 + [_vp]),
+    "mvs_fpn_merge_wgrad_workspace_bytes": (_sz, [_i] * 3),
+    "mvs_fpn_merge_wgrad": (_i, [_vp] * 7 + [_sz] + [_i] * 3 + [_vp]),
+    "mvs_fpn_up2_adjoint": (_i, [_vp, _vp] + [_i] * 3 + [_vp]),
     "mvs_fmt_weights_bytes": (_sz, []),
     "mvs_fmt_vectors_bytes": (_sz, []),
     "mvs_fmt_kv_operand_bytes": (_sz, []),

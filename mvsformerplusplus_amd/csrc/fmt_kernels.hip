@@ -29,9 +29,10 @@
 //      (conv2d_source_kernel on FtMergeSrc) + the same convolution on PlanarSrc are the unfused form.
 //   4. the pathway's backward (further down): fmt_path_bwd_kernel (the interpolation's adjoint as a gather, d prev,
 //      the partials of d W_r), fmt_smooth_wgrad_kernel (d S on v_mfma_f32_16x16x4_f32 with the merged map re-evaluated in LDS) and
-//      fmt_partial_reduce_kernel (fixed-order sum of the partials).  The blocks' backward is not in this file (training.py).
+//      fmt_partial_reduce_kernel (fixed-order sum of the partials, partial_reduce.h).  The blocks' backward is not in this file (training.py).
 // Staged positions are clamped to the image explicitly (zero padding from a branch, never from an out-of-range load).
 #include "conv2d_split.h"
+#include "partial_reduce.h"
 
 namespace mvs {
 
@@ -422,7 +423,6 @@ static bool ft_path_args(const char* what, int N, int C, int H, int W) {
 // gradients leave each workgroup as one fp32 partial; fmt_partial_reduce_kernel adds the partials in a fixed order (no atomics).
 // ---------------------------------------------------------------------------------------------------------------------------------
 constexpr int FT_BWD_PIX = 256;               // coarse pixels per workgroup pass of fmt_path_bwd_kernel
-constexpr int FT_RED_SEG = 16;                // segments of consecutive partials per output element in the reduction
 
 // partials (= workgroups) of one launch: bounded, so that the reduction's chains stay short (8192 / C: 256 | 512 | 1024)
 static int ft_bwd_parts(long long work, int C) {
@@ -625,31 +625,6 @@ __global__ __launch_bounds__(256) void fmt_smooth_wgrad_kernel(FtMergeSrc<C> src
                 if (co < C) dst[co * F::NCOL + col] = acc[rb][t][r];
             }
     }
-}
-
-// out[e] = the sum of part[p][e] over the launch's partials in a fixed order: FT_RED_SEG segments of consecutive partials, each added
-// front to back by one thread, then the segment sums front to back.
-__global__ __launch_bounds__(256) void fmt_partial_reduce_kernel(const float* __restrict__ part, float* __restrict__ out, int nparts, int nelem) {
-    HIP_DYNAMIC_SHARED(float4, lds4)
-    float* seg = reinterpret_cast<float*>(lds4);                  // [FT_RED_SEG][16]
-    const int tid = (int)threadIdx.x, e = (int)blockIdx.x * 16 + (tid & 15), s = tid >> 4;
-    const int per = (nparts + FT_RED_SEG - 1) / FT_RED_SEG, p0 = s * per, p1 = p0 + per < nparts ? p0 + per : nparts;
-    float sum = 0.0f;
-    if (e < nelem)
-        for (int p = p0; p < p1; ++p) sum += part[(size_t)p * nelem + e];
-    seg[tid] = sum;
-    __syncthreads();
-    if (tid < 16 && e < nelem) {
-        float t = seg[tid];
-#pragma unroll
-        for (int k = 1; k < FT_RED_SEG; ++k) t += seg[k * 16 + tid];
-        out[e] = t;
-    }
-}
-
-static int ft_reduce_partials(const float* part, float* out, int nparts, int nelem, hipStream_t st) {
-    hipLaunchKernelGGL(fmt_partial_reduce_kernel, dim3(ceil_div(nelem, 16)), dim3(256), 256 * sizeof(float), st, part, out, nparts, nelem);
-    return check_launch("fmt_partial_reduce_kernel");
 }
 
 static bool ft_level_built(int C) { return C == 32 || C == 16 || C == 8; }

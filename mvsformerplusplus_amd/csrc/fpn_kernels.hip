@@ -6,8 +6,8 @@
 // FPNDecoder: out0 = Swish(BN(1x1 64->64)); intra_k = up2(intra_{k-1}) + inner_k(lateral_k), inner_k = 1x1 conv with bias, up2 =
 // F.interpolate(scale_factor=2, bilinear, align_corners=True) in fp32; out_k = Swish(BN(3x3 64->Ck))).
 //
-// Three kernels, all instances of the templates in conv2d_split.h (this file holds MergeSrc, the list of built layers and the entry
-// points):
+// Three kernels, all instances of the templates in conv2d_split.h (this file holds the list of built layers and the entry points;
+// MergeSrc is in fpn_merge.h, which the training kernels of fpn_train_kernels.hip share):
 //   1. the convolution (reported as fpn_conv_kernel): conv2d_split_kernel<Cin, Cout, k, stride, PlanarSrc, PlanarSink<true>> - Conv2d(k = 1 |
 //      3 | 5 | 7, stride 1 | 2, padding k/2) with the BatchNorm folded on the host into weights + bias, then none | Swish |
 //      LeakyReLU(0.1); planar fp32 in and out, split-bf16 three-term MFMA (fp32-equivalent).  Cin = 3 is staged as one octet with
@@ -19,63 +19,7 @@
 //      tile and its halo on the fly, so the full-resolution 64-channel intra3 is never written (453 MB write + read per view at
 //      1152 x 1536 in fp32).
 // Staged positions are clamped to the image explicitly (zero padding from a branch, never from an out-of-range load).
-#include "conv2d_split.h"
-
-namespace mvs {
-
-// intra[c] at a full-resolution pixel = up2(prev)[c] + b[c] + sum_ci w[c][ci] * lat[ci]; prev [N, 64, H/2, W/2], lat [N, CLAT, H, W]
-template <int CLAT>
-struct MergeSrc {
-    static constexpr int STAGE_OCTETS = 0;
-    const float* prev;
-    const float* lat;
-    const float* w;          // [64][CLAT]
-    const float* b;          // [64]
-    int H, W, h, w2;         // full resolution; prev is h x w2 (H = 2h, W = 2 w2)
-    float sy, sx;            // align_corners=True source scale (h - 1) / (H - 1), in fp32 like F.interpolate on fp32 input
-    float l[CLAT];
-    const float* pp;
-    int dy, dx;
-    float ly, lx;
-    __device__ __forceinline__ void at(int n, int gy, int gx) {
-        const size_t HW = (size_t)H * W;
-        const float* lp = lat + (size_t)n * CLAT * HW + (size_t)gy * W + gx;
-#pragma unroll
-        for (int ci = 0; ci < CLAT; ++ci) l[ci] = lp[(size_t)ci * HW];
-        const float fy = sy * (float)gy, fx = sx * (float)gx;
-        const int y0 = (int)fy, x0 = (int)fx;
-        ly = fy - (float)y0;
-        lx = fx - (float)x0;
-        dy = y0 < h - 1 ? w2 : 0;
-        dx = x0 < w2 - 1 ? 1 : 0;
-        pp = prev + (size_t)n * 64 * h * w2 + (size_t)y0 * w2 + x0;
-    }
-    __device__ __forceinline__ void load8(int c0, float* v) const {
-        const size_t hw = (size_t)h * w2;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            const int c = c0 + k;
-            const float* q = pp + (size_t)c * hw;
-            const float up = (1.0f - ly) * ((1.0f - lx) * q[0] + lx * q[dx]) + ly * ((1.0f - lx) * q[dy] + lx * q[dy + dx]);
-            float s = b[c];
-#pragma unroll
-            for (int ci = 0; ci < CLAT; ++ci) s = fmaf(w[c * CLAT + ci], l[ci], s);
-            v[k] = up + s;
-        }
-    }
-};
-
-template <int CLAT>
-static MergeSrc<CLAT> merge_src(const float* prev, const float* lat, const float* w, const float* b, int H, int W) {
-    MergeSrc<CLAT> s{};
-    s.prev = prev; s.lat = lat; s.w = w; s.b = b;
-    s.H = H; s.W = W; s.h = H / 2; s.w2 = W / 2;
-    s.sy = H > 1 ? (float)(s.h - 1) / (float)(H - 1) : 0.0f;
-    s.sx = W > 1 ? (float)(s.w2 - 1) / (float)(W - 1) : 0.0f;
-    return s;
-}
-
-}  // namespace mvs
+#include "fpn_merge.h"
 
 using namespace mvs;
 

@@ -9,6 +9,7 @@ full-resolution map is never written.
 Outputs are fp32 planar ``[N, C, H, W]``.  Under the reference's bf16 autocast (``test.py:250``) its own modules return bf16; these
 return the fp32-equivalent values (inputs in bf16 are widened once).  Inference only: ``train()`` mode or an input that requires
 grad raises.  ``patch_fpn(model)`` swaps a model's ``encoder`` / ``decoder`` for these and leaves everything else alone.
+``TrainableFPNDecoder`` (``patch_fpn(model, trainable_decoder=True)``) adds the decoder's train mode.
 """
 from __future__ import annotations
 
@@ -142,14 +143,18 @@ class FPNDecoder(nn.Module):
             return p
         return self._cache.get(self, build)
 
-    def forward(self, conv01: torch.Tensor, conv11: torch.Tensor, conv21: torch.Tensor, conv31: torch.Tensor) -> List[torch.Tensor]:
-        _check_inference(self, conv01, conv11, conv21, conv31)
+    @staticmethod
+    def _check_inputs(conv01, conv11, conv21, conv31):
         N, _, h, w = conv31.shape
         want = [(N, 8, 8 * h, 8 * w), (N, 16, 4 * h, 4 * w), (N, 32, 2 * h, 2 * w), (N, 64, h, w)]
         got = [tuple(t.shape) for t in (conv01, conv11, conv21, conv31)]
         if got != want:
             raise ValueError("FPNDecoder takes the encoder's [conv01, conv11, conv21, conv31] (8 / 16 / 32 / 64 channels, each level twice "
                              "the next one's size); got %s" % got)
+
+    def forward(self, conv01: torch.Tensor, conv11: torch.Tensor, conv21: torch.Tensor, conv31: torch.Tensor) -> List[torch.Tensor]:
+        _check_inference(self, conv01, conv11, conv21, conv31)
+        self._check_inputs(conv01, conv11, conv21, conv31)
         with torch.no_grad():
             p = self._params(conv31.device)
             out0 = ops.fpn_conv(conv31, *p["out0"], 64, 1, 1, ops.FPN_ACT_SWISH)
@@ -162,20 +167,40 @@ class FPNDecoder(nn.Module):
             return [out0, out1, out2, out3]
 
 
+class TrainableFPNDecoder(FPNDecoder):
+    """FPNDecoder with a train mode: the same constructor and state-dict keys.  In train mode its forward is
+    ``training.fpn_decoder_forward_train`` (batch-statistics BatchNorm, running statistics updated, gradients for the inputs and all 22
+    parameters).  In eval mode under no_grad it is FPNDecoder.forward, bit for bit.  Eval mode with inputs that require grad - fine-tuning
+    through frozen BatchNorm statistics - is not built and raises."""
+
+    def forward(self, conv01: torch.Tensor, conv11: torch.Tensor, conv21: torch.Tensor, conv31: torch.Tensor) -> List[torch.Tensor]:
+        if self.training:
+            from .training import fpn_decoder_forward_train
+            return fpn_decoder_forward_train(self, conv01, conv11, conv21, conv31)
+        if torch.is_grad_enabled() and any(x.requires_grad for x in (conv01, conv11, conv21, conv31)):
+            raise RuntimeError("TrainableFPNDecoder in eval() mode has no autograd: gradients through frozen (running-statistics) BatchNorm are "
+                               "not built; call .train() for batch-statistics training, or run eval() under torch.no_grad()")
+        return super().forward(conv01, conv11, conv21, conv31)
+
+
 def _feat_chs_of(enc: nn.Module) -> List[int]:
     return [enc.conv00.conv.out_channels, enc.downsample1.conv.out_channels, enc.downsample2.conv.out_channels,
             enc.downsample3.conv.out_channels]
 
 
-def patch_fpn(model: nn.Module) -> nn.Module:
+def patch_fpn(model: nn.Module, trainable_decoder: bool = False) -> nn.Module:
     """Swap ``model.encoder`` / ``model.decoder`` (the reference's FPNEncoder / FPNDecoder) for the native modules: parameters carried
     over by ``load_state_dict(strict=True)``, device and train / eval mode preserved.  The ViT, CrossVITDecoder, FMT, the
-    ``conv31 + vit_feat`` add and the fusions are left as they are.  Returns ``model``: ``model = patch_fpn(patch_model(model))``."""
+    ``conv31 + vit_feat`` add and the fusions are left as they are.  Returns ``model``: ``model = patch_fpn(patch_model(model))``.
+    trainable_decoder=True installs ``TrainableFPNDecoder`` as the decoder and leaves ``model.encoder`` untouched: the native encoder
+    cannot train, so the reference's stays."""
     enc, dec = model.encoder, model.decoder
     if not isinstance(enc.conv00.bn, nn.BatchNorm2d):
         raise NotImplementedError("patch_fpn: the encoder's norm is %s; the native FPNEncoder folds BatchNorm2d (norm_type='BN')" % type(enc.conv00.bn).__name__)
     feat_chs = _feat_chs_of(enc)
-    for name, old, new in (("encoder", enc, FPNEncoder(feat_chs)), ("decoder", dec, FPNDecoder(feat_chs))):
+    swaps = (("decoder", dec, TrainableFPNDecoder(feat_chs)),) if trainable_decoder else \
+        (("encoder", enc, FPNEncoder(feat_chs)), ("decoder", dec, FPNDecoder(feat_chs)))
+    for name, old, new in swaps:
         new.load_state_dict(old.state_dict(), strict=True)
         ref = next(old.parameters())
         new = new.to(ref.device).train(old.training)

@@ -142,6 +142,105 @@ def fpn_merge_conv(prev: torch.Tensor, lateral: torch.Tensor, w_inner: torch.Ten
     return out
 
 
+# ---- FPNDecoder in train mode ----
+def _fpn_ws(nbytes: int, like: torch.Tensor, what: str) -> torch.Tensor:
+    if not nbytes:
+        raise _lib.MvsHipError("%s: not built for these arguments (or out of range)" % what)
+    return torch.empty(nbytes, dtype=torch.uint8, device=like.device)
+
+
+def fpn_bn_swish_fwd(z: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float, conv_bias: Optional[torch.Tensor] = None,
+                     running_mean: Optional[torch.Tensor] = None, running_var: Optional[torch.Tensor] = None,
+                     momentum: float = 0.0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Batch-statistics BatchNorm2d + Swish of a planar fp32 map z [N,C,H,W] (C <= 64) -> (y, stats [3, C] = mean | biased variance |
+    invstd).  Given running_mean / running_var (fp32, contiguous; updated in place), one step of `momentum` with mean + conv_bias and the
+    unbiased variance - what nn.BatchNorm2d does behind a convolution with that bias.  Sums in fp64, fixed order."""
+    z = _planar32(z)
+    N, C, H, W = z.shape
+    L = lib()
+    ws = _fpn_ws(L.mvs_fpn_bn_workspace_bytes(N, C, H, W), z, "mvs_fpn_bn_swish_fwd")
+    stats, y = torch.empty(3, C, dtype=torch.float32, device=z.device), torch.empty_like(z)
+    check(L.mvs_fpn_bn_swish_fwd(ptr(z), ptr(conv_bias), ptr(gamma), ptr(beta), float(eps), float(momentum), ptr(running_mean), ptr(running_var),
+                                 ptr(stats), ptr(y), ptr(ws), ws.numel(), N, C, H, W, stream_of(z)), "mvs_fpn_bn_swish_fwd")
+    return y, stats
+
+
+def fpn_bn_swish_bwd(d_y: torch.Tensor, z: torch.Tensor, stats: torch.Tensor, gamma: torch.Tensor,
+                     beta: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Backward of fpn_bn_swish_fwd -> (d_z, d_gamma, d_beta)."""
+    z, d_y = _planar32(z), _planar32(d_y)
+    if d_y.shape != z.shape:
+        raise ValueError("d_y must have z's shape %s; got %s" % (tuple(z.shape), tuple(d_y.shape)))
+    N, C, H, W = z.shape
+    L = lib()
+    ws = _fpn_ws(L.mvs_fpn_bn_workspace_bytes(N, C, H, W), z, "mvs_fpn_bn_swish_bwd")
+    d_z = torch.empty_like(z)
+    d_gamma, d_beta = torch.empty(C, dtype=torch.float32, device=z.device), torch.empty(C, dtype=torch.float32, device=z.device)
+    check(L.mvs_fpn_bn_swish_bwd(ptr(d_y), ptr(z), ptr(stats), ptr(gamma), ptr(beta), ptr(d_z), ptr(d_gamma), ptr(d_beta), ptr(ws), ws.numel(),
+                                 N, C, H, W, stream_of(z)), "mvs_fpn_bn_swish_bwd")
+    return d_z, d_gamma, d_beta
+
+
+def fpn_train_conv_is_built(cin: int, cout: int, k: int) -> bool:
+    return bool(lib().mvs_fpn_train_conv_is_built(int(cin), int(cout), int(k)))
+
+
+def fpn_train_conv(x: torch.Tensor, w: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Conv2d(Cin, Cout, k, padding k//2) of a planar map without bias or activation, w [Cout, Cin, k, k] fp32 (packed here, on its
+    device): the FPNDecoder's data gradients (fpn_train_conv_is_built)."""
+    x = _planar32(x)
+    N, cin, H, W = x.shape
+    cout, k = w.shape[0], w.shape[2]
+    assert w.shape[1] == cin and w.shape[3] == k, (tuple(w.shape), cin)
+    if out is None:
+        out = torch.empty(N, cout, H, W, dtype=torch.float32, device=x.device)
+    assert out.shape == (N, cout, H, W) and out.dtype == torch.float32
+    wp = packing.pack_fpn_conv_weights(w, 1)
+    check(lib().mvs_fpn_train_conv_fwd(ptr(x), ptr(wp), ptr(out), N, cin, cout, k, H, W, stream_of(x)), "mvs_fpn_train_conv_fwd")
+    return out
+
+
+def fpn_wgrad(d_y: torch.Tensor, x: torch.Tensor, k: int, ones: bool = False) -> torch.Tensor:
+    """d_w [Cout, Cin (+ 1), k, k] = the correlation of d_y [N,Cout,H,W] with x [N,Cin,H,W] (zero padding k//2), exact fp32 products;
+    ones appends an input channel that is 1 inside the image (d_w[:, Cin] = the gradient of a bias behind the taps).  Deterministic."""
+    d_y, x = _planar32(d_y), _planar32(x)
+    N, cout, H, W = d_y.shape
+    cin = x.shape[1]
+    assert x.shape == (N, cin, H, W), (tuple(d_y.shape), tuple(x.shape))
+    L = lib()
+    ws = _fpn_ws(L.mvs_fpn_wgrad_workspace_bytes(N, cin, cout, int(k), int(ones), H, W), x, "mvs_fpn_wgrad (Cout %d, Cin %d, k %d, ones %d)"
+                 % (cout, cin, k, ones))
+    d_w = torch.empty(cout, cin + int(ones), k, k, dtype=torch.float32, device=x.device)
+    check(L.mvs_fpn_wgrad(ptr(d_y), ptr(x), ptr(d_w), ptr(ws), ws.numel(), N, cin, cout, int(k), int(ones), H, W, stream_of(x)), "mvs_fpn_wgrad")
+    return d_w
+
+
+def fpn_merge_wgrad(d_y: torch.Tensor, prev: torch.Tensor, lateral: torch.Tensor, w_inner: torch.Tensor, b_inner: torch.Tensor) -> torch.Tensor:
+    """Weight gradient [8, 64, 3, 3] of the decoder's last 3x3 convolution: the correlation of d_y [N,8,H,W] with fpn_merge(prev, lateral,
+    ...), which is re-evaluated inside the kernel and never written."""
+    d_y, prev, lateral = _planar32(d_y), _planar32(prev), _planar32(lateral)
+    N, clat, H, W = lateral.shape
+    assert clat == 8 and prev.shape == (N, 64, H // 2, W // 2) and d_y.shape == (N, 8, H, W), (tuple(prev.shape), tuple(lateral.shape), tuple(d_y.shape))
+    L = lib()
+    ws = _fpn_ws(L.mvs_fpn_merge_wgrad_workspace_bytes(N, H, W), lateral, "mvs_fpn_merge_wgrad")
+    d_w = torch.empty(8, 64, 3, 3, dtype=torch.float32, device=lateral.device)
+    check(L.mvs_fpn_merge_wgrad(ptr(d_y), ptr(prev), ptr(lateral), ptr(_planar32(w_inner)), ptr(_planar32(b_inner)), ptr(d_w), ptr(ws), ws.numel(),
+                                N, H, W, stream_of(lateral)), "mvs_fpn_merge_wgrad")
+    return d_w
+
+
+def fpn_up2_adjoint(d_fine: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The adjoint of fpn_merge's upsample: d_fine [N,64,H,W] -> [N,64,H/2,W/2], a gather over the forward's own taps."""
+    d_fine = _planar32(d_fine)
+    N, C, H, W = d_fine.shape
+    assert C == 64 and H % 2 == 0 and W % 2 == 0, tuple(d_fine.shape)
+    if out is None:
+        out = torch.empty(N, 64, H // 2, W // 2, dtype=torch.float32, device=d_fine.device)
+    assert out.shape == (N, 64, H // 2, W // 2) and out.dtype == torch.float32
+    check(lib().mvs_fpn_up2_adjoint(ptr(d_fine), ptr(out), N, H, W, stream_of(d_fine)), "mvs_fpn_up2_adjoint")
+    return out
+
+
 def _fmt_tokens(x: torch.Tensor) -> torch.Tensor:
     x = _planar32(x)
     if x.dim() < 3 or x.shape[1] != 64:

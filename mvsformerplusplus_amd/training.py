@@ -39,8 +39,10 @@ The feature side receives the cascade's `d features` in ``fmt_forward_train`` (D
 packed on the device, backward hand-written like ``TransformerBlockTrain``'s with only the block's input kept), each pathway level one
 node (``FmtPathLevelTrain``: forward = the fused inference launch; backward = the forward convolution with flipped taps for the
 lateral, ``mvs_fmt_path_bwd`` - the interpolation's exact adjoint as a gather - for the coarse map and the 1x1 weights, and
-``mvs_fmt_smooth_wgrad`` on fp32 MFMA for the 3x3 weights, the merged map recomputed in its staging; no atomics).  The FPN, the ViT and
-its decoder have no training form.
+``mvs_fmt_smooth_wgrad`` on fp32 MFMA for the 3x3 weights, the merged map recomputed in its staging; no atomics).  Its input gradients
+go on into ``fpn_decoder_forward_train``, the train-mode FPNDecoder: planar batch-statistics BatchNorm + Swish,
+weight gradients on fp32 MFMA, the upsample's adjoint as a gather, the last level fused so that its 64-channel full-resolution map is
+never written in either direction.  The FPN encoder, the ViT and its decoder have no training form.
 """
 from __future__ import annotations
 
@@ -763,6 +765,151 @@ def fmt_forward_train(module, features: Dict[str, torch.Tensor]) -> Dict[str, to
                                        getattr(module, "smooth_%d" % k).weight)
         outs["stage%d" % (k + 1)] = prev.reshape((B, V) + tuple(prev.shape[1:]))
     return outs
+
+
+# --------------------------------------------------------------------------------------------------
+# FPNDecoder (features.py): where fmt_forward_train's input gradients go
+# --------------------------------------------------------------------------------------------------
+def _fpn_bn_swish(z, bn, conv_bias, gamma, beta):
+    """Train-mode BatchNorm2d + Swish of the pre-activation z = conv(x) WITHOUT its bias: batch statistics (the bias cancels in
+    z - mean), one momentum step of the running statistics with mean + bias and the unbiased variance, num_batches_tracked + 1."""
+    rm, rv, momentum = bn.running_mean, bn.running_var, 0.0
+    if rm is not None:
+        if rm.dtype != torch.float32 or not rm.is_contiguous() or not rv.is_contiguous():
+            raise NotImplementedError("FPNDecoder training: BatchNorm running statistics must be contiguous fp32 buffers")
+        with torch.no_grad():
+            bn.num_batches_tracked += 1
+        momentum = float(bn.momentum) if bn.momentum is not None else 1.0 / float(bn.num_batches_tracked)
+    return ops.fpn_bn_swish_fwd(z, gamma, beta, bn.eps, conv_bias if rm is not None else None, rm, rv, momentum)
+
+
+def _fpn_vec(p):
+    return p.detach().float().contiguous()
+
+
+class FpnHeadTrain(torch.autograd.Function):
+    """out_k = Swish(BatchNorm2d(Conv2d(64, C_k, 1 | 3)(x) + b)) in train mode for k = 0, 1, 2 (module.py:246-252).  Forward: the inference
+    convolution on the un-folded weights, then the planar batch-statistics BatchNorm + Swish.  Kept: x (which the neighbouring merge node
+    holds anyway), the pre-activation z (C_k channels) and the statistics.  Backward: mvs_fpn_bn_swish_bwd, the weight gradient on fp32
+    MFMA, the data gradient on the forward convolution with flipped, channel-transposed taps.  The conv bias sits in front of a
+    batch-statistics BatchNorm: its gradient is exactly zero and is returned as zeros."""
+
+    @staticmethod
+    def forward(ctx, x, bn, w, b, gamma, beta):
+        x0, w32, g, bt = ops._f32c(x.detach()), w.detach().float(), _fpn_vec(gamma), _fpn_vec(beta)
+        k = w32.shape[2]
+        z = ops.fpn_conv(x0, packing.pack_fpn_conv_weights(w32, 1), None, w32.shape[0], k, 1, ops.FPN_ACT_NONE)
+        y, stats = _fpn_bn_swish(z, bn, _fpn_vec(b), g, bt)
+        ctx.save_for_backward(x0, z, stats, w32, g, bt)
+        ctx.b_like = (b.shape, b.dtype)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, d_y):
+        x0, z, stats, w32, g, bt = ctx.saved_tensors
+        d_z, d_g, d_b = ops.fpn_bn_swish_bwd(d_y, z, stats, g, bt)
+        d_w = ops.fpn_wgrad(d_z, x0, w32.shape[2])
+        d_x = ops.fpn_train_conv(d_z, w32.flip(2, 3).transpose(0, 1).contiguous()) if ctx.needs_input_grad[0] else None
+        return d_x, None, d_w, torch.zeros(ctx.b_like[0], dtype=ctx.b_like[1], device=d_z.device), d_g, d_b
+
+
+class FpnMergeTrain(torch.autograd.Function):
+    """intra_k = up2(prev) + inner_k(lat) for k = 1, 2 (module.py:262-266): the inference launch forward; kept: lat.  Backward: d prev on
+    mvs_fpn_up2_adjoint (the upsample's exact adjoint as a gather), d lat = W_inner^T d intra as a 1x1 convolution, d W_inner | d b_inner
+    in one fp32-MFMA weight-gradient launch (the bias is its column of ones)."""
+
+    @staticmethod
+    def forward(ctx, prev, lat, wi, bi):
+        l = ops._f32c(lat.detach())
+        wi2 = wi.detach().float().reshape(wi.shape[0], -1).contiguous()
+        ctx.save_for_backward(l, wi2)
+        ctx.wi_shape = wi.shape
+        return ops.fpn_merge(ops._f32c(prev.detach()), l, wi2, _fpn_vec(bi))
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, d_intra):
+        l, wi2 = ctx.saved_tensors
+        d = ops._f32c(d_intra)
+        clat = l.shape[1]
+        d_prev = ops.fpn_up2_adjoint(d) if ctx.needs_input_grad[0] else None
+        d_lat = ops.fpn_train_conv(d, wi2.t().reshape(clat, 64, 1, 1).contiguous()) if ctx.needs_input_grad[1] else None
+        d_wb = ops.fpn_wgrad(d, l, 1, ones=True).reshape(64, clat + 1)
+        return d_prev, d_lat, d_wb[:, :clat].reshape(ctx.wi_shape), d_wb[:, clat].contiguous()
+
+
+class FpnLevel3Train(torch.autograd.Function):
+    """out3 = Swish(BatchNorm2d(Conv2d(64, 8, 3)(up2(prev) + inner3(lat)) + b)) in train mode, merge and head in one node (module.py:267-268).
+    Neither the 64-channel full-resolution intra3 nor its gradient ever exists as a whole tensor.  Forward: the fused inference launch
+    (intra3 evaluated in the convolution's staging) -> z [N,8,H,W], then BatchNorm + Swish.  Backward, with dz from mvs_fpn_bn_swish_bwd:
+      d W_out3   mvs_fpn_merge_wgrad, intra3 re-evaluated in its staging;
+      d lat      = W_inner^T conv^T(dz): a 1x1 after a 3x3 composes exactly, borders included -> ONE 8 -> 8 3x3 convolution of dz;
+      d W_inner, d b_inner = sum_p d intra3 (x) [lat | 1] = the contraction of W_out3 with the 8 x 9 x 3 x 3 correlation of dz with [lat | 1]
+                 (one small weight-gradient launch; the contraction is a 64 x 9 x 72 product);
+      d prev     = up2^T(conv^T(dz)), one view at a time: the view's d intra3 slab (conv^T, 8 -> 64) is gathered into d prev and reused."""
+
+    @staticmethod
+    def forward(ctx, prev, lat, bn, wi, bi, w, b, gamma, beta):
+        p, l = ops._f32c(prev.detach()), ops._f32c(lat.detach())
+        wi2, bi1 = wi.detach().float().reshape(64, 8).contiguous(), _fpn_vec(bi)
+        w32, g, bt = w.detach().float(), _fpn_vec(gamma), _fpn_vec(beta)
+        z = ops.fpn_merge_conv(p, l, wi2, bi1, packing.pack_fpn_conv_weights(w32, 1), None, 8, ops.FPN_ACT_NONE)
+        y, stats = _fpn_bn_swish(z, bn, _fpn_vec(b), g, bt)
+        ctx.save_for_backward(p, l, z, stats, wi2, bi1, w32, g, bt)
+        ctx.like = (wi.shape, b.shape, b.dtype)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, d_y):
+        p, l, z, stats, wi2, bi1, w32, g, bt = ctx.saved_tensors
+        d_z, d_g, d_b = ops.fpn_bn_swish_bwd(d_y, z, stats, g, bt)
+        d_w = ops.fpn_merge_wgrad(d_z, p, l, wi2, bi1)
+        corr = ops.fpn_wgrad(d_z, l, 3, ones=True).double()                                # [8, 8 + 1, 3, 3]
+        w64 = w32.double()
+        d_wi = torch.einsum("cokl,cikl->oi", w64, corr[:, :8]).float().reshape(ctx.like[0])
+        d_bi = torch.einsum("cokl,ckl->o", w64, corr[:, 8]).float()
+        wd = w32.flip(2, 3).transpose(0, 1).contiguous()                                   # conv^T: dz (8) -> d intra3 (64)
+        d_lat = None
+        if ctx.needs_input_grad[1]:
+            d_lat = ops.fpn_train_conv(d_z, torch.einsum("oi,ockl->ickl", wi2.double(), wd.double()).float().contiguous())
+        d_prev = None
+        if ctx.needs_input_grad[0]:
+            d_prev = torch.empty_like(p)
+            slab = torch.empty((1, 64) + tuple(l.shape[2:]), dtype=torch.float32, device=l.device)
+            for n in range(l.shape[0]):
+                ops.fpn_up2_adjoint(ops.fpn_train_conv(d_z[n:n + 1], wd, out=slab), out=d_prev[n:n + 1])
+        return (d_prev, d_lat, None, d_wi, d_bi, d_w, torch.zeros(ctx.like[1], dtype=ctx.like[2], device=d_z.device), d_g, d_b)
+
+
+def fpn_decoder_forward_train(module, conv01, conv11, conv21, conv31):
+    """FPNDecoder.forward in train mode with autograd: `module` is a features.FPNDecoder (feat_chs [8, 16, 32, 64]), the inputs the
+    encoder's [N, 8 | 16 | 32 | 64, ...] maps -> [out0, out1, out2, out3], fp32 contiguous [N, 64 | 32 | 16 | 8, ...].  nn.BatchNorm2d's
+    train-mode semantics: every head normalises with the batch mean and biased variance of its channels over all N H W samples (the
+    reference's training branch calls the decoder once on [B V, ...]), the running statistics take one momentum step (unbiased variance;
+    running_mean includes the conv bias although the kernels drop it where it cancels) and num_batches_tracked grows by one.  One autograd
+    node per head (``FpnHeadTrain``), per merge (``FpnMergeTrain``) and one for the fused last level (``FpnLevel3Train``).  Gradients
+    reach every input that requires grad, in that input's dtype (fp16 / bf16 inputs are widened once), and all 22 parameters; the four
+    ``out_k.0.bias`` sit in front of a batch-statistics BatchNorm, so their true gradient is exactly zero and an exact zero tensor is
+    returned for them.  No double backward.  Single process only: with torch.distributed initialised on more than one rank this
+    raises (SyncBatchNorm on the feature side is not built)."""
+    if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
+        raise NotImplementedError("fpn_decoder_forward_train: batch statistics are per process; SyncBatchNorm / multi-GPU training of the "
+                                  "feature side is not built")
+    module._check_inputs(conv01, conv11, conv21, conv31)
+    c01, c11, c21, c31 = (t.float() for t in (conv01, conv11, conv21, conv31))
+    head = lambda k, x: FpnHeadTrain.apply(x, getattr(module, "out%d" % k)[1], getattr(module, "out%d" % k)[0].weight,
+                                           getattr(module, "out%d" % k)[0].bias, getattr(module, "out%d" % k)[1].weight,
+                                           getattr(module, "out%d" % k)[1].bias)
+    out0 = head(0, c31)
+    intra1 = FpnMergeTrain.apply(c31, c21, module.inner1.weight, module.inner1.bias)
+    out1 = head(1, intra1)
+    intra2 = FpnMergeTrain.apply(intra1, c11, module.inner2.weight, module.inner2.bias)
+    out2 = head(2, intra2)
+    out3 = FpnLevel3Train.apply(intra2, c01, module.out3[1], module.inner3.weight, module.inner3.bias, module.out3[0].weight,
+                                module.out3[0].bias, module.out3[1].weight, module.out3[1].bias)
+    return [out0, out1, out2, out3]
 
 
 _FP32_TRAIN_WARNED = False
