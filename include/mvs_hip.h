@@ -32,6 +32,12 @@ extern "C" {
 #define MVS_ABI_VERSION 11
 
 enum { MVS_OK = 0, MVS_ERR_ARG = 1, MVS_ERR_UNSUPPORTED = 2, MVS_ERR_LAUNCH = 3, MVS_ERR_WORKSPACE = 4 };
+/* The return type of every function whose int is MVS_OK or an MVS_ERR_* code; predicates (*_is_built, *_is_tuned, mvs_gather_*) and
+ * mvs_abi_version keep plain int.  This header is the only statement of the ABI: the Python binding reads its prototypes, these
+ * constants and, from this typedef, which results to check (mvsformerplusplus_amd/_header.py), so it stays plain C in a closed type
+ * vocabulary: int, float, double, size_t, long long, unsigned long long, pointers, const char* results.  The typedef names int: it
+ * changes no symbol and no calling convention, MVS_ABI_VERSION stays 11 and the definitions keep writing int.                     */
+typedef int mvs_status;
 enum { MVS_DTYPE_F32 = 0, MVS_DTYPE_BF16 = 1, MVS_DTYPE_F16 = 2 };
 /* feature-map layouts accepted by the two gather passes:
  *   MVS_LAYOUT_PLANAR       [B,V,C,H,W]          what the reference's FPN / FMT emit (models/module.py:257-270, models/FMT.py:195-197)
@@ -99,31 +105,31 @@ const char* mvs_last_error(void);
  * proj [B,V,2,4,4] (0 = extrinsic, 1 = intrinsic; datasets/general_eval.py:211-216).
  * For every source view v>=1: P = E.clone(); P[:3,:4] = K[:3,:3] @ E[:3,:4] (cost_volume.py:68-71),
  * M = P_v @ inverse(P_0); homography[b, v-1] = {M[:3,:3] row-major (9), M[:3,3] (3)}.          */
-int mvs_compose_homography(const float* proj, int B, int V, float* homography /*[B,V-1,12]*/, void* stream);
+mvs_status mvs_compose_homography(const float* proj, int B, int V, float* homography /*[B,V-1,12]*/, void* stream);
 /* Round 5, cascade prologue (DINOv2_mvsformer_model.py:127-150): the homographies of ALL stages (n_stages <= 8 proj tensors [B,V,2,4,4],
  * host array of device pointers) -> homography [n_stages,B,V-1,12], and - hyp != NULL - stage 1's hypotheses (mvs_init_range_fwd:
  * depth_values [B,N] -> hyp [B,D,H,W]) in ONE launch instead of n_stages + 1.                                                */
-int mvs_cascade_prologue_fwd(const float* const* proj_host_ptrs, int n_stages, int B, int V, float* homography,
-                             const float* depth_values, int N, int inverse, float* hyp, int D, int H, int W, void* stream);
+mvs_status mvs_cascade_prologue_fwd(const float* const* proj_host_ptrs, int n_stages, int B, int V, float* homography,
+                                    const float* depth_values, int N, int inverse, float* hyp, int D, int H, int W, void* stream);
 /* same from already-composed 4x4 projections (the argument form of homo_warping_3D_with_mask) */
-int mvs_homography_from_proj(const float* src_proj /*[B,4,4]*/, const float* ref_proj /*[B,4,4]*/, int B,
-                             float* homography /*[B,12]*/, void* stream);
+mvs_status mvs_homography_from_proj(const float* src_proj /*[B,4,4]*/, const float* ref_proj /*[B,4,4]*/, int B,
+                                    float* homography /*[B,12]*/, void* stream);
 
 /* ---- a2/a3: models/warping.py:69-109 homo_warping_3D_with_mask ---------------------------------
  * src_fea [B,C,H,W] (dtype), depth [B,D] (depth_is_volume=0) or [B,D,H,W] (1)
  * -> warped [B,C,D,H,W] fp32, proj_mask [B,D,H,W] uint8 (either may be NULL).                   */
-int mvs_homo_warp_fwd(const void* src_fea, int dtype, const float* homography /*[B,12]*/, const float* depth,
-                      int depth_is_volume, float* warped, uint8_t* proj_mask, int B, int C, int D, int H, int W,
-                      void* stream);
+mvs_status mvs_homo_warp_fwd(const void* src_fea, int dtype, const float* homography /*[B,12]*/, const float* depth,
+                             int depth_is_volume, float* warped, uint8_t* proj_mask, int B, int C, int D, int H, int W,
+                             void* stream);
 
 /* ---- a2-a5 fused: warp + group-wise correlation + softmax-entropy, cost_volume.py:65-92 --------
  * features [B,V,C,H,W] (dtype; view 0 = reference), hyp [B,D,H,W]
  * -> entropy [B,V-1,H,W].  No [C,D,H,W] or [G,D,H,W] intermediate is materialised.
  * Only source views in [view_begin, view_end) (1-based view indices) are processed.
  * gather_format: MVS_GATHER_F32 / MVS_GATHER_F16 (above).                                        */
-int mvs_warp_corr_entropy_fwd(const void* features, int dtype, int layout, const float* homography /*[B,V-1,12]*/,
-                              const float* hyp, float* entropy, int B, int V, int C, int G, int D, int H, int W,
-                              int view_begin, int view_end, int gather_format, void* stream);
+mvs_status mvs_warp_corr_entropy_fwd(const void* features, int dtype, int layout, const float* homography /*[B,V-1,12]*/,
+                                     const float* hyp, float* entropy, int B, int V, int C, int G, int D, int H, int W,
+                                     int view_begin, int view_end, int gather_format, void* stream);
 
 /* ---- pass 1 that KEEPS the per-view group correlations + the streaming pass 2 ------------------------------------------------
  * cost_volume.py:74-101 with the [B,G,D,H,W] per-view correlation the reference materialises kept as [B,V-1,D,H,W,8] in `corr_format`
@@ -134,11 +140,11 @@ int mvs_warp_corr_entropy_fwd(const void* features, int dtype, int layout, const
  * gather's shapes; MVS_CORR_F32 additionally needs D > 4); MVS_ERR_UNSUPPORTED elsewhere - the two-gather pair above covers every
  * shape.  Whether the stream pays (16 / 32 B per voxel and view written and read against a second gather) is the caller's policy.   */
 int mvs_gather_keeps_correlations(int layout, int C, int G, int D, int H, int W);
-int mvs_warp_corr_entropy_keep_fwd(const void* features, int dtype, int layout, const float* homography /*[B,V-1,12]*/,
-                                   const float* hyp, float* entropy, void* corr, int corr_format, int B, int V, int C, int G, int D,
-                                   int H, int W, void* stream);
-int mvs_corr_aggregate_fwd(const void* corr, int corr_format, const float* vis /*[B,V-1,H,W]*/, void* volume_cl, int volume_format,
-                           int B, int V, int D, int H, int W, void* stream);
+mvs_status mvs_warp_corr_entropy_keep_fwd(const void* features, int dtype, int layout, const float* homography /*[B,V-1,12]*/,
+                                          const float* hyp, float* entropy, void* corr, int corr_format, int B, int V, int C, int G, int D,
+                                          int H, int W, void* stream);
+mvs_status mvs_corr_aggregate_fwd(const void* corr, int corr_format, const float* vis /*[B,V-1,H,W]*/, void* volume_cl, int volume_format,
+                                  int B, int V, int D, int H, int W, void* stream);
 
 /* ---- section 8f #4, producer side (round 5): the feature side's LAST 3x3 convolution emitting the hand-off layout ----------------
  * Replaces Conv2d(Cin, Cout, 3, padding=1[, bias]) [+ folded BatchNorm2d] [+ Swish] followed by torch.stack / mvs_pack_features:
@@ -149,14 +155,14 @@ int mvs_corr_aggregate_fwd(const void* corr, int corr_format, const float* vis /
  * elements (so that view v of [B,V,C/8,H,W,8] can be written in place: out_batch_stride = V * Cout * H * W).  mvs_feature_conv_is_built
  * says which (Cin, Cout) pairs exist; others return MVS_ERR_UNSUPPORTED.                                                          */
 int mvs_feature_conv_is_built(int Cin, int Cout);
-int mvs_conv2d3x3_tiles_fwd(const void* x, int in_dtype, const void* w_packed, const float* bias, int act, void* tiled, int out_dtype,
-                            int N, int Cin, int Cout, int H, int W, long long in_batch_stride, long long out_batch_stride,
-                            void* stream);
+mvs_status mvs_conv2d3x3_tiles_fwd(const void* x, int in_dtype, const void* w_packed, const float* bias, int act, void* tiled, int out_dtype,
+                                   int N, int Cin, int Cout, int H, int W, long long in_batch_stride, long long out_batch_stride,
+                                   void* stream);
 
 /* ---- section 8f #4: feature hand-off -------------------------------------------------------------------
  * features [N,C,H,W] (dtype) -> tiled [N,C/8,H,W,8] (out_dtype); C % 8 == 0.  fp32 / bf16 / fp16 in, any of them out except
  * bf16 <-> fp16.  The cast to a 2-byte type rounds to nearest even, like the .to(bfloat16) the reference's autocast applies. */
-int mvs_pack_features(const void* features, int dtype, void* tiled, int out_dtype, int N, int C, int H, int W, void* stream);
+mvs_status mvs_pack_features(const void* features, int dtype, void* tiled, int out_dtype, int N, int C, int H, int W, void* stream);
 
 /* ---- a5: visibility CNN, cost_volume.py:36,93 + module.py:168-197 ------------------------------
  * entropy [N,H,W] -> vis [N,H,W] = sigmoid(conv1x1(CBR(16->8)(CBR(16->16)(CBR(1->16)(entropy))))).
@@ -164,23 +170,23 @@ int mvs_pack_features(const void* features, int dtype, void* tiled, int out_dtyp
  *   w1 [9][16] + b1[16] (BN folded), w2/w3 = MFMA-packed 3x3 weights (layout below), b2[16], b3[8]
  *   (padded to 16), w4[8], b4[1].  workspace >= mvs_vis_workspace_bytes(N,H,W).                  */
 size_t mvs_vis_workspace_bytes(int N, int H, int W, int precision);
-int mvs_vis_weight_fwd(const float* entropy, const float* w1, const float* b1, const void* w2, const float* b2,
-                       const void* w3, const float* b3, const float* w4, const float* b4, float* vis,
-                       void* workspace, size_t workspace_bytes, int N, int H, int W, int precision, void* stream);
+mvs_status mvs_vis_weight_fwd(const float* entropy, const float* w1, const float* b1, const void* w2, const float* b2,
+                              const void* w3, const float* b3, const float* w4, const float* b4, float* vis,
+                              void* workspace, size_t workspace_bytes, int N, int H, int W, int precision, void* stream);
 
 /* the first (1->16 3x3 + BN + ReLU -> [N,H,W,16] channel-last) and last (8->1 1x1 + sigmoid) layer of the chain above
  * on their own; the two middle layers are mvs_conv3d_bn_relu_fwd with kd = 1 */
-int mvs_vis_conv1_fwd(const float* entropy, const float* w1, const float* b1, float* out_cl16, int N, int H, int W, void* stream);
-int mvs_vis_out_fwd(const float* x_cl8, const float* w4, const float* b4, float* vis, int N, int H, int W, void* stream);
+mvs_status mvs_vis_conv1_fwd(const float* entropy, const float* w1, const float* b1, float* out_cl16, int N, int H, int W, void* stream);
+mvs_status mvs_vis_out_fwd(const float* x_cl8, const float* w4, const float* b4, float* vis, int N, int H, int W, void* stream);
 
 /* ---- a4 + a6: recompute warp + correlation, weight by visibility, aggregate over views ----------
  * cost_volume.py:79-101.  vis [B,V-1,H,W].  volume_cl [B,D,H,W,G] channel-last.
  *   normalise = 1 : volume = sum_v ip_v*vis_v / (sum_v vis_v + 1e-6)              (single GPU)
  *   normalise = 0 : volume = partial sum over [view_begin, view_end), vis_sum [B,H,W] = partial
  *                   sum of vis (view-sharded multi-GPU: all-reduce both, then mvs_volume_normalise) */
-int mvs_warp_corr_aggregate_fwd(const void* features, int dtype, int layout, const float* homography, const float* hyp,
-                                const float* vis, float* volume_cl, float* vis_sum, int normalise, int volume_format, int B,
-                                int V, int C, int G, int D, int H, int W, int view_begin, int view_end, void* stream);
+mvs_status mvs_warp_corr_aggregate_fwd(const void* features, int dtype, int layout, const float* homography, const float* hyp,
+                                       const float* vis, float* volume_cl, float* vis_sum, int normalise, int volume_format, int B,
+                                       int V, int C, int G, int D, int H, int W, int view_begin, int view_end, void* stream);
 /* ---- slab exchange of the view-sharded latency mode (no reference counterpart - the reference is
  * single-GPU; the sums follow cost_volume.py:97-101).  Message j = rows [row_begin[j], row_end[j]) of a PARTIAL fp32 volume
  * [B,D,H,W,G] followed by the same rows of the partial visibility sum [B,H,W], i.e. B*D*rows*W*G + B*rows*W floats (G: v10).
@@ -188,18 +194,18 @@ int mvs_warp_corr_aggregate_fwd(const void* features, int dtype, int layout, con
  * mvs_slab_reduce: slab_out = sum over ranks j = 0 .. n_ranks-1, in that order, of rank j's partial of MY rows [row_begin, row_end):
  * the own slice (j == my_rank) read in place from (volume_cl, vis_sum), the others from recv_host_ptrs[j] (NULL = rank j sent
  * nothing).  The pointer arrays are HOST arrays of device pointers (at most 16 ranks).                                           */
-int mvs_slab_pack(const float* volume_cl, const float* vis_sum, float* const* send_host_ptrs, const int* row_begin, const int* row_end,
-                  int n_ranks, int B, int D, int H, int W, int G, void* stream);
-int mvs_slab_reduce(const float* volume_cl, const float* vis_sum, float* const* recv_host_ptrs, int n_ranks, int my_rank, float* slab_out,
-                    int row_begin, int row_end, int B, int D, int H, int W, int G, void* stream);
+mvs_status mvs_slab_pack(const float* volume_cl, const float* vis_sum, float* const* send_host_ptrs, const int* row_begin, const int* row_end,
+                         int n_ranks, int B, int D, int H, int W, int G, void* stream);
+mvs_status mvs_slab_reduce(const float* volume_cl, const float* vis_sum, float* const* recv_host_ptrs, int n_ranks, int my_rank, float* slab_out,
+                           int row_begin, int row_end, int B, int D, int H, int W, int G, void* stream);
 /* volume_cl /= (vis_sum + 1e-6) in place; volume_format = MVS_VOLUME_SPLIT additionally converts it to the split format */
-int mvs_volume_normalise(float* volume_cl, const float* vis_sum, int B, int D, int H, int W, int G, int volume_format, void* stream);
+mvs_status mvs_volume_normalise(float* volume_cl, const float* vis_sum, int B, int D, int H, int W, int G, int volume_format, void* stream);
 /* fp32 volume [B,D,H,W,8] (vis_sum != NULL: divided by vis_sum + 1e-6 first) -> fp16 [B,D,H,W,8] in a separate buffer, clamped to the
  * fp16 range: the cost volume of the MVS_PREC_F16X2 U-Net where the aggregate pass could not write it directly (view-sharded
  * multi-GPU partial sums; shapes outside the LDS-staged gather)                                                                */
 /* 1 when the two gather passes take the LDS-staged kernels for this shape (the only ones that write MVS_VOLUME_SPLIT / _F16 directly) */
 int mvs_gather_is_lds_staged(int layout, int C, int G, int D, int H, int W);
-int mvs_volume_to_f16(const float* volume_cl, const float* vis_sum, void* out_f16, int B, int D, int H, int W, int G, void* stream);
+mvs_status mvs_volume_to_f16(const float* volume_cl, const float* vis_sum, void* out_f16, int B, int D, int H, int W, int G, void* stream);
 
 /* ---- section 8f #2 (first slice): backward of mvs_warp_corr_aggregate_fwd(normalise = 1) ----------------------------
  * The gradient the reference's autograd produces for cost_volume.py:74-101: the sampling grid is built under torch.no_grad()
@@ -207,26 +213,26 @@ int mvs_volume_to_f16(const float* volume_cl, const float* vis_sum, void* out_f1
  * maps only.  features planar [B,V,C,H,W] (fp32 / bf16 / fp16), volume_cl = the forward's output, vis_sum [B,H,W] = sum_v vis_v,
  * grad_volume_cl [B,D,H,W,G]; outputs: grad_features [B,V,C,H,W] fp32 (zeroed here, source views accumulated with atomics),
  * grad_vis [B,V-1,H,W].  Any C, G with C % G == 0.                                                                          */
-int mvs_warp_corr_aggregate_bwd(const void* features, int dtype, const float* homography, const float* hyp, const float* vis,
-                                const float* vis_sum, const float* volume_cl, const float* grad_volume_cl,
-                                float* grad_features, float* grad_vis, int B, int V, int C, int G, int D, int H, int W,
-                                void* stream);
+mvs_status mvs_warp_corr_aggregate_bwd(const void* features, int dtype, const float* homography, const float* hyp, const float* vis,
+                                       const float* vis_sum, const float* volume_cl, const float* grad_volume_cl,
+                                       float* grad_features, float* grad_vis, int B, int V, int C, int G, int D, int H, int W,
+                                       void* stream);
 
 /* ---- a7: Conv3d + folded BatchNorm3d + ReLU, module.py:89-126 ----------------------------------
  * x_cl [B,D,H,W,Cin] -> y_cl [B,OD,OH,OW,Cout]; kernel (kd,3,3), kd in {1,3}, padding (kd/2,1,1),
  * stride (sd,sh,sw) in {1,2}.  Implicit GEMM on MFMA; `precision` = MVS_PREC_* selects the contraction and the
  * packed-weight format (packing.pack_conv_weights / pack_conv_weights_bf16x3, DESIGN.md "MFMA weight packing");
  * bias [max(Cout,16)] fp32.                                                                                */
-int mvs_conv3d_bn_relu_fwd(const float* x_cl, const void* w_packed, const float* bias, float* y_cl, int B, int Cin,
-                           int Cout, int D, int H, int W, int kd, int sd, int sh, int sw, int relu, int precision,
-                           void* stream);
+mvs_status mvs_conv3d_bn_relu_fwd(const float* x_cl, const void* w_packed, const float* bias, float* y_cl, int B, int Cin,
+                                  int Cout, int D, int H, int W, int kd, int sd, int sh, int sw, int relu, int precision,
+                                  void* stream);
 
 /* ---- a10: CostRegNet's 3x3x3 `prob` head (Conv3d(8, 1, 3, padding 1, bias=False), module.py:391,407) on the MFMA path:
  * x_cl [B,D,H,W,8] -> logits [B,D,H,W] planar.  w_packed = the [1,8,3,3,3] weight zero-padded to 16 output rows and packed like
  * a Conv3d(8,16) (packing.pack_conv_weights_bf16x3); bias [16] (zeros for the reference's bias-free layer).  MVS_PREC_BF16X3 only;
  * the exact-fp32 form of the same head is mvs_prob_regress_fwd(prob_ksize = 3).                                               */
-int mvs_conv3d_logits_fwd(const float* x_cl, const void* w_packed, const float* bias, float* logits, int B, int D, int H,
-                          int W, int precision, void* stream);
+mvs_status mvs_conv3d_logits_fwd(const float* x_cl, const void* w_packed, const float* bias, float* logits, int B, int D, int H,
+                                 int W, int precision, void* stream);
 
 /* ---- section 8f #2: training-mode regulariser (batch-statistics BatchNorm, weight gradients) -------------------------------
  * Channel-last fp32 [N voxels][C], C in {8,16,32,64}; `groups` independent statistics sets of N voxels each (tensor [groups][N][C],
@@ -242,18 +248,18 @@ int mvs_conv3d_logits_fwd(const float* x_cl, const void* w_packed, const float* 
  *   mvs_conv3d_wgrad   dW[CB][CA][kd*9] of Conv3d(k (kd,3,3), kd = 1 | 3, 'same' padding, stride) from input a_cl [B,D,H,W,CA] and output gradient
  *                      g_cl [B,OD,OH,OW,CB] on the fp32 MFMA path; a transposed convolution's weight gradient is the same call
  *                      with a = its output gradient and g = its input (result in ConvTranspose3d's [Cin][Cout][27] layout)    */
-int mvs_deconv3d_linear_fwd(const float* x_cl, const void* w_packed, const float* bias, float* y_cl, int B, int Cin, int Cout,
-                            int D, int H, int W, int sd, int precision, void* stream);
-int mvs_bn_stats(const float* x_cl, double* sums, long long N, int C, int groups, void* stream);
-int mvs_bn_finalize(const double* sums, double count, float eps, float* mean, float* var, float* invstd, float* running_mean,
-                    float* running_var, float momentum, int C, int groups, void* stream);
-int mvs_bn_running_update(const float* mean, const float* var, double count, float momentum, float* running_mean,
-                          float* running_var, int C, int groups, void* stream);
-int mvs_bn_relu_apply(const float* z_cl, const float* mean, const float* invstd, const float* gamma, const float* beta,
-                      const float* skip_cl, float* y_cl, long long N, int C, int relu, int groups, void* stream);
-int mvs_bn_relu_bwd(const float* dy_cl, const float* z_cl, const float* mean, const float* invstd, const float* gamma,
-                    const float* beta, double* sums, double count, float* dz_cl, long long N, int C, int relu,
-                    int use_batch_stats, int phase, int groups, void* stream);
+mvs_status mvs_deconv3d_linear_fwd(const float* x_cl, const void* w_packed, const float* bias, float* y_cl, int B, int Cin, int Cout,
+                                   int D, int H, int W, int sd, int precision, void* stream);
+mvs_status mvs_bn_stats(const float* x_cl, double* sums, long long N, int C, int groups, void* stream);
+mvs_status mvs_bn_finalize(const double* sums, double count, float eps, float* mean, float* var, float* invstd, float* running_mean,
+                           float* running_var, float momentum, int C, int groups, void* stream);
+mvs_status mvs_bn_running_update(const float* mean, const float* var, double count, float momentum, float* running_mean,
+                                 float* running_var, int C, int groups, void* stream);
+mvs_status mvs_bn_relu_apply(const float* z_cl, const float* mean, const float* invstd, const float* gamma, const float* beta,
+                             const float* skip_cl, float* y_cl, long long N, int C, int relu, int groups, void* stream);
+mvs_status mvs_bn_relu_bwd(const float* dy_cl, const float* z_cl, const float* mean, const float* invstd, const float* gamma,
+                           const float* beta, double* sums, double count, float* dz_cl, long long N, int C, int relu,
+                           int use_batch_stats, int phase, int groups, void* stream);
 /* One conv / transposed-conv + batch-statistics BatchNorm + ReLU [+ skip] block per call (the launches of the granular entry points
  * chained in C): forward = pack, linear convolution -> z, statistics, finalize (+ running-statistics step), normalise -> y;
  * backward = running-statistics step (the reference's checkpoint recomputation), reduce -> dgamma / dbeta, dz, weight gradient dw
@@ -261,34 +267,34 @@ int mvs_bn_relu_bwd(const float* dy_cl, const float* z_cl, const float* mean, co
  * zero_bias: >= 64 zeros; wpack_ws: bf16 scratch of mvs_pack_*_weights_elems elements (max over the block's three packings);
  * sums_ws: double [groups][2C]; B, D, H, W = the block INPUT's batch and size.  SyncBatchNorm / eval-mode BatchNorm: use the
  * granular entry points (an all-reduce sits between statistics and finalize).                                                  */
-int mvs_train_block_fwd(const float* a_in_cl, const float* w, int transposed, int Cin, int Cout, int kd, int sd, int sh, int sw,
-                        int B, int D, int H, int W, const float* gamma, const float* beta, float eps, float* running_mean,
-                        float* running_var, float momentum, const float* skip_cl, const float* zero_bias, void* wpack_ws,
-                        double* sums_ws, float* z_cl, float* mean, float* var, float* invstd, float* y_cl, int groups,
-                        void* stream);
-int mvs_train_block_bwd(const float* dy_cl, const float* a_in_cl, const float* z_cl, const float* mean, const float* var,
-                        const float* invstd, const float* w, int transposed, int Cin, int Cout, int kd, int sd, int sh, int sw,
-                        int B, int D, int H, int W, const float* gamma, const float* beta, float* running_mean,
-                        float* running_var, float momentum, const float* zero_bias, void* wpack_ws, double* sums_ws,
-                        float* dz_cl, float* dw, float* dgamma, float* dbeta, float* da_cl, int groups, void* stream);
+mvs_status mvs_train_block_fwd(const float* a_in_cl, const float* w, int transposed, int Cin, int Cout, int kd, int sd, int sh, int sw,
+                               int B, int D, int H, int W, const float* gamma, const float* beta, float eps, float* running_mean,
+                               float* running_var, float momentum, const float* skip_cl, const float* zero_bias, void* wpack_ws,
+                               double* sums_ws, float* z_cl, float* mean, float* var, float* invstd, float* y_cl, int groups,
+                               void* stream);
+mvs_status mvs_train_block_bwd(const float* dy_cl, const float* a_in_cl, const float* z_cl, const float* mean, const float* var,
+                               const float* invstd, const float* w, int transposed, int Cin, int Cout, int kd, int sd, int sh, int sw,
+                               int B, int D, int H, int W, const float* gamma, const float* beta, float* running_mean,
+                               float* running_var, float momentum, const float* zero_bias, void* wpack_ws, double* sums_ws,
+                               float* dz_cl, float* dw, float* dgamma, float* dbeta, float* da_cl, int groups, void* stream);
 
 /* MFMA weight packing on the device (bit-identical to packing.pack_conv_weights_bf16x3 / pack_deconv_weights_bf16x3; used by the
  * training path, which re-packs every un-folded weight each iteration).  *_elems = number of bf16 elements of the packed tensor
  * (-1: unsupported shape).  w: Conv3d [cout][cin][ntap] (tflip = 1: read as [cin][cout] with reversed taps = the data-gradient form
  * of a stride-1 convolution) / ConvTranspose3d [cin][cout][27].                                                               */
 long long mvs_pack_conv_weights_elems(int cout, int cin, int ntap, int ch);
-int mvs_pack_conv_weights(const float* w, void* packed_bf16, int cout, int cin, int ntap, int ch, int tflip, void* stream);
+mvs_status mvs_pack_conv_weights(const float* w, void* packed_bf16, int cout, int cin, int ntap, int ch, int tflip, void* stream);
 long long mvs_pack_deconv_weights_elems(int cin, int cout, int sd);
-int mvs_pack_deconv_weights(const float* w, void* packed_bf16, int cin, int cout, int sd, void* stream);
-int mvs_conv3d_wgrad(const float* a_cl, const float* g_cl, float* dw, int B, int CA, int CB, int D, int H, int W, int kd,
-                     int sd, int sh, int sw, void* stream);
+mvs_status mvs_pack_deconv_weights(const float* w, void* packed_bf16, int cin, int cout, int sd, void* stream);
+mvs_status mvs_conv3d_wgrad(const float* a_cl, const float* g_cl, float* dw, int B, int CA, int CB, int D, int H, int W, int kd,
+                            int sd, int sh, int sw, void* stream);
 
 /* ---- a7: ConvTranspose3d(k3, padding 1, stride (sd,2,2), output_padding (sd-1,1,1)) + BN + ReLU,
  * then + skip (module.py:129-165, 402-405, 467-481, 498-501).
  * x_cl [B,D,H,W,Cin] -> y_cl [B,D*sd,2H,2W,Cout]; skip_cl has y's shape (NULL = no skip).          */
-int mvs_deconv3d_bn_relu_add_fwd(const float* x_cl, const void* w_packed, const float* bias, const float* skip_cl,
-                                 float* y_cl, int B, int Cin, int Cout, int D, int H, int W, int sd, int precision,
-                                 void* stream);
+mvs_status mvs_deconv3d_bn_relu_add_fwd(const float* x_cl, const void* w_packed, const float* bias, const float* skip_cl,
+                                        float* y_cl, int B, int Cin, int Cout, int D, int H, int W, int sd, int precision,
+                                        void* stream);
 
 /* ---- a7-a9, layer shapes OUTSIDE the tuned tables: shape-generic exact-fp32 Conv3d / ConvTranspose3d -------------------------------
  * Replaces nn.Conv3d / nn.ConvTranspose3d (+ folded BatchNorm3d, ReLU, skip add) of module.py:89-165 for any channel counts, kernel
@@ -300,9 +306,9 @@ int mvs_deconv3d_bn_relu_add_fwd(const float* x_cl, const void* w_packed, const 
  *   skip_cl [B,OD,OH,OW,Cout] or NULL, added after bias and ReLU (module.py:403-405).
  *   transposed = 0: O = (N + 2p - k) / s + 1 per axis;  transposed = 1: O = (N - 1) s - 2p + k + output_padding, 0 <= output_padding < s
  *   (the caller states OD, OH, OW; anything else is MVS_ERR_ARG).  Cout == 1 writes what is also a planar [B,OD,OH,OW] volume.          */
-int mvs_conv3d_generic_fwd(const float* x_cl, const float* w_tck, const float* bias, const float* skip_cl, float* y_cl, int B,
-                           int Cin, int Cout, int D, int H, int W, int OD, int OH, int OW, int kd, int kh, int kw, int sd, int sh,
-                           int sw, int pd, int ph, int pw, int transposed, int relu, void* stream);
+mvs_status mvs_conv3d_generic_fwd(const float* x_cl, const float* w_tck, const float* bias, const float* skip_cl, float* y_cl, int B,
+                                  int Cin, int Cout, int D, int H, int W, int OD, int OH, int OW, int kd, int kh, int kw, int sd, int sh,
+                                  int sw, int pd, int ph, int pw, int transposed, int relu, void* stream);
 /* 1 when mvs_conv3d_bn_relu_fwd / mvs_deconv3d_bn_relu_add_fwd have a tuned MFMA kernel for the layer shape (kernel (kd,3,3), padding
  * (kd/2,1,1) / the k3 p1 (sd,2,2) transposed form), else 0: the host mirror routes the layer to mvs_conv3d_generic_fwd then */
 int mvs_conv3d_is_tuned(int Cin, int Cout, int kd, int sd, int sh, int sw);
@@ -310,23 +316,23 @@ int mvs_deconv3d_is_tuned(int Cin, int Cout, int sd);
 
 /* the last U-Net layer with the 1x1x1 `prob` head in its epilogue (Cout = 8): x_cl [B,D,H,W,Cin] -> logits [B,D*sd,2H,2W]
  * = prob(skip + relu(bn(deconv(x)))); MVS_PREC_BF16X3 only.  mvs_regnet_logits_fwd chains it after the other eight layers. */
-int mvs_deconv3d_prob_fwd(const float* x_cl, const void* w_packed, const float* bias, const float* skip_cl, const float* prob_w,
-                          const float* prob_b, float* logits, int B, int Cin, int D, int H, int W, int sd, int precision,
-                          void* stream);
+mvs_status mvs_deconv3d_prob_fwd(const float* x_cl, const void* w_packed, const float* bias, const float* skip_cl, const float* prob_w,
+                                 const float* prob_b, float* logits, int B, int Cin, int D, int H, int W, int sd, int precision,
+                                 void* stream);
 
 /* ---- a8/a9: whole regulariser U-Net (CostRegNet / CostRegNet3D), module.py:367-408 / 453-504 ----
  * volume_cl [B,D,H,W,8] -> feat_cl [B,D,H,W,8] = conv0 + relu(bn(deconv11(...))) (input of `prob`).
  * params: 9 packed weight pointers + 9 bias pointers in layer order conv1..conv6, conv7, conv9, conv11.*/
 size_t mvs_regnet_workspace_bytes(int kind, int B, int D, int H, int W);
-int mvs_regnet_fwd(int kind, const float* volume_cl, const void* const* w_packed, const float* const* bias,
-                   float* feat_cl, void* workspace, size_t workspace_bytes, int B, int D, int H, int W, int precision,
-                   void* stream);
+mvs_status mvs_regnet_fwd(int kind, const float* volume_cl, const void* const* w_packed, const float* const* bias,
+                          float* feat_cl, void* workspace, size_t workspace_bytes, int B, int D, int H, int W, int precision,
+                          void* stream);
 /* the same U-Net with a 1x1x1 `prob` head (CostRegNet3D, module.py:486,502: prob_w [8], prob_b [1]) applied in the epilogue
  * of the last ConvTranspose3d: volume_cl -> logits [B,D,H,W] = prob_volume_pre; the 8-channel full-resolution feature
  * volume is never written (MVS_PREC_BF16X3 only).  Follow with mvs_softmax_regress_fwd.                              */
-int mvs_regnet_logits_fwd(int kind, const float* volume_cl, const void* const* w_packed, const float* const* bias,
-                          const float* prob_w, const float* prob_b, float* logits, void* workspace, size_t workspace_bytes,
-                          int B, int D, int H, int W, int precision, void* stream);
+mvs_status mvs_regnet_logits_fwd(int kind, const float* volume_cl, const void* const* w_packed, const float* const* bias,
+                                 const float* prob_w, const float* prob_b, float* logits, void* workspace, size_t workspace_bytes,
+                                 int B, int D, int H, int W, int precision, void* stream);
 
 /* ---- a8/a9 `prob` + a10 + a11: logits, softmax, depth regression, confidence --------------------
  * feat_cl [B,D,H,W,8]; prob_w: [8] (+ prob_b[1]) for the 1x1x1 head (CostRegNet3D, module.py:486)
@@ -334,51 +340,51 @@ int mvs_regnet_logits_fwd(int kind, const float* volume_cl, const void* const* w
  * hyp [B,D,H,W].  mode: MVS_HEAD_*.  conf_n: window of conf_regression for MVS_HEAD_REG (0 = max prob).
  * Outputs (any of prob_volume / prob_volume_pre may be NULL): depth [B,H,W], conf [B,H,W],
  * prob_volume [B,D,H,W], prob_volume_pre [B,D,H,W].                                                */
-int mvs_prob_regress_fwd(const float* feat_cl, const float* prob_w, const float* prob_b, int prob_ksize,
-                         const float* hyp, float tmp, int mode, int conf_n, float* depth, float* conf,
-                         float* prob_volume, float* prob_volume_pre, int B, int D, int H, int W, void* stream);
+mvs_status mvs_prob_regress_fwd(const float* feat_cl, const float* prob_w, const float* prob_b, int prob_ksize,
+                                const float* hyp, float tmp, int mode, int conf_n, float* depth, float* conf,
+                                float* prob_volume, float* prob_volume_pre, int B, int D, int H, int W, void* stream);
 /* same head on precomputed logits [B,D,H,W] (depth_regression / conf_regression callers) */
-int mvs_softmax_regress_fwd(const float* logits, const float* hyp, float tmp, int mode, int conf_n, float* depth,
-                            float* conf, float* prob_volume, int B, int D, int H, int W, void* stream);
+mvs_status mvs_softmax_regress_fwd(const float* logits, const float* hyp, float tmp, int mode, int conf_n, float* depth,
+                                   float* conf, float* prob_volume, int B, int D, int H, int W, void* stream);
 /* Round 5: a stage's head fused with the NEXT stage's inverse-depth schedule (mvs_softmax_regress_fwd + mvs_schedule_inverse_range_fwd with
  * shift = 0 in one launch; DINOv2_mvsformer_model.py:133-148 + cost_volume.py:105-131): besides depth / conf / prob_volume it writes
  * next_hyp [B,next_D,2H,2W] from this stage's depth and hypotheses (module.py:707-724, `ratio` = the next stage's depth_interals_ratio).
  * depth / conf / prob_volume are bit-identical to mvs_softmax_regress_fwd's; next_hyp equals the stand-alone schedule's up to FMA
  * contraction of the two translation units (<= 2e-6 of its range; bit-identical on the shipped build).                               */
-int mvs_softmax_regress_schedule_fwd(const float* logits, const float* hyp, float tmp, int mode, int conf_n, float* depth, float* conf,
-                                     float* prob_volume, float ratio, float* next_hyp, int next_D, int B, int D, int H, int W,
-                                     void* stream);
+mvs_status mvs_softmax_regress_schedule_fwd(const float* logits, const float* hyp, float tmp, int mode, int conf_n, float* depth, float* conf,
+                                            float* prob_volume, float ratio, float* next_hyp, int next_D, int B, int D, int H, int W,
+                                            void* stream);
 /* Round 5: the LAST cascade stage's head with a16 fused (DINOv2_mvsformer_model.py:167-177): besides depth / conf / prob_volume it writes
  * conf_avg [B,H,W] = (sum_i nearest-upsampled prev_conf[i] + conf) / (n_prev + 1); prev_conf[i] is [B, H >> shift[i], W >> shift[i]]
  * (host arrays of n_prev <= 7 device pointers / shifts, earliest stage first: the summation order of mvs_confidence_average).    */
-int mvs_softmax_regress_confavg_fwd(const float* logits, const float* hyp, float tmp, int mode, int conf_n, float* depth,
-                                    float* conf, float* prob_volume, const float* const* prev_conf_host_ptrs,
-                                    const int* prev_shifts_host, int n_prev, float* conf_avg, int B, int D, int H, int W,
-                                    void* stream);
+mvs_status mvs_softmax_regress_confavg_fwd(const float* logits, const float* hyp, float tmp, int mode, int conf_n, float* depth,
+                                           float* conf, float* prob_volume, const float* const* prev_conf_host_ptrs,
+                                           const int* prev_shifts_host, int n_prev, float* conf_avg, int B, int D, int H, int W,
+                                           void* stream);
 
 /* module.py:649-671 as free functions on a probability volume p [B,D,H,W]:
  * depth_regression: out = sum_d p*depth_values (depth_values [B,D,H,W]); conf_regression: window sum of n. */
-int mvs_depth_regression_fwd(const float* p, const float* depth_values, float* out, int B, int D, int H, int W, void* stream);
-int mvs_conf_regression_fwd(const float* p, int n, float* out, int B, int D, int H, int W, void* stream);
+mvs_status mvs_depth_regression_fwd(const float* p, const float* depth_values, float* out, int B, int D, int H, int W, void* stream);
+mvs_status mvs_conf_regression_fwd(const float* p, int n, float* out, int B, int D, int H, int W, void* stream);
 
 /* ---- a13-a15: hypothesis ranges, module.py:674-741 ----------------------------------------------*/
-int mvs_init_range_fwd(const float* depth_values /*[B,N]*/, int N, int inverse, float* hyp /*[B,D,H,W]*/, int B,
-                       int D, int H, int W, void* stream);
+mvs_status mvs_init_range_fwd(const float* depth_values /*[B,N]*/, int N, int inverse, float* hyp /*[B,D,H,W]*/, int B,
+                              int D, int H, int W, void* stream);
 /* the per-pixel form of the two (module.py:683-688, 698-703): depth_values [B,H,W,N], every pixel's own first / last depth */
-int mvs_init_range_pixel_fwd(const float* depth_values /*[B,H,W,N]*/, int N, int inverse, float* hyp /*[B,D,H,W]*/, int B,
-                             int D, int H, int W, void* stream);
+mvs_status mvs_init_range_pixel_fwd(const float* depth_values /*[B,H,W,N]*/, int N, int inverse, float* hyp /*[B,D,H,W]*/, int B,
+                                    int D, int H, int W, void* stream);
 /* prev_depth [B,H/2,W/2], prev_hyp [B,Dprev,H/2,W/2] -> hyp [B,D,H,W]; ratio = depth_interals_ratio; shift != 0: the reference's
  * `shift=True` branch (module.py:712-715), statement by statement                                                             */
-int mvs_schedule_inverse_range_fwd(const float* prev_depth, const float* prev_hyp, int Dprev, float ratio, int shift,
-                                   float* hyp, int B, int D, int H, int W, void* stream);
+mvs_status mvs_schedule_inverse_range_fwd(const float* prev_depth, const float* prev_hyp, int Dprev, float ratio, int shift,
+                                          float* hyp, int B, int D, int H, int W, void* stream);
 /* interval [B] = depth_interals_ratio * depth_interval, or (interval_per_pixel != 0) [B,H/2,W/2] (module.py:727-741) */
-int mvs_schedule_range_fwd(const float* prev_depth, const float* interval, int interval_per_pixel, float* hyp, int B, int D,
-                           int H, int W, void* stream);
+mvs_status mvs_schedule_range_fwd(const float* prev_depth, const float* interval, int interval_per_pixel, float* hyp, int B, int D,
+                                  int H, int W, void* stream);
 
 /* ---- a16: confidence fusion, DINOv2_mvsformer_model.py:167-177 -----------------------------------
  * out[b,y,x] = mean_s conf_s[b, y >> shift_s, x >> shift_s] (nearest upsample), n_stages <= 8.      */
-int mvs_confidence_average(const float* const* conf_host_ptrs, const int* shifts_host, int n_stages, float* out,
-                           int B, int H, int W, void* stream);
+mvs_status mvs_confidence_average(const float* const* conf_host_ptrs, const int* shifts_host, int n_stages, float* out,
+                                  int B, int H, int W, void* stream);
 
 /* ==== section 8f #1: stage-1 transformer regulariser of the shipped config =========================
  * PureTransformerCostReg module.py:602-646 (FlashAttnBlock :535-583, FFN :507-532, LayerNorm3D :586-599), softmax
@@ -394,35 +400,35 @@ int mvs_confidence_average(const float* const* conf_host_ptrs, const int* shifts
  * (stage 1) and written, otherwise they are read (later stages reuse stage 1's, DINOv2_mvsformer_model.py:152-160);
  * the last two are always written.  -> position3d [B,3,D,H,W] in 0..1.                                            */
 size_t mvs_position3d_workspace_bytes(void);
-int mvs_position3d_fwd(const float* K, const float* hyp, const float* depth_values, int n_depth_values, float* range,
-                       int compute_range, float* workspace, size_t workspace_bytes, float* position3d, int B, int D,
-                       int H, int W, void* stream);
+mvs_status mvs_position3d_fwd(const float* K, const float* hyp, const float* depth_values, int n_depth_values, float* range,
+                              int compute_range, float* workspace, size_t workspace_bytes, float* position3d, int B, int D,
+                              int H, int W, void* stream);
 
 /* get_position_3d(normalize=False), position_encoding.py:146-149: position3d [B,3,D,H,W] = K^-1 [x, y, 1] * depth, no ranges (v10) */
-int mvs_position3d_raw_fwd(const float* K, const float* hyp, float* position3d, int B, int D, int H, int W, void* stream);
+mvs_status mvs_position3d_raw_fwd(const float* K, const float* hyp, float* position3d, int B, int D, int H, int W, void* stream);
 /* PositionEncoding3D(position3d, C, rescale) as a tensor of its own, position_encoding.py:164-189: position3d [B,3,N] (N = D*H*W) ->
  * pe [B,3C,N], channel ax*C + 2f = sin(pos_ax * rescale * div_f), + 1 = cos; div_term [C/2] (device) = the frequencies
  * exp(2f * (-ln 1e4 / C)) as the caller computed them; C even.  The hot path never materialises the encoding (mvs_tr_embed_fwd
  * evaluates it per token); this is the standalone form for callers of the function (v10)                                        */
-int mvs_position_encoding3d_fwd(const float* position3d, const float* div_term, float* pe, int B, int C, float rescale, long long N,
-                                void* stream);
+mvs_status mvs_position_encoding3d_fwd(const float* position3d, const float* div_term, float* pe, int B, int C, float rescale, long long N,
+                                       void* stream);
 
 /* x + pe_proj(PositionEncoding3D(position3d, 8)) (module.py:631-635, position_encoding.py:166-189; skipped when
  * position3d == NULL), `down` = Conv3d(8, 64, kernel = stride = (rd,rh,rw)) + bias + LayerNorm3D(64, eps 1e-6).
  * volume_cl [B,D,H,W,8], pe_w = pe_proj.weight [8][24], pe_div_host = the 4 frequencies exp(2k * -ln(1e4)/8) (HOST
  * pointer), w_packed = pack_linear_bf16x3(down.0.weight as [64][patch_voxel*8 + c]) -> tokens [B,n,64].           */
-int mvs_tr_embed_fwd(const float* volume_cl, const float* position3d, const float* pe_w, const float* pe_div_host,
-                     const void* w_packed, const float* bias, const float* ln_w, const float* ln_b, float* tokens,
-                     int B, int D, int H, int W, int rd, int rh, int rw, int precision, void* stream);
+mvs_status mvs_tr_embed_fwd(const float* volume_cl, const float* position3d, const float* pe_w, const float* pe_div_host,
+                            const void* w_packed, const float* bias, const float* ln_w, const float* ln_b, float* tokens,
+                            int B, int D, int H, int W, int rd, int rh, int rw, int precision, void* stream);
 
 /* y = epilogue(x @ W^T): x [B,n,K], W [N,K] packed, y [B,n,N].
  *   MVS_TR_EPI_BIAS    y = x W^T (+ bias)                                                K = 64
  *   MVS_TR_EPI_GELU    y = gelu(x W^T + bias), exact erf form (FFN.linear1 + act)         K = 64
  *   MVS_TR_EPI_RES_LN  y = LayerNorm(residual + gamma[0] * (x W^T + bias)), N = 64        K = 64 | 256
  *                      (attn.proj / ffn.linear2 + layer scale + post-norm, module.py:575-576)                      */
-int mvs_tr_linear_fwd(const float* x, const void* w_packed, const float* bias, int epilogue, const float* residual,
-                      const float* gamma, const float* ln_w, const float* ln_b, float ln_eps, float* y, int B, int n,
-                      int K, int N, int precision, void* stream);
+mvs_status mvs_tr_linear_fwd(const float* x, const void* w_packed, const float* bias, int epilogue, const float* residual,
+                             const float* gamma, const float* ln_w, const float* ln_b, float ln_eps, float* y, int B, int n,
+                             int K, int N, int precision, void* stream);
 
 /* attn.qkv (no bias) written as the operands of the attention kernel, q pre-scaled by softmax_scale * log2 e.  softmax_scale =
  * head_dim^-0.5 * log(n) / log(train_avg_length) for "entropy_invariance" (attention.py:158-161).  heads = 4, head_dim = 16.
@@ -436,26 +442,26 @@ int mvs_tr_linear_fwd(const float* x, const void* w_packed, const float* bias, i
  *                                (csrc/attention_f16_kernels.hip); npad = n rounded up to 256
  * Each buffer holds mvs_tr_attention_operand_bytes(B, n, heads) bytes (enough for either format).                              */
 size_t mvs_tr_attention_operand_bytes(int B, int n, int heads);
-int mvs_tr_qkv_fwd(const float* x, const void* w_packed, void* q, void* k, void* vt, float softmax_scale, int B, int n,
-                   int heads, int precision, int operand_format, void* stream);
+mvs_status mvs_tr_qkv_fwd(const float* x, const void* w_packed, void* q, void* k, void* vt, float softmax_scale, int B, int n,
+                          int heads, int precision, int operand_format, void* stream);
 /* softmax(q k^T) v over all n tokens -> out [B,n,heads*16] (scaled_dot_product_attention, attention.py:96);
  * precision = the operand format of mvs_tr_qkv_fwd: MVS_PREC_BF16X3 (four-term scores, three-term p.v), MVS_PREC_BF16P (the same with
  * one-term probabilities) or MVS_PREC_ATTN16 (fp16 q / k, bf16 p / v, one MFMA term, fp32 softmax statistics and accumulation)              */
-int mvs_tr_attention_fwd(const void* q, const void* k, const void* vt, float* out, int B, int n, int heads,
-                         int precision, void* stream);
+mvs_status mvs_tr_attention_fwd(const void* q, const void* k, const void* vt, float* out, int B, int n, int heads,
+                                int precision, void* stream);
 /* Backward of the attention core (training path; the reference differentiates scaled_dot_product_attention / flash-attn,
  * dino/layers/attention.py:141-170): qkv [B,n,3,heads,16] fp32 = the projection's plain output (q | k | v), o [B,n,heads*16] the
  * forward result, d_o its gradient -> d_qkv [B,n,3,heads,16] (dq | dk | dv).  fp32 throughout, two launches, no atomics.
  * lse_ws / dsum_ws: B*heads*n floats each (log-sum-exp and sum_c d_o*o per query row, produced by the first launch).            */
-int mvs_tr_attention_bwd(const float* qkv, const float* o, const float* d_o, float* d_qkv, float* lse_ws, float* dsum_ws,
-                         int B, int n, int heads, float softmax_scale, void* stream);
+mvs_status mvs_tr_attention_bwd(const float* qkv, const float* o, const float* d_o, float* d_qkv, float* lse_ws, float* dsum_ws,
+                                int B, int n, int heads, float softmax_scale, void* stream);
 
 /* `up` = ConvTranspose3d(64, 8, kernel = stride = (rd,rh,rw)) + bias + LayerNorm3D(8, eps 1e-6), then `prob` =
  * Conv3d(8, 1, 1) + bias (module.py:621-626, 643-644): tokens [B,n,64] -> logits [B,D,H,W].
  * w_packed = pack_linear_bf16x3(up.0.weight as [patch_voxel*8 + co][ci]).                                          */
-int mvs_tr_up_prob_fwd(const float* tokens, const void* w_packed, const float* up_bias, const float* ln_w,
-                       const float* ln_b, const float* prob_w, const float* prob_b, float* logits, int B, int D, int H,
-                       int W, int rd, int rh, int rw, int precision, void* stream);
+mvs_status mvs_tr_up_prob_fwd(const float* tokens, const void* w_packed, const float* up_bias, const float* ln_w,
+                              const float* ln_b, const float* prob_w, const float* prob_b, float* logits, int B, int D, int H,
+                              int W, int rd, int rh, int rw, int precision, void* stream);
 
 /* ==== section 8f #3: depth-map filtering after inference ============================================
  * misc/fusion.py (reprojection-consistency filters) as driven by test.py:388-409 ("pcd") and test.py:455-483 ("dpcd").
@@ -463,7 +469,7 @@ int mvs_tr_up_prob_fwd(const float* tokens, const void* w_packed, const float* u
  * camera into mvs_fusion_campack_floats() floats {K, K^-1, E, E^-1} (the reference inverts them per call, fusion.py:24,32).
  * Depth / confidence maps are planar fp32 [n,h,w] / [n,v,h,w]; pixel centres sit at +0.5 (fusion.py:9-10).              */
 size_t mvs_fusion_campack_floats(void);
-int mvs_fusion_prepare_cams(const float* cams /*[N,2,4,4]*/, int N, float* packed /*[N,campack]*/, void* stream);
+mvs_status mvs_fusion_prepare_cams(const float* cams /*[N,2,4,4]*/, int N, float* packed /*[N,campack]*/, void* stream);
 /* dynamic = 0: get_reproj (fusion.py:80-97) + vis_filter (:100-109) + ave_fusion (:112-114); p0 = img_dist_thresh,
  *              p1 = depth_thresh, vthresh = view threshold; srcs_conf (nullable) zeroes source depths with conf <=
  *              conf_thresh (test.py:389-392); vis_masks [n,v,h,w].
@@ -474,14 +480,14 @@ int mvs_fusion_prepare_cams(const float* cams /*[N,2,4,4]*/, int N, float* packe
  * depth [n,h,w] = averaged depth, geo_mask / mask [n,h,w] (mask = geo & (ref_conf > conf_thresh), ref_conf nullable),
  * points [n,3,h,w] = world coordinates of the averaged depth (test.py:406-409); any of vis_masks / geo_mask / mask /
  * points may be NULL.  v <= 16.                                                                                          */
-int mvs_fusion_filter_fwd(int dynamic, const float* ref_depth, const float* ref_conf, const float* srcs_depth,
-                          const float* srcs_conf, const float* ref_cam_packed, const float* srcs_cam_packed,
-                          const float* xyd_in, const float* in_range_in, float conf_thresh, float p0, float p1, float vthresh,
-                          float* xyd_out, float* in_range_out, uint8_t* vis_masks, float* depth, uint8_t* geo_mask,
-                          uint8_t* mask, float* points, int n, int v, int h, int w, void* stream);
+mvs_status mvs_fusion_filter_fwd(int dynamic, const float* ref_depth, const float* ref_conf, const float* srcs_depth,
+                                 const float* srcs_conf, const float* ref_cam_packed, const float* srcs_cam_packed,
+                                 const float* xyd_in, const float* in_range_in, float conf_thresh, float p0, float p1, float vthresh,
+                                 float* xyd_out, float* in_range_out, uint8_t* vis_masks, float* depth, uint8_t* geo_mask,
+                                 uint8_t* mask, float* points, int n, int v, int h, int w, void* stream);
 /* ave_fusion (fusion.py:112-114) on its own: masks [n,v,h,w] fp32 */
-int mvs_fusion_ave_fwd(const float* ref_depth, const float* reproj_xyd, const float* masks, float* out, int n, int v, int h,
-                       int w, void* stream);
+mvs_status mvs_fusion_ave_fwd(const float* ref_depth, const float* reproj_xyd, const float* masks, float* out, int n, int v, int h,
+                              int w, void* stream);
 
 /* ==== point cloud: the filtered views of a scene as one binary PLY body =====================
  * The per-view body after the filter in test.py filter_depth (:414-442) / dynamic_filter_depth (:485-517): keep the pixels of
@@ -494,9 +500,9 @@ int mvs_fusion_ave_fwd(const float* ref_depth, const float* reproj_xyd, const fl
  * The caller keeps *counter + h*w <= capacity (records past the capacity are dropped, the counter still advances).
  * workspace: mvs_pointcloud_workspace_bytes(h, w) bytes, stream-ordered scratch.                                          */
 size_t mvs_pointcloud_workspace_bytes(int h, int w);
-int mvs_pointcloud_append(const uint8_t* mask, const float* points, const uint8_t* rgb, int h, int w, void* workspace,
-                          size_t workspace_bytes, unsigned* counter, unsigned* view_counts, int view_slot, uint8_t* records,
-                          long long capacity, void* stream);
+mvs_status mvs_pointcloud_append(const uint8_t* mask, const float* points, const uint8_t* rgb, int h, int w, void* workspace,
+                                 size_t workspace_bytes, unsigned* counter, unsigned* view_counts, int view_slot, uint8_t* records,
+                                 long long capacity, void* stream);
 
 /* ==== gipuma route: fusibile's cross-view consistency fusion as misc/gipuma.py drives it ===========
  * The probability filter (misc/gipuma.py:160-181), the camera conversion (:72-92: P = [K 0; 0 1] E, first three rows) and the
@@ -506,19 +512,19 @@ int mvs_pointcloud_append(const uint8_t* mask, const float* points, const uint8_
  * pair_consts [N, N, pair_floats] (fp32, host memory; the caller uploads them).  Fails on a singular P[:, :3].              */
 size_t mvs_gipuma_view_floats(void);
 size_t mvs_gipuma_pair_floats(void);
-int mvs_gipuma_prepare_cams(const float* cams, int N, float* view_consts, float* pair_consts);
+mvs_status mvs_gipuma_prepare_cams(const float* cams, int N, float* view_consts, float* pair_consts);
 /* one view's slot: depth_out = keep ? depth : 0 (keep u8 [h,w] nullable = keep all), color_out = packed rgb [h,w,3] u8     */
-int mvs_gipuma_prepare_view(const float* depth, const uint8_t* keep, const uint8_t* rgb, int h, int w, float* depth_out,
-                            uint32_t* color_out, void* stream);
+mvs_status mvs_gipuma_prepare_view(const float* depth, const uint8_t* keep, const uint8_t* rgb, int h, int w, float* depth_out,
+                                   uint32_t* color_out, void* stream);
 /* one launch per reference view r, in processing order on ONE stream (the marks of launch r are read by the later launches):
  * mask [h,w] u8, points [3,h,w] fp32, rgb [h,w,3] u8 of view r, as mvs_pointcloud_append reads them (points / rgb are written
  * for kept pixels only); used[c][v][u] = 1 for every pixel an emitted vertex used (c != r).  depth_min / depth_max are applied
  * exactly as in fp64 to the fp32 map values; a vertex needs n >= num_consistent consistent views.  skipped (nullable,
  * diagnostic) receives the used[r] the launch read.                                                                        */
-int mvs_gipuma_fuse_view(const float* depths, const uint32_t* colors, uint8_t* used, const float* view_consts,
-                         const float* pair_consts, int N, int h, int w, int r, double depth_min, double depth_max,
-                         float disp_thresh, double num_consistent, uint8_t* mask, float* points, uint8_t* rgb,
-                         uint8_t* skipped, void* stream);
+mvs_status mvs_gipuma_fuse_view(const float* depths, const uint32_t* colors, uint8_t* used, const float* view_consts,
+                                const float* pair_consts, int N, int h, int w, int r, double depth_min, double depth_max,
+                                float disp_thresh, double num_consistent, uint8_t* mask, float* points, uint8_t* rgb,
+                                uint8_t* skipped, void* stream);
 
 /* ==== colmap2mvsnet: view-selection scores and depth values of a COLMAP model =====================
  * fp64 throughout, device-resident.  mvs_colmap_depths: z[k] = erow[obs_img[k]] . [xyz[obs_pt[k]], 1] for n observations
@@ -528,10 +534,10 @@ int mvs_gipuma_fuse_view(const float* depths, const uint32_t* colors, uint8_t* u
  * 2 sigma2^2.  max_pairs >= the number of co-visible pairs i < j sizes `pairs` (u32); flags u8 [N, N] scratch (zeroed here);
  * workspace of mvs_colmap_workspace_bytes(N) (0 = N out of range).  Deterministic: no atomics, fixed reduction order.     */
 size_t mvs_colmap_workspace_bytes(int N);
-int mvs_colmap_depths(const int* obs_img, const int* obs_pt, long long n, const double* xyz, const double* erow, double* z, void* stream);
-int mvs_colmap_scores(const int* img_ptr, const int* img_pts, const int* img_mult, int N, const int* pt_ptr, const int* pt_imgs, int P,
-                      const double* xyz, const double* centres, double theta0, double den1, double den2, long long max_pairs,
-                      uint8_t* flags, unsigned* pairs, void* workspace, size_t workspace_bytes, double* score, void* stream);
+mvs_status mvs_colmap_depths(const int* obs_img, const int* obs_pt, long long n, const double* xyz, const double* erow, double* z, void* stream);
+mvs_status mvs_colmap_scores(const int* img_ptr, const int* img_pts, const int* img_mult, int N, const int* pt_ptr, const int* pt_imgs, int P,
+                             const double* xyz, const double* centres, double theta0, double den1, double den2, long long max_pairs,
+                             uint8_t* flags, unsigned* pairs, void* workspace, size_t workspace_bytes, double* score, void* stream);
 
 /* ==== FPN feature encoder and decoder at full image resolution ========================================
  * models/module.py:47-86 (Conv2d: conv without bias + BatchNorm2d + leaky_relu 0.1), models/module.py:200-270 (FPNEncoder,
@@ -547,12 +553,12 @@ int mvs_colmap_scores(const int* img_ptr, const int* img_pts, const int* img_mul
  *   (Clat, Cout) = the fused last level.  H and W even.                                                                              */
 int mvs_fpn_conv_is_built(int Cin, int Cout, int k, int stride);
 int mvs_fpn_merge_is_built(int Clat, int Cout);
-int mvs_fpn_conv_fwd(const float* x, const void* w_packed, const float* bias, int act, float* y, int N, int Cin, int Cout, int k, int stride,
-                     int H, int W, void* stream);
-int mvs_fpn_merge_fwd(const float* prev, const float* lateral, const float* w_inner, const float* b_inner, float* intra, int N, int Clat,
-                      int H, int W, void* stream);
-int mvs_fpn_merge_conv_fwd(const float* prev, const float* lateral, const float* w_inner, const float* b_inner, const void* w_packed,
-                           const float* bias, int act, float* y, int N, int Clat, int Cout, int H, int W, void* stream);
+mvs_status mvs_fpn_conv_fwd(const float* x, const void* w_packed, const float* bias, int act, float* y, int N, int Cin, int Cout, int k, int stride,
+                            int H, int W, void* stream);
+mvs_status mvs_fpn_merge_fwd(const float* prev, const float* lateral, const float* w_inner, const float* b_inner, float* intra, int N, int Clat,
+                             int H, int W, void* stream);
+mvs_status mvs_fpn_merge_conv_fwd(const float* prev, const float* lateral, const float* w_inner, const float* b_inner, const void* w_packed,
+                                  const float* bias, int act, float* y, int N, int Clat, int Cout, int H, int W, void* stream);
 
 /* ---- FPNDecoder in train mode: out_k = Swish(BatchNorm2d(conv(intra_k) + b)) with batch statistics over
  * all N H W samples of a channel, and its backward.  The forward convolutions are mvs_fpn_conv_fwd / mvs_fpn_merge_conv_fwd on
@@ -574,20 +580,20 @@ int mvs_fpn_merge_conv_fwd(const float* prev, const float* lateral, const float*
  * mvs_fpn_up2_adjoint: d_coarse [N,64,H/2,W/2] = U^T d_fine [N,64,H,W], U = mvs_fpn_merge_fwd's upsample; a gather with the forward's own
  *   coordinate function (the exact adjoint).  H and W even.                                                                          */
 size_t mvs_fpn_bn_workspace_bytes(int N, int C, int H, int W);
-int mvs_fpn_bn_swish_fwd(const float* z, const float* conv_bias, const float* gamma, const float* beta, float eps, float momentum,
-                         float* running_mean, float* running_var, float* stats, float* y, void* workspace, size_t workspace_bytes, int N, int C,
-                         int H, int W, void* stream);
-int mvs_fpn_bn_swish_bwd(const float* dy, const float* z, const float* stats, const float* gamma, const float* beta, float* dz, float* d_gamma,
-                         float* d_beta, void* workspace, size_t workspace_bytes, int N, int C, int H, int W, void* stream);
+mvs_status mvs_fpn_bn_swish_fwd(const float* z, const float* conv_bias, const float* gamma, const float* beta, float eps, float momentum,
+                                float* running_mean, float* running_var, float* stats, float* y, void* workspace, size_t workspace_bytes, int N, int C,
+                                int H, int W, void* stream);
+mvs_status mvs_fpn_bn_swish_bwd(const float* dy, const float* z, const float* stats, const float* gamma, const float* beta, float* dz, float* d_gamma,
+                                float* d_beta, void* workspace, size_t workspace_bytes, int N, int C, int H, int W, void* stream);
 int mvs_fpn_train_conv_is_built(int Cin, int Cout, int k);
-int mvs_fpn_train_conv_fwd(const float* x, const void* w_packed, float* y, int N, int Cin, int Cout, int k, int H, int W, void* stream);
+mvs_status mvs_fpn_train_conv_fwd(const float* x, const void* w_packed, float* y, int N, int Cin, int Cout, int k, int H, int W, void* stream);
 size_t mvs_fpn_wgrad_workspace_bytes(int N, int Cin, int Cout, int k, int ones, int H, int W);
-int mvs_fpn_wgrad(const float* dy, const float* x, float* dw, void* workspace, size_t workspace_bytes, int N, int Cin, int Cout, int k, int ones,
-                  int H, int W, void* stream);
+mvs_status mvs_fpn_wgrad(const float* dy, const float* x, float* dw, void* workspace, size_t workspace_bytes, int N, int Cin, int Cout, int k, int ones,
+                         int H, int W, void* stream);
 size_t mvs_fpn_merge_wgrad_workspace_bytes(int N, int H, int W);
-int mvs_fpn_merge_wgrad(const float* dy, const float* prev, const float* lateral, const float* w_inner, const float* b_inner, float* dw,
-                        void* workspace, size_t workspace_bytes, int N, int H, int W, void* stream);
-int mvs_fpn_up2_adjoint(const float* d_fine, float* d_coarse, int N, int H, int W, void* stream);
+mvs_status mvs_fpn_merge_wgrad(const float* dy, const float* prev, const float* lateral, const float* w_inner, const float* b_inner, float* dw,
+                               void* workspace, size_t workspace_bytes, int N, int H, int W, void* stream);
+mvs_status mvs_fpn_up2_adjoint(const float* d_fine, float* d_coarse, int N, int H, int W, void* stream);
 
 /* ==== FMT_with_pathway: stage-1 linear attention + pathway ============================================
  * models/FMT.py:35-206 with the shipped FMT_config (Linear attention, d_model 64, 4 heads, ffn, pre-norm, LayerScale).  Token
@@ -609,15 +615,15 @@ size_t mvs_fmt_weights_bytes(void);
 size_t mvs_fmt_vectors_bytes(void);
 size_t mvs_fmt_kv_operand_bytes(void);
 size_t mvs_fmt_kv_workspace_bytes(int N, int n);
-int mvs_fmt_kv_fwd(const float* x, const float* pe, const void* w_packed, const float* vectors, void* workspace, size_t workspace_bytes,
-                   void* kv_operand, int N, int n, void* stream);
-int mvs_fmt_block_fwd(const float* x, const float* pe, const void* kv_operand, const void* w_packed, const float* vectors, float* y, int N,
-                      int n, int kv_div, void* stream);
-int mvs_fmt_path_fwd(const float* prev, const float* lateral, const float* w_reduce, const void* w_packed, float* y, int N, int C, int h, int w,
-                     int H, int W, void* stream);
-int mvs_fmt_merge_fwd(const float* prev, const float* lateral, const float* w_reduce, float* merged, int N, int C, int h, int w, int H, int W,
-                      void* stream);
-int mvs_fmt_smooth_fwd(const float* x, const void* w_packed, float* y, int N, int C, int H, int W, void* stream);
+mvs_status mvs_fmt_kv_fwd(const float* x, const float* pe, const void* w_packed, const float* vectors, void* workspace, size_t workspace_bytes,
+                          void* kv_operand, int N, int n, void* stream);
+mvs_status mvs_fmt_block_fwd(const float* x, const float* pe, const void* kv_operand, const void* w_packed, const float* vectors, float* y, int N,
+                             int n, int kv_div, void* stream);
+mvs_status mvs_fmt_path_fwd(const float* prev, const float* lateral, const float* w_reduce, const void* w_packed, float* y, int N, int C, int h, int w,
+                            int H, int W, void* stream);
+mvs_status mvs_fmt_merge_fwd(const float* prev, const float* lateral, const float* w_reduce, float* merged, int N, int C, int h, int w, int H, int W,
+                             void* stream);
+mvs_status mvs_fmt_smooth_fwd(const float* x, const void* w_packed, float* y, int N, int C, int H, int W, void* stream);
 /* Backward of one pathway level Y = S * M, M = U(W_r prev) + lateral.  d lateral = dM is mvs_fmt_smooth_fwd of
  * dY with S's taps flipped and its channel axes exchanged.  Weight gradients are per-workgroup fp32 partials in `workspace` (the
  * *_workspace_bytes queries; 0 = out of range or not built) added in a fixed order: no atomics, bit-identical run to run.
@@ -626,11 +632,11 @@ int mvs_fmt_smooth_fwd(const float* x, const void* w_packed, float* y, int N, in
  * mvs_fmt_smooth_wgrad: d_w_smooth [C,C,3,3] = sum_pixels dY (x) M shifted by the tap, exact fp32 products; M is recomputed from
  *   prev, lateral and w_reduce in the kernel's staging and never written.                                                          */
 size_t mvs_fmt_path_bwd_workspace_bytes(int N, int C, int h, int w);
-int mvs_fmt_path_bwd(const float* d_merged, const float* prev, const float* w_reduce, float* d_prev, float* d_w_reduce, void* workspace,
-                     size_t workspace_bytes, int N, int C, int h, int w, int H, int W, void* stream);
+mvs_status mvs_fmt_path_bwd(const float* d_merged, const float* prev, const float* w_reduce, float* d_prev, float* d_w_reduce, void* workspace,
+                            size_t workspace_bytes, int N, int C, int h, int w, int H, int W, void* stream);
 size_t mvs_fmt_smooth_wgrad_workspace_bytes(int N, int C, int H, int W);
-int mvs_fmt_smooth_wgrad(const float* dy, const float* prev, const float* lateral, const float* w_reduce, float* d_w_smooth, void* workspace,
-                         size_t workspace_bytes, int N, int C, int h, int w, int H, int W, void* stream);
+mvs_status mvs_fmt_smooth_wgrad(const float* dy, const float* prev, const float* lateral, const float* w_reduce, float* d_w_smooth, void* workspace,
+                                size_t workspace_bytes, int N, int C, int h, int w, int H, int W, void* stream);
 
 /* ==== CrossVITDecoder: the ViT feature decoder at d_model 768 =========================================
  * models/module.py:273-364 with the shipped decoder_cfg (Linear attention, 12 heads of 64, ffn, pre-norm, LayerScale).  The residual
@@ -652,16 +658,16 @@ int mvs_fmt_smooth_wgrad(const float* dy, const float* prev, const float* latera
 size_t mvs_vitdec_packed_bytes(long long rows, int channels);
 size_t mvs_vitdec_summary_bytes(int NV);
 size_t mvs_vitdec_kv_workspace_bytes(int NV, int n);
-int mvs_vitdec_rows_fwd(const void* in, int in_dtype, long long in_batch_stride, long long in_view_stride, long long in_row_stride, int in_v0,
-                        int in_views, const float* prev, const float* prev_value, const float* mix_w, const float* mix_b, float* x,
-                        void* x_packed, int out_V, int out_v0, const float* ln_w, const float* ln_b, void* xn_packed, int NV, int n,
-                        int channels, void* stream);
-int mvs_vitdec_linear_fwd(const void* a_packed, const void* w_packed, const float* bias, const float* gamma, const float* residual, void* y,
-                          int M, int K, int N, int epilogue, int elu_cols, void* stream);
-int mvs_vitdec_kv_fwd(const float* kv, void* workspace, size_t workspace_bytes, float* summary, int NV, int n, int channels, void* stream);
-int mvs_vitdec_apply_fwd(const float* q, const float* summary, void* a_packed, int NV, int n, int kv_div, int channels, void* stream);
-int mvs_vitdec_conv_fwd(const void* x_packed, const void* w_packed, const float* bias, void* y, int layer, int planar, int NV, int H, int W,
-                        void* stream);
+mvs_status mvs_vitdec_rows_fwd(const void* in, int in_dtype, long long in_batch_stride, long long in_view_stride, long long in_row_stride, int in_v0,
+                               int in_views, const float* prev, const float* prev_value, const float* mix_w, const float* mix_b, float* x,
+                               void* x_packed, int out_V, int out_v0, const float* ln_w, const float* ln_b, void* xn_packed, int NV, int n,
+                               int channels, void* stream);
+mvs_status mvs_vitdec_linear_fwd(const void* a_packed, const void* w_packed, const float* bias, const float* gamma, const float* residual, void* y,
+                                 int M, int K, int N, int epilogue, int elu_cols, void* stream);
+mvs_status mvs_vitdec_kv_fwd(const float* kv, void* workspace, size_t workspace_bytes, float* summary, int NV, int n, int channels, void* stream);
+mvs_status mvs_vitdec_apply_fwd(const float* q, const float* summary, void* a_packed, int NV, int n, int kv_div, int channels, void* stream);
+mvs_status mvs_vitdec_conv_fwd(const void* x_packed, const void* w_packed, const float* bias, void* y, int layer, int planar, int NV, int H, int W,
+                               void* stream);
 
 /* ==== DINOv2 ViT-B/14 backbone: forward_interval_features ==============================================
  * models/dino/dinov2.py vit_base(patch_size=14) with the shipped dino_cfg: 14 x 14 patch embedding + interpolated position embedding,
@@ -680,21 +686,21 @@ int mvs_vitdec_conv_fwd(const void* x_packed, const void* w_packed, const float*
  * mvs_vit_attention_fwd: softmax(q k^T) v per (view, head) over keys 0 .. ntok - 1 (online softmax in fp32, exp2; no atomics, no split
  *   over the keys: bit-identical run to run) -> packed-split [NV * npad, 768], the row operand of attn.proj.                        */
 size_t mvs_vit_qkv_bytes(int NV, int npad);
-int mvs_vit_rows_fwd(const void* in, int in_dtype, long long in_batch_stride, long long in_view_stride, long long in_row_stride, int in_v0,
-                     int in_views, const float* prev, const float* prev_value, const float* mix_w, const float* mix_b, float* x,
-                     void* x_packed, int out_V, int out_v0, const float* ln_w, const float* ln_b, float ln_eps, void* xn_packed, int NV, int n,
-                     int channels, void* stream);
-int mvs_vit_patches_fwd(const void* img, int dtype, long long batch_stride, long long channel_stride, long long row_stride,
-                        long long col_stride, void* a_packed, int NV, int gh, int gw, int patch, int in_chans, void* stream);
-int mvs_vit_embed_fwd(const void* a_packed, const void* w_packed, const float* bias, const float* pos, const float* cls_pos, float* x, int NV,
-                      int n, int npad, int channels, void* stream);
-int mvs_vit_qkv_fwd(const void* xn_packed, const void* w_packed, const float* bias, void* qkv, int NV, int npad, float q_scale, int channels,
-                    void* stream);
-int mvs_vit_attention_fwd(const void* qkv, void* a_packed, int NV, int ntok, int npad, int heads, int head_dim, void* stream);
+mvs_status mvs_vit_rows_fwd(const void* in, int in_dtype, long long in_batch_stride, long long in_view_stride, long long in_row_stride, int in_v0,
+                            int in_views, const float* prev, const float* prev_value, const float* mix_w, const float* mix_b, float* x,
+                            void* x_packed, int out_V, int out_v0, const float* ln_w, const float* ln_b, float ln_eps, void* xn_packed, int NV, int n,
+                            int channels, void* stream);
+mvs_status mvs_vit_patches_fwd(const void* img, int dtype, long long batch_stride, long long channel_stride, long long row_stride,
+                               long long col_stride, void* a_packed, int NV, int gh, int gw, int patch, int in_chans, void* stream);
+mvs_status mvs_vit_embed_fwd(const void* a_packed, const void* w_packed, const float* bias, const float* pos, const float* cls_pos, float* x, int NV,
+                             int n, int npad, int channels, void* stream);
+mvs_status mvs_vit_qkv_fwd(const void* xn_packed, const void* w_packed, const float* bias, void* qkv, int NV, int npad, float q_scale, int channels,
+                           void* stream);
+mvs_status mvs_vit_attention_fwd(const void* qkv, void* a_packed, int NV, int ntok, int npad, int heads, int head_dim, void* stream);
 
 /* ---- layout helpers for the nn.Module-level API (NCDHW <-> channel-last) -------------------------*/
-int mvs_ncdhw_to_cl(const float* x, float* y_cl, int B, int C, int D, int H, int W, void* stream);
-int mvs_cl_to_ncdhw(const float* x_cl, float* y, int B, int C, int D, int H, int W, void* stream);
+mvs_status mvs_ncdhw_to_cl(const float* x, float* y_cl, int B, int C, int D, int H, int W, void* stream);
+mvs_status mvs_cl_to_ncdhw(const float* x_cl, float* y, int B, int C, int D, int H, int W, void* stream);
 
 /* ==== the network's glue (DINOv2_mvsformer_model.py:72-88) ===============================================
  * mvs_resize_bicubic_fwd: img fp32 [N,C,H,W] read in place with its four element strides -> out contiguous fp32 [N,C,h,w] =
@@ -705,10 +711,10 @@ int mvs_cl_to_ncdhw(const float* x_cl, float* y, int B, int C, int D, int H, int
  *   neighbour clamped.  (xh, xw) == (h, w): out = base + x bit for bit.  out may be base.
  * The source coordinate is evaluated as an exact rational (floor + once-rounded fraction), not in fp32.  Sizes <= 32768, N * C <= 65535,
  * strides >= 0.  One launch each, no workspace.                                                                     */
-int mvs_resize_bicubic_fwd(const float* img, long long batch_stride, long long channel_stride, long long row_stride, long long col_stride,
-                           float* out, int N, int C, int H, int W, int h, int w, void* stream);
-int mvs_resize_bilinear_add_fwd(const float* base, const float* x, long long batch_stride, long long channel_stride, long long row_stride,
-                                long long col_stride, float* out, int N, int C, int h, int w, int xh, int xw, void* stream);
+mvs_status mvs_resize_bicubic_fwd(const float* img, long long batch_stride, long long channel_stride, long long row_stride, long long col_stride,
+                                  float* out, int N, int C, int H, int W, int h, int w, void* stream);
+mvs_status mvs_resize_bilinear_add_fwd(const float* base, const float* x, long long batch_stride, long long channel_stride, long long row_stride,
+                                       long long col_stride, float* out, int N, int C, int h, int w, int xh, int xw, void* stream);
 
 /* ==== a scene's depth inference: the two ends of the per-view loop (general_eval.py:112-131, test.py:266-294) ====
  * mvs_image_prepare_fwd: src uint8 RGB [h,w,3] (decoded image) -> planar fp32 [3,H,W] = table[c][resized] AND resized uint8 [H,W,3], where
@@ -722,9 +728,9 @@ int mvs_resize_bilinear_add_fwd(const float* base, const float* x, long long bat
  *   rows bottom-up (a PFM body), then uint8 [H,W] = uint8(c * 255) truncated and clamped to 0..255 with c = conf, or (conf * 3 + reg_conf) / 4
  *   as three separately rounded fp32 operations when reg_conf is given.
  * One launch each, no workspace.                                                                                     */
-int mvs_image_prepare_fwd(const unsigned char* src, int h, int w, int pad_rows, const float* table, float* planar, unsigned char* resized,
-                          int H, int W, void* stream);
-int mvs_depth_outputs_pack_fwd(const float* depth, const float* conf, const float* reg_conf, void* staging, int H, int W, void* stream);
+mvs_status mvs_image_prepare_fwd(const unsigned char* src, int h, int w, int pad_rows, const float* table, float* planar, unsigned char* resized,
+                                 int H, int W, void* stream);
+mvs_status mvs_depth_outputs_pack_fwd(const float* depth, const float* conf, const float* reg_conf, void* staging, int H, int W, void* stream);
 
 /* ==== the multi-stage depth losses and the validation metrics (models/losses.py, utils.py:156-189) ================
  * All maps are dense planar fp32: logits / hyp [B,D,H,W], depth / gt / mask [B,H,W] (a pixel counts where mask > 0.5), interval [B].  Every
@@ -748,18 +754,18 @@ int mvs_depth_outputs_pack_fwd(const float* depth, const float* conf, const floa
  *   pixel: NaN), row B = the mean over the images.  Two launches.                                                          */
 #define MVS_METRICS_MAX_T 8
 size_t mvs_loss_workspace_bytes(long long pixels);
-int mvs_ce_loss_fwd(const float* logits, const float* hyp, const float* gt, const float* mask, int inverse, double weight, int* index, float* lse,
-                    void* workspace, size_t workspace_bytes, float* loss, int* count, int B, int D, int H, int W, void* stream);
-int mvs_ce_loss_bwd(const float* logits, const int* index, const float* lse, const float* grad_loss, const int* count, double weight,
-                    float* grad_logits, int B, int D, int H, int W, void* stream);
-int mvs_reg_loss_fwd(const float* depth, const float* gt, const float* mask, const float* interval, const float* hyp, int inverse, double weight,
-                     void* workspace, size_t workspace_bytes, float* loss, int* count, int B, int D, int H, int W, void* stream);
-int mvs_reg_loss_bwd(const float* depth, const float* gt, const float* mask, const float* interval, const float* hyp, int inverse,
-                     const float* grad_loss, const int* count, double weight, float* grad_depth, int B, int D, int H, int W, void* stream);
+mvs_status mvs_ce_loss_fwd(const float* logits, const float* hyp, const float* gt, const float* mask, int inverse, double weight, int* index, float* lse,
+                           void* workspace, size_t workspace_bytes, float* loss, int* count, int B, int D, int H, int W, void* stream);
+mvs_status mvs_ce_loss_bwd(const float* logits, const int* index, const float* lse, const float* grad_loss, const int* count, double weight,
+                           float* grad_logits, int B, int D, int H, int W, void* stream);
+mvs_status mvs_reg_loss_fwd(const float* depth, const float* gt, const float* mask, const float* interval, const float* hyp, int inverse, double weight,
+                            void* workspace, size_t workspace_bytes, float* loss, int* count, int B, int D, int H, int W, void* stream);
+mvs_status mvs_reg_loss_bwd(const float* depth, const float* gt, const float* mask, const float* interval, const float* hyp, int inverse,
+                            const float* grad_loss, const int* count, double weight, float* grad_depth, int B, int D, int H, int W, void* stream);
 size_t mvs_depth_metrics_workspace_bytes(int B, int H, int W, int T);
-int mvs_depth_metrics(const float* est, const float* gt, const void* mask, int mask_bytes, const float* interval, double divisor, int per_sample,
-                      const double* thres, const double* band_lo, const double* band_hi, int T, void* workspace, size_t workspace_bytes,
-                      int* counts, double* sums, float* means, int B, int H, int W, void* stream);
+mvs_status mvs_depth_metrics(const float* est, const float* gt, const void* mask, int mask_bytes, const float* interval, double divisor, int per_sample,
+                             const double* thres, const double* band_lo, const double* band_hi, int T, void* workspace, size_t workspace_bytes,
+                             int* counts, double* sums, float* means, int B, int H, int W, void* stream);
 
 #ifdef __cplusplus
 }

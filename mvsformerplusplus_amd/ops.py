@@ -1,6 +1,10 @@
 """Tensor-level wrappers over the C ABI (include/mvs_hip.h).  Each function allocates its outputs with torch
 (so the caching allocator owns them), enqueues the HIP kernels on the caller's current stream and returns
-fresh tensors.  No autograd: this is the inference path (SURVEY.md section 8f #2 lists backward as next).
+fresh tensors.  No autograd in here: the forward AND backward kernels of the training path are wrapped as plain functions
+(*_bwd, *_wgrad, train_block_*, the losses); training.py builds the torch.autograd.Functions on top of them.
+
+The bound library raises MvsHipError itself when a function the header declares mvs_status returns an error (_lib._GuardedLib),
+so no call site checks a code.
 """
 from __future__ import annotations
 
@@ -11,11 +15,20 @@ from typing import List, Optional, Sequence, Tuple
 import torch
 
 from . import _lib, packing
-from ._lib import check, lib, ptr, stream_of
+from ._lib import lib, ptr, stream_of
 
 
 def _f32c(t: torch.Tensor) -> torch.Tensor:
     return t.contiguous() if t.dtype == torch.float32 else t.float().contiguous()
+
+
+def _workspace(nbytes: int, device, unbuilt: Optional[str] = None) -> torch.Tensor:
+    """The scratch buffer of a mvs_*_workspace_bytes query: uint8 (ptr() wants contiguity, no element type; the allocator aligns far
+    beyond 8 bytes), rounded up past the next multiple of 16 so that it is never empty.  The C side is still told `nbytes`.  With
+    `unbuilt` (the call's name) a query of zero means that nothing is built for the arguments, and raises."""
+    if unbuilt is not None and not nbytes:
+        raise _lib.MvsHipError("%s: not built for these arguments (or out of range)" % unbuilt)
+    return torch.empty((nbytes // 16 + 1) * 16, dtype=torch.uint8, device=device)
 
 
 class PackedFeatures:
@@ -62,7 +75,7 @@ def pack_features(features: torch.Tensor, dtype: Optional[torch.dtype] = None) -
     B, V, Cc, H, W = f.shape
     dtype = f.dtype if dtype is None else dtype
     out = torch.empty(B, V, Cc // 8, H, W, 8, dtype=dtype, device=f.device)
-    check(lib().mvs_pack_features(ptr(f), code, ptr(out), _lib.DTYPE_CODE[dtype], B * V, Cc, H, W, stream_of(f)), "mvs_pack_features")
+    lib().mvs_pack_features(ptr(f), code, ptr(out), _lib.DTYPE_CODE[dtype], B * V, Cc, H, W, stream_of(f))
     return PackedFeatures(out)
 
 
@@ -84,9 +97,8 @@ def conv2d3x3_tiles(x: torch.Tensor, w_packed: torch.Tensor, bias: Optional[torc
     if out is None:
         out = torch.empty(N, cout // 8, H, W, 8, dtype=dtype, device=x.device)
     assert out.shape == (N, cout // 8, H, W, 8) and out.stride()[1:] == (H * W * 8, W * 8, 8, 1) and out.dtype in _lib.DTYPE_CODE, "tiled output [N,C/8,H,W,8]"
-    check(lib().mvs_conv2d3x3_tiles_fwd(ptr(x), _lib.DTYPE_CODE[x.dtype], ptr(w_packed), ptr(bias), 1 if swish else 0, ptr(out), _lib.DTYPE_CODE[out.dtype],
-                                        N, cin, cout, H, W, x.stride(0) if N > 1 else cin * H * W, out.stride(0) if N > 1 else cout * H * W,
-                                        stream_of(x)), "mvs_conv2d3x3_tiles_fwd")
+    lib().mvs_conv2d3x3_tiles_fwd(ptr(x), _lib.DTYPE_CODE[x.dtype], ptr(w_packed), ptr(bias), 1 if swish else 0, ptr(out), _lib.DTYPE_CODE[out.dtype],
+                                  N, cin, cout, H, W, x.stride(0) if N > 1 else cin * H * W, out.stride(0) if N > 1 else cout * H * W, stream_of(x))
     return out
 
 
@@ -112,8 +124,7 @@ def fpn_conv(x: torch.Tensor, w_packed: torch.Tensor, bias: Optional[torch.Tenso
     x = _planar32(x)
     N, cin, H, W = x.shape
     out = torch.empty(N, cout, (H - 1) // stride + 1, (W - 1) // stride + 1, dtype=torch.float32, device=x.device)
-    check(lib().mvs_fpn_conv_fwd(ptr(x), ptr(w_packed), ptr(bias), int(act), ptr(out), N, cin, int(cout), int(k), int(stride), H, W,
-                                 stream_of(x)), "mvs_fpn_conv_fwd")
+    lib().mvs_fpn_conv_fwd(ptr(x), ptr(w_packed), ptr(bias), int(act), ptr(out), N, cin, int(cout), int(k), int(stride), H, W, stream_of(x))
     return out
 
 
@@ -124,8 +135,7 @@ def fpn_merge(prev: torch.Tensor, lateral: torch.Tensor, w_inner: torch.Tensor, 
     N, clat, H, W = lateral.shape
     assert prev.shape == (N, 64, H // 2, W // 2) and H % 2 == 0 and W % 2 == 0, (tuple(prev.shape), tuple(lateral.shape))
     out = torch.empty(N, 64, H, W, dtype=torch.float32, device=lateral.device)
-    check(lib().mvs_fpn_merge_fwd(ptr(prev), ptr(lateral), ptr(_planar32(w_inner)), ptr(_planar32(b_inner)), ptr(out), N, clat, H, W,
-                                  stream_of(lateral)), "mvs_fpn_merge_fwd")
+    lib().mvs_fpn_merge_fwd(ptr(prev), ptr(lateral), ptr(_planar32(w_inner)), ptr(_planar32(b_inner)), ptr(out), N, clat, H, W, stream_of(lateral))
     return out
 
 
@@ -137,16 +147,12 @@ def fpn_merge_conv(prev: torch.Tensor, lateral: torch.Tensor, w_inner: torch.Ten
     N, clat, H, W = lateral.shape
     assert prev.shape == (N, 64, H // 2, W // 2) and H % 2 == 0 and W % 2 == 0, (tuple(prev.shape), tuple(lateral.shape))
     out = torch.empty(N, cout, H, W, dtype=torch.float32, device=lateral.device)
-    check(lib().mvs_fpn_merge_conv_fwd(ptr(prev), ptr(lateral), ptr(_planar32(w_inner)), ptr(_planar32(b_inner)), ptr(w_packed), ptr(bias),
-                                       int(act), ptr(out), N, clat, int(cout), H, W, stream_of(lateral)), "mvs_fpn_merge_conv_fwd")
+    lib().mvs_fpn_merge_conv_fwd(ptr(prev), ptr(lateral), ptr(_planar32(w_inner)), ptr(_planar32(b_inner)), ptr(w_packed), ptr(bias),
+                                 int(act), ptr(out), N, clat, int(cout), H, W, stream_of(lateral))
     return out
 
 
 # ---- FPNDecoder in train mode ----
-def _fpn_ws(nbytes: int, like: torch.Tensor, what: str) -> torch.Tensor:
-    if not nbytes:
-        raise _lib.MvsHipError("%s: not built for these arguments (or out of range)" % what)
-    return torch.empty(nbytes, dtype=torch.uint8, device=like.device)
 
 
 def fpn_bn_swish_fwd(z: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float, conv_bias: Optional[torch.Tensor] = None,
@@ -158,10 +164,11 @@ def fpn_bn_swish_fwd(z: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, e
     z = _planar32(z)
     N, C, H, W = z.shape
     L = lib()
-    ws = _fpn_ws(L.mvs_fpn_bn_workspace_bytes(N, C, H, W), z, "mvs_fpn_bn_swish_fwd")
+    nbytes = L.mvs_fpn_bn_workspace_bytes(N, C, H, W)
+    ws = _workspace(nbytes, z.device, unbuilt="mvs_fpn_bn_swish_fwd")
     stats, y = torch.empty(3, C, dtype=torch.float32, device=z.device), torch.empty_like(z)
-    check(L.mvs_fpn_bn_swish_fwd(ptr(z), ptr(conv_bias), ptr(gamma), ptr(beta), float(eps), float(momentum), ptr(running_mean), ptr(running_var),
-                                 ptr(stats), ptr(y), ptr(ws), ws.numel(), N, C, H, W, stream_of(z)), "mvs_fpn_bn_swish_fwd")
+    L.mvs_fpn_bn_swish_fwd(ptr(z), ptr(conv_bias), ptr(gamma), ptr(beta), float(eps), float(momentum), ptr(running_mean), ptr(running_var),
+                           ptr(stats), ptr(y), ptr(ws), nbytes, N, C, H, W, stream_of(z))
     return y, stats
 
 
@@ -173,11 +180,12 @@ def fpn_bn_swish_bwd(d_y: torch.Tensor, z: torch.Tensor, stats: torch.Tensor, ga
         raise ValueError("d_y must have z's shape %s; got %s" % (tuple(z.shape), tuple(d_y.shape)))
     N, C, H, W = z.shape
     L = lib()
-    ws = _fpn_ws(L.mvs_fpn_bn_workspace_bytes(N, C, H, W), z, "mvs_fpn_bn_swish_bwd")
+    nbytes = L.mvs_fpn_bn_workspace_bytes(N, C, H, W)
+    ws = _workspace(nbytes, z.device, unbuilt="mvs_fpn_bn_swish_bwd")
     d_z = torch.empty_like(z)
     d_gamma, d_beta = torch.empty(C, dtype=torch.float32, device=z.device), torch.empty(C, dtype=torch.float32, device=z.device)
-    check(L.mvs_fpn_bn_swish_bwd(ptr(d_y), ptr(z), ptr(stats), ptr(gamma), ptr(beta), ptr(d_z), ptr(d_gamma), ptr(d_beta), ptr(ws), ws.numel(),
-                                 N, C, H, W, stream_of(z)), "mvs_fpn_bn_swish_bwd")
+    L.mvs_fpn_bn_swish_bwd(ptr(d_y), ptr(z), ptr(stats), ptr(gamma), ptr(beta), ptr(d_z), ptr(d_gamma), ptr(d_beta), ptr(ws), nbytes,
+                           N, C, H, W, stream_of(z))
     return d_z, d_gamma, d_beta
 
 
@@ -196,7 +204,7 @@ def fpn_train_conv(x: torch.Tensor, w: torch.Tensor, out: Optional[torch.Tensor]
         out = torch.empty(N, cout, H, W, dtype=torch.float32, device=x.device)
     assert out.shape == (N, cout, H, W) and out.dtype == torch.float32
     wp = packing.pack_fpn_conv_weights(w, 1)
-    check(lib().mvs_fpn_train_conv_fwd(ptr(x), ptr(wp), ptr(out), N, cin, cout, k, H, W, stream_of(x)), "mvs_fpn_train_conv_fwd")
+    lib().mvs_fpn_train_conv_fwd(ptr(x), ptr(wp), ptr(out), N, cin, cout, k, H, W, stream_of(x))
     return out
 
 
@@ -208,10 +216,10 @@ def fpn_wgrad(d_y: torch.Tensor, x: torch.Tensor, k: int, ones: bool = False) ->
     cin = x.shape[1]
     assert x.shape == (N, cin, H, W), (tuple(d_y.shape), tuple(x.shape))
     L = lib()
-    ws = _fpn_ws(L.mvs_fpn_wgrad_workspace_bytes(N, cin, cout, int(k), int(ones), H, W), x, "mvs_fpn_wgrad (Cout %d, Cin %d, k %d, ones %d)"
-                 % (cout, cin, k, ones))
+    nbytes = L.mvs_fpn_wgrad_workspace_bytes(N, cin, cout, int(k), int(ones), H, W)
+    ws = _workspace(nbytes, x.device, unbuilt="mvs_fpn_wgrad (Cout %d, Cin %d, k %d, ones %d)" % (cout, cin, k, ones))
     d_w = torch.empty(cout, cin + int(ones), k, k, dtype=torch.float32, device=x.device)
-    check(L.mvs_fpn_wgrad(ptr(d_y), ptr(x), ptr(d_w), ptr(ws), ws.numel(), N, cin, cout, int(k), int(ones), H, W, stream_of(x)), "mvs_fpn_wgrad")
+    L.mvs_fpn_wgrad(ptr(d_y), ptr(x), ptr(d_w), ptr(ws), nbytes, N, cin, cout, int(k), int(ones), H, W, stream_of(x))
     return d_w
 
 
@@ -222,10 +230,11 @@ def fpn_merge_wgrad(d_y: torch.Tensor, prev: torch.Tensor, lateral: torch.Tensor
     N, clat, H, W = lateral.shape
     assert clat == 8 and prev.shape == (N, 64, H // 2, W // 2) and d_y.shape == (N, 8, H, W), (tuple(prev.shape), tuple(lateral.shape), tuple(d_y.shape))
     L = lib()
-    ws = _fpn_ws(L.mvs_fpn_merge_wgrad_workspace_bytes(N, H, W), lateral, "mvs_fpn_merge_wgrad")
+    nbytes = L.mvs_fpn_merge_wgrad_workspace_bytes(N, H, W)
+    ws = _workspace(nbytes, lateral.device, unbuilt="mvs_fpn_merge_wgrad")
     d_w = torch.empty(8, 64, 3, 3, dtype=torch.float32, device=lateral.device)
-    check(L.mvs_fpn_merge_wgrad(ptr(d_y), ptr(prev), ptr(lateral), ptr(_planar32(w_inner)), ptr(_planar32(b_inner)), ptr(d_w), ptr(ws), ws.numel(),
-                                N, H, W, stream_of(lateral)), "mvs_fpn_merge_wgrad")
+    L.mvs_fpn_merge_wgrad(ptr(d_y), ptr(prev), ptr(lateral), ptr(_planar32(w_inner)), ptr(_planar32(b_inner)), ptr(d_w), ptr(ws), nbytes,
+                          N, H, W, stream_of(lateral))
     return d_w
 
 
@@ -237,7 +246,7 @@ def fpn_up2_adjoint(d_fine: torch.Tensor, out: Optional[torch.Tensor] = None) ->
     if out is None:
         out = torch.empty(N, 64, H // 2, W // 2, dtype=torch.float32, device=d_fine.device)
     assert out.shape == (N, 64, H // 2, W // 2) and out.dtype == torch.float32
-    check(lib().mvs_fpn_up2_adjoint(ptr(d_fine), ptr(out), N, H, W, stream_of(d_fine)), "mvs_fpn_up2_adjoint")
+    lib().mvs_fpn_up2_adjoint(ptr(d_fine), ptr(out), N, H, W, stream_of(d_fine))
     return out
 
 
@@ -280,9 +289,9 @@ def fmt_kv(x: torch.Tensor, w_packed: torch.Tensor, vectors: torch.Tensor, pe: O
     N, n = x.shape[0], x[0, 0].numel()
     L = lib()
     ws_bytes = L.mvs_fmt_kv_workspace_bytes(N, n)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
+    ws = _workspace(ws_bytes, x.device)
     out = torch.empty(N, L.mvs_fmt_kv_operand_bytes(), dtype=torch.uint8, device=x.device)
-    check(L.mvs_fmt_kv_fwd(ptr(x), ptr(pe), ptr(w_packed), ptr(vectors), ptr(ws), ws_bytes, ptr(out), N, n, stream_of(x)), "mvs_fmt_kv_fwd")
+    L.mvs_fmt_kv_fwd(ptr(x), ptr(pe), ptr(w_packed), ptr(vectors), ptr(ws), ws_bytes, ptr(out), N, n, stream_of(x))
     return out
 
 
@@ -298,8 +307,7 @@ def fmt_block(x: torch.Tensor, kv_operand: torch.Tensor, w_packed: torch.Tensor,
     assert kv_div >= 1 and kv_operand.shape[0] * kv_div >= N and kv_operand.shape[1] == lib().mvs_fmt_kv_operand_bytes(), \
         (tuple(kv_operand.shape), kv_div, N)
     out = torch.empty_like(x)
-    check(lib().mvs_fmt_block_fwd(ptr(x), ptr(pe), ptr(kv_operand), ptr(w_packed), ptr(vectors), ptr(out), N, n, int(kv_div), stream_of(x)),
-          "mvs_fmt_block_fwd")
+    lib().mvs_fmt_block_fwd(ptr(x), ptr(pe), ptr(kv_operand), ptr(w_packed), ptr(vectors), ptr(out), N, n, int(kv_div), stream_of(x))
     return out
 
 
@@ -317,8 +325,7 @@ def fmt_path(prev: torch.Tensor, lateral: torch.Tensor, w_reduce: torch.Tensor, 
     prev, lateral, w_reduce, N, C, h, w, H, W = _fmt_level(prev, lateral, w_reduce)
     _fmt_smooth_weights(w_packed, C)
     out = torch.empty_like(lateral)
-    check(lib().mvs_fmt_path_fwd(ptr(prev), ptr(lateral), ptr(w_reduce), ptr(w_packed), ptr(out), N, C, h, w, H, W, stream_of(lateral)),
-          "mvs_fmt_path_fwd")
+    lib().mvs_fmt_path_fwd(ptr(prev), ptr(lateral), ptr(w_reduce), ptr(w_packed), ptr(out), N, C, h, w, H, W, stream_of(lateral))
     return out
 
 
@@ -326,7 +333,7 @@ def fmt_merge(prev: torch.Tensor, lateral: torch.Tensor, w_reduce: torch.Tensor)
     """The merged map of a pathway level, written out (the unfused form): bilinear(dim_reduction(prev)) + lateral -> [N,C,H,W] fp32."""
     prev, lateral, w_reduce, N, C, h, w, H, W = _fmt_level(prev, lateral, w_reduce)
     out = torch.empty_like(lateral)
-    check(lib().mvs_fmt_merge_fwd(ptr(prev), ptr(lateral), ptr(w_reduce), ptr(out), N, C, h, w, H, W, stream_of(lateral)), "mvs_fmt_merge_fwd")
+    lib().mvs_fmt_merge_fwd(ptr(prev), ptr(lateral), ptr(w_reduce), ptr(out), N, C, h, w, H, W, stream_of(lateral))
     return out
 
 
@@ -336,7 +343,7 @@ def fmt_smooth(x: torch.Tensor, w_packed: torch.Tensor) -> torch.Tensor:
     N, C, H, W = x.shape
     _fmt_smooth_weights(w_packed, C)
     out = torch.empty_like(x)
-    check(lib().mvs_fmt_smooth_fwd(ptr(x), ptr(w_packed), ptr(out), N, C, H, W, stream_of(x)), "mvs_fmt_smooth_fwd")
+    lib().mvs_fmt_smooth_fwd(ptr(x), ptr(w_packed), ptr(out), N, C, H, W, stream_of(x))
     return out
 
 
@@ -354,10 +361,9 @@ def fmt_path_bwd(d_merged: torch.Tensor, prev: torch.Tensor, w_reduce: torch.Ten
     prev, d_merged, w_reduce, N, C, h, w, H, W = _fmt_level(prev, d_merged, w_reduce)
     L = lib()
     ws_bytes = L.mvs_fmt_path_bwd_workspace_bytes(N, C, h, w)
-    ws = torch.empty(max(ws_bytes, 4), dtype=torch.uint8, device=prev.device)
+    ws = _workspace(ws_bytes, prev.device)
     d_prev, d_w = torch.empty_like(prev), torch.empty(C, 2 * C, dtype=torch.float32, device=prev.device)
-    check(L.mvs_fmt_path_bwd(ptr(d_merged), ptr(prev), ptr(w_reduce), ptr(d_prev), ptr(d_w), ptr(ws), ws_bytes, N, C, h, w, H, W, stream_of(prev)),
-          "mvs_fmt_path_bwd")
+    L.mvs_fmt_path_bwd(ptr(d_merged), ptr(prev), ptr(w_reduce), ptr(d_prev), ptr(d_w), ptr(ws), ws_bytes, N, C, h, w, H, W, stream_of(prev))
     return d_prev, d_w
 
 
@@ -369,10 +375,9 @@ def fmt_smooth_wgrad(d_y: torch.Tensor, prev: torch.Tensor, lateral: torch.Tenso
     d_y = _fmt_level_grad(d_y, lateral.shape, "d_y")
     L = lib()
     ws_bytes = L.mvs_fmt_smooth_wgrad_workspace_bytes(N, C, H, W)
-    ws = torch.empty(max(ws_bytes, 4), dtype=torch.uint8, device=lateral.device)
+    ws = _workspace(ws_bytes, lateral.device)
     d_w = torch.empty(C, C, 3, 3, dtype=torch.float32, device=lateral.device)
-    check(L.mvs_fmt_smooth_wgrad(ptr(d_y), ptr(prev), ptr(lateral), ptr(w_reduce), ptr(d_w), ptr(ws), ws_bytes, N, C, h, w, H, W,
-                                 stream_of(lateral)), "mvs_fmt_smooth_wgrad")
+    L.mvs_fmt_smooth_wgrad(ptr(d_y), ptr(prev), ptr(lateral), ptr(w_reduce), ptr(d_w), ptr(ws), ws_bytes, N, C, h, w, H, W, stream_of(lateral))
     return d_w
 
 
@@ -437,10 +442,9 @@ def vitdec_rows(inp: torch.Tensor, v0: int, views: int, *, prev: Optional[torch.
         raise ValueError("vitdec_rows: nothing to compute")
     x = torch.empty(M, 768, dtype=torch.float32, device=inp.device) if want_x else None
     xn = torch.empty(L.mvs_vitdec_packed_bytes(M, 768), dtype=torch.uint8, device=inp.device) if ln is not None else None
-    check(L.mvs_vitdec_rows_fwd(_base_ptr(inp), _lib.DTYPE_CODE[inp.dtype], inp.stride(0), inp.stride(1), inp.stride(2), int(v0), int(views),
-                                ptr(prev), ptr(prev_value) if prev is not None else None, ptr(mix[0]) if mix else None,
-                                ptr(mix[1]) if mix else None, ptr(x), ptr(xp), out_V, int(out_v0), ptr(ln[0]) if ln else None,
-                                ptr(ln[1]) if ln else None, ptr(xn), B * views, n, 768, stream_of(inp)), "mvs_vitdec_rows_fwd")
+    L.mvs_vitdec_rows_fwd(_base_ptr(inp), _lib.DTYPE_CODE[inp.dtype], inp.stride(0), inp.stride(1), inp.stride(2), int(v0), int(views), ptr(prev),
+                          ptr(prev_value) if prev is not None else None, ptr(mix[0]) if mix else None, ptr(mix[1]) if mix else None, ptr(x), ptr(xp),
+                          out_V, int(out_v0), ptr(ln[0]) if ln else None, ptr(ln[1]) if ln else None, ptr(xn), B * views, n, 768, stream_of(inp))
     return x, xp, xn
 
 
@@ -464,8 +468,8 @@ def vitdec_linear(a_packed: torch.Tensor, M: int, w_packed: torch.Tensor, K: int
         out = torch.empty(lib().mvs_vitdec_packed_bytes(M, N), dtype=torch.uint8, device=a_packed.device)
     else:
         out = torch.empty(M, N, dtype=torch.float32, device=a_packed.device)
-    check(lib().mvs_vitdec_linear_fwd(ptr(a_packed), ptr(w_packed), ptr(bias), ptr(gamma), ptr(residual), ptr(out), int(M), int(K), int(N),
-                                      int(epilogue), int(elu_cols), stream_of(a_packed)), "mvs_vitdec_linear_fwd")
+    lib().mvs_vitdec_linear_fwd(ptr(a_packed), ptr(w_packed), ptr(bias), ptr(gamma), ptr(residual), ptr(out), int(M), int(K), int(N),
+                                int(epilogue), int(elu_cols), stream_of(a_packed))
     return out
 
 
@@ -476,9 +480,9 @@ def vitdec_kv(kv: torch.Tensor, NV: int, n: int) -> torch.Tensor:
         raise ValueError("kv must be contiguous fp32 [NV * n, 1536]; got %s %s" % (kv.dtype, tuple(kv.shape)))
     L = lib()
     ws_bytes = L.mvs_vitdec_kv_workspace_bytes(NV, n)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=kv.device)
+    ws = _workspace(ws_bytes, kv.device)
     out = torch.empty(NV, 12, 64 * 64 + 64, dtype=torch.float32, device=kv.device)
-    check(L.mvs_vitdec_kv_fwd(ptr(kv), ptr(ws), ws_bytes, ptr(out), NV, n, kv.shape[1], stream_of(kv)), "mvs_vitdec_kv_fwd")
+    L.mvs_vitdec_kv_fwd(ptr(kv), ptr(ws), ws_bytes, ptr(out), NV, n, kv.shape[1], stream_of(kv))
     return out
 
 
@@ -492,7 +496,7 @@ def vitdec_apply(q: torch.Tensor, summary: torch.Tensor, NV: int, n: int, kv_div
         raise ValueError("summary must be vitdec_kv's fp32 [NVkv, 12, 4160] with NVkv * kv_div >= NV; got %s, kv_div %d, NV %d"
                          % (tuple(summary.shape), kv_div, NV))
     out = torch.empty(lib().mvs_vitdec_packed_bytes(NV * n, 768), dtype=torch.uint8, device=q.device)
-    check(lib().mvs_vitdec_apply_fwd(ptr(q), ptr(summary), ptr(out), NV, n, int(kv_div), q.shape[1], stream_of(q)), "mvs_vitdec_apply_fwd")
+    lib().mvs_vitdec_apply_fwd(ptr(q), ptr(summary), ptr(out), NV, n, int(kv_div), q.shape[1], stream_of(q))
     return out
 
 
@@ -516,8 +520,7 @@ def vitdec_conv(x_packed: torch.Tensor, w_packed: torch.Tensor, bias: torch.Tens
             out = torch.empty(lib().mvs_vitdec_packed_bytes(NV * s * H * s * W, cout), dtype=torch.uint8, device=x_packed.device)
     else:
         out = torch.empty(1, dtype=torch.uint8, device=x_packed.device)       # the library refuses the layer
-    check(lib().mvs_vitdec_conv_fwd(ptr(x_packed), ptr(w_packed), ptr(bias), ptr(out), int(layer), 1 if planar else 0, NV, H, W,
-                                    stream_of(x_packed)), "mvs_vitdec_conv_fwd")
+    lib().mvs_vitdec_conv_fwd(ptr(x_packed), ptr(w_packed), ptr(bias), ptr(out), int(layer), 1 if planar else 0, NV, H, W, stream_of(x_packed))
     return out
 
 
@@ -546,9 +549,8 @@ def vit_rows(x: torch.Tensor, *, ln: Optional[Tuple[torch.Tensor, torch.Tensor]]
     L = lib()
     y = torch.empty_like(x) if norm is not None else None
     xn = torch.empty(L.mvs_vitdec_packed_bytes(M, 768), dtype=torch.uint8, device=x.device) if ln is not None else None
-    check(L.mvs_vit_rows_fwd(ptr(x), 0, M * 768, M * 768, 768, 0, 1, None, None, ptr(norm[0]) if norm else None, ptr(norm[1]) if norm else None,
-                             ptr(y), None, 1, 0, ptr(ln[0]) if ln else None, ptr(ln[1]) if ln else None, float(eps), ptr(xn), 1, M, 768,
-                             stream_of(x)), "mvs_vit_rows_fwd")
+    L.mvs_vit_rows_fwd(ptr(x), 0, M * 768, M * 768, 768, 0, 1, None, None, ptr(norm[0]) if norm else None, ptr(norm[1]) if norm else None, ptr(y),
+                       None, 1, 0, ptr(ln[0]) if ln else None, ptr(ln[1]) if ln else None, float(eps), ptr(xn), 1, M, 768, stream_of(x))
     return y, xn
 
 
@@ -562,8 +564,8 @@ def vit_patches(img: torch.Tensor) -> torch.Tensor:
     NV, _, H, W = img.shape
     gh, gw = H // 14, W // 14
     out = torch.empty(lib().mvs_vitdec_packed_bytes(NV * gh * gw, VIT_KPAD), dtype=torch.uint8, device=img.device)
-    check(lib().mvs_vit_patches_fwd(_base_ptr(img), _lib.DTYPE_CODE[img.dtype], img.stride(0), img.stride(1), img.stride(2), img.stride(3),
-                                    ptr(out), NV, gh, gw, 14, 3, stream_of(img)), "mvs_vit_patches_fwd")
+    lib().mvs_vit_patches_fwd(_base_ptr(img), _lib.DTYPE_CODE[img.dtype], img.stride(0), img.stride(1), img.stride(2), img.stride(3),
+                              ptr(out), NV, gh, gw, 14, 3, stream_of(img))
     return out
 
 
@@ -581,8 +583,7 @@ def vit_embed(a_packed: torch.Tensor, w_packed: torch.Tensor, bias: torch.Tensor
     _vitdec_vec(cls_pos, 768, "cls_pos", a_packed)
     npad = vit_npad(n + 1)
     x = torch.empty(NV * npad, 768, dtype=torch.float32, device=a_packed.device)
-    check(lib().mvs_vit_embed_fwd(ptr(a_packed), ptr(w_packed), ptr(bias), ptr(pos), ptr(cls_pos), ptr(x), int(NV), int(n), npad, 768,
-                                  stream_of(a_packed)), "mvs_vit_embed_fwd")
+    lib().mvs_vit_embed_fwd(ptr(a_packed), ptr(w_packed), ptr(bias), ptr(pos), ptr(cls_pos), ptr(x), int(NV), int(n), npad, 768, stream_of(a_packed))
     return x
 
 
@@ -597,8 +598,7 @@ def vit_qkv(xn_packed: torch.Tensor, w_packed: torch.Tensor, bias: torch.Tensor,
                          % (2 * 768 * 2304, w_packed.dtype, w_packed.numel()))
     _vitdec_vec(bias, 2304, "bias", xn_packed)
     out = torch.empty(lib().mvs_vit_qkv_bytes(NV, npad), dtype=torch.uint8, device=xn_packed.device)
-    check(lib().mvs_vit_qkv_fwd(ptr(xn_packed), ptr(w_packed), ptr(bias), ptr(out), int(NV), int(npad), float(q_scale), 768,
-                                stream_of(xn_packed)), "mvs_vit_qkv_fwd")
+    lib().mvs_vit_qkv_fwd(ptr(xn_packed), ptr(w_packed), ptr(bias), ptr(out), int(NV), int(npad), float(q_scale), 768, stream_of(xn_packed))
     return out
 
 
@@ -611,8 +611,7 @@ def vit_attention(qkv: torch.Tensor, NV: int, ntok: int, npad: int, heads: int =
         raise ValueError("qkv must be vit_qkv's uint8 tensor of mvs_vit_qkv_bytes(%d, %d) = %d bytes; got %s %s"
                          % (NV, npad, want, qkv.dtype, tuple(qkv.shape)))
     out = torch.empty(lib().mvs_vitdec_packed_bytes(NV * npad, 768), dtype=torch.uint8, device=qkv.device)
-    check(lib().mvs_vit_attention_fwd(ptr(qkv), ptr(out), int(NV), int(ntok), int(npad), int(heads), int(head_dim), stream_of(qkv)),
-          "mvs_vit_attention_fwd")
+    lib().mvs_vit_attention_fwd(ptr(qkv), ptr(out), int(NV), int(ntok), int(npad), int(heads), int(head_dim), stream_of(qkv))
     return out
 
 
@@ -638,7 +637,7 @@ def compose_homography(proj_matrices: torch.Tensor) -> torch.Tensor:
     B, V = p.shape[:2]
     assert p.shape[2:] == (2, 4, 4), "proj_matrices must be [B,V,2,4,4]"
     out = torch.empty(B, V - 1, 12, dtype=torch.float32, device=p.device)
-    check(lib().mvs_compose_homography(ptr(p), B, V, ptr(out), stream_of(p)), "mvs_compose_homography")
+    lib().mvs_compose_homography(ptr(p), B, V, ptr(out), stream_of(p))
     return out
 
 
@@ -658,8 +657,8 @@ def cascade_prologue(proj_matrices: Sequence[torch.Tensor], depth_values: Option
         N = dv.shape[1]
         hyp = torch.empty(B, ndepths, H, W, dtype=torch.float32, device=dv.device)
     pa = _ptr_array(ps)
-    check(lib().mvs_cascade_prologue_fwd(C.cast(pa, C.c_void_p), len(ps), B, V, ptr(hom), ptr(dv), N, 1 if inverse else 0, ptr(hyp), ndepths, H, W,
-                                         stream_of(ps[0])), "mvs_cascade_prologue_fwd")
+    lib().mvs_cascade_prologue_fwd(C.cast(pa, C.c_void_p), len(ps), B, V, ptr(hom), ptr(dv), N, 1 if inverse else 0, ptr(hyp), ndepths, H, W,
+                                   stream_of(ps[0]))
     return list(hom.unbind(0)), hyp
 
 
@@ -667,7 +666,7 @@ def homography_from_proj(src_proj: torch.Tensor, ref_proj: torch.Tensor) -> torc
     s, r = _f32c(src_proj), _f32c(ref_proj)
     B = s.shape[0]
     out = torch.empty(B, 12, dtype=torch.float32, device=s.device)
-    check(lib().mvs_homography_from_proj(ptr(s), ptr(r), B, ptr(out), stream_of(s)), "mvs_homography_from_proj")
+    lib().mvs_homography_from_proj(ptr(s), ptr(r), B, ptr(out), stream_of(s))
     return out
 
 
@@ -680,8 +679,7 @@ def homo_warp(src_fea: torch.Tensor, homography: torch.Tensor, depth_values: tor
     is_vol = 1 if dv.dim() == 4 else 0
     warped = torch.empty(B, Cc, D, H, W, dtype=torch.float32, device=f.device) if want_warped else None
     mask = torch.empty(B, D, H, W, dtype=torch.uint8, device=f.device) if want_mask else None
-    check(lib().mvs_homo_warp_fwd(ptr(f), code, ptr(homography.contiguous()), ptr(dv), is_vol, ptr(warped), ptr(mask),
-                                  B, Cc, D, H, W, stream_of(f)), "mvs_homo_warp_fwd")
+    lib().mvs_homo_warp_fwd(ptr(f), code, ptr(homography.contiguous()), ptr(dv), is_vol, ptr(warped), ptr(mask), B, Cc, D, H, W, stream_of(f))
     return warped, (mask.bool() if mask is not None else None)
 
 
@@ -701,8 +699,8 @@ def warp_corr_entropy(features: torch.Tensor, code: int, homography: torch.Tenso
     else:
         ent = torch.zeros(B, V - 1, H, W, dtype=torch.float32, device=features.device)
     ft, layout = _feat_ptr(features)
-    check(lib().mvs_warp_corr_entropy_fwd(ptr(ft), code, layout, ptr(homography), ptr(hyp), ptr(ent), B, V, Cc, G, D, H, W,
-                                          view_begin, view_end, 1 if f16_window else 0, stream_of(ft)), "mvs_warp_corr_entropy_fwd")
+    lib().mvs_warp_corr_entropy_fwd(ptr(ft), code, layout, ptr(homography), ptr(hyp), ptr(ent), B, V, Cc, G, D, H, W,
+                                    view_begin, view_end, 1 if f16_window else 0, stream_of(ft))
     return ent
 
 
@@ -713,9 +711,8 @@ def vis_weight(entropy: torch.Tensor, params: Sequence[torch.Tensor], precision:
     N = e.numel() // (H * W)
     vis = torch.empty_like(e)
     nbytes = lib().mvs_vis_workspace_bytes(N, H, W, precision)
-    ws = torch.empty(max(nbytes // 4, 4), dtype=torch.float32, device=e.device)
-    check(lib().mvs_vis_weight_fwd(ptr(e), *[ptr(p) for p in params], ptr(vis), ptr(ws), nbytes, N, H, W, precision, stream_of(e)),
-          "mvs_vis_weight_fwd")
+    ws = _workspace(nbytes, e.device)
+    lib().mvs_vis_weight_fwd(ptr(e), *[ptr(p) for p in params], ptr(vis), ptr(ws), nbytes, N, H, W, precision, stream_of(e))
     return vis
 
 
@@ -724,14 +721,14 @@ def vis_conv1(entropy: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor) -> torc
     H, W = e.shape[-2:]
     N = e.numel() // (H * W)
     out = torch.empty(N, H, W, 16, dtype=torch.float32, device=e.device)
-    check(lib().mvs_vis_conv1_fwd(ptr(e), ptr(w1), ptr(b1), ptr(out), N, H, W, stream_of(e)), "mvs_vis_conv1_fwd")
+    lib().mvs_vis_conv1_fwd(ptr(e), ptr(w1), ptr(b1), ptr(out), N, H, W, stream_of(e))
     return out
 
 
 def vis_out(x_cl8: torch.Tensor, w4: torch.Tensor, b4: torch.Tensor, shape) -> torch.Tensor:
     N, H, W, _ = x_cl8.shape
     vis = torch.empty(shape, dtype=torch.float32, device=x_cl8.device)
-    check(lib().mvs_vis_out_fwd(ptr(x_cl8), ptr(w4), ptr(b4), ptr(vis), N, H, W, stream_of(x_cl8)), "mvs_vis_out_fwd")
+    lib().mvs_vis_out_fwd(ptr(x_cl8), ptr(w4), ptr(b4), ptr(vis), N, H, W, stream_of(x_cl8))
     return vis
 
 
@@ -750,9 +747,9 @@ def warp_corr_aggregate(features: torch.Tensor, code: int, homography: torch.Ten
         vol = torch.empty(B, D, H, W, G, dtype=torch.float16 if f16 else torch.float32, device=features.device)
         vsum = None if normalise else torch.empty(B, H, W, dtype=torch.float32, device=features.device)
     ft, layout = _feat_ptr(features)
-    check(lib().mvs_warp_corr_aggregate_fwd(ptr(ft), code, layout, ptr(homography), ptr(hyp), ptr(vis), ptr(vol), ptr(vsum),
-                                            1 if normalise else 0, _lib.VOLUME_F16 if f16 else (_lib.VOLUME_SPLIT if split else _lib.VOLUME_F32), B, V, Cc, G, D, H, W,
-                                            view_begin, view_end, stream_of(ft)), "mvs_warp_corr_aggregate_fwd")
+    lib().mvs_warp_corr_aggregate_fwd(ptr(ft), code, layout, ptr(homography), ptr(hyp), ptr(vis), ptr(vol), ptr(vsum),
+                                      1 if normalise else 0, _lib.VOLUME_F16 if f16 else (_lib.VOLUME_SPLIT if split else _lib.VOLUME_F32), B, V, Cc, G, D, H, W,
+                                      view_begin, view_end, stream_of(ft))
     return vol, vsum
 
 
@@ -763,16 +760,14 @@ def warp_corr_aggregate_bwd(features: torch.Tensor, code: int, homography: torch
     D = hyp.shape[1]
     gfeat = torch.empty(B, V, Cc, H, W, dtype=torch.float32, device=features.device)
     gvis = torch.empty(B, V - 1, H, W, dtype=torch.float32, device=features.device)
-    check(lib().mvs_warp_corr_aggregate_bwd(ptr(features), code, ptr(homography), ptr(hyp), ptr(vis), ptr(vis_sum), ptr(volume_cl),
-                                            ptr(grad_volume_cl), ptr(gfeat), ptr(gvis), B, V, Cc, G, D, H, W, stream_of(features)),
-          "mvs_warp_corr_aggregate_bwd")
+    lib().mvs_warp_corr_aggregate_bwd(ptr(features), code, ptr(homography), ptr(hyp), ptr(vis), ptr(vis_sum), ptr(volume_cl),
+                                      ptr(grad_volume_cl), ptr(gfeat), ptr(gvis), B, V, Cc, G, D, H, W, stream_of(features))
     return gfeat, gvis
 
 
 def volume_normalise_(vol_cl: torch.Tensor, vis_sum: torch.Tensor, split: bool = False) -> torch.Tensor:
     B, D, H, W, G = vol_cl.shape
-    check(lib().mvs_volume_normalise(ptr(vol_cl), ptr(vis_sum), B, D, H, W, G, _lib.VOLUME_SPLIT if split else _lib.VOLUME_F32,
-                                     stream_of(vol_cl)), "mvs_volume_normalise")
+    lib().mvs_volume_normalise(ptr(vol_cl), ptr(vis_sum), B, D, H, W, G, _lib.VOLUME_SPLIT if split else _lib.VOLUME_F32, stream_of(vol_cl))
     return vol_cl
 
 
@@ -799,9 +794,8 @@ def warp_corr_entropy_keep(features, code: int, homography: torch.Tensor, hyp: t
     ft, layout = _feat_ptr(features)
     ent = torch.empty(B, V - 1, H, W, dtype=torch.float32, device=ft.device)
     corr = torch.empty(B, V - 1, D, H, W, 8, dtype=torch.float32 if exact else torch.float16, device=ft.device)
-    check(lib().mvs_warp_corr_entropy_keep_fwd(ptr(ft), code, layout, ptr(homography), ptr(hyp), ptr(ent), ptr(corr),
-                                               _lib.CORR_F32 if exact else _lib.CORR_F16, B, V, Cc, G, D, H, W, stream_of(ft)),
-          "mvs_warp_corr_entropy_keep_fwd")
+    lib().mvs_warp_corr_entropy_keep_fwd(ptr(ft), code, layout, ptr(homography), ptr(hyp), ptr(ent), ptr(corr),
+                                         _lib.CORR_F32 if exact else _lib.CORR_F16, B, V, Cc, G, D, H, W, stream_of(ft))
     return ent, corr
 
 
@@ -817,7 +811,7 @@ def corr_aggregate(corr: torch.Tensor, vis: torch.Tensor, split: bool = False, f
     vol = torch.empty(B, D, H, W, 8, dtype=torch.float16 if f16 else torch.float32, device=corr.device)
     fmt = _lib.VOLUME_F16 if f16 else (_lib.VOLUME_SPLIT if split else _lib.VOLUME_F32)
     cfmt = _lib.CORR_F32 if corr.dtype == torch.float32 else _lib.CORR_F16
-    check(lib().mvs_corr_aggregate_fwd(ptr(corr), cfmt, ptr(v), ptr(vol), fmt, B, NV + 1, D, H, W, stream_of(corr)), "mvs_corr_aggregate_fwd")
+    lib().mvs_corr_aggregate_fwd(ptr(corr), cfmt, ptr(v), ptr(vol), fmt, B, NV + 1, D, H, W, stream_of(corr))
     return vol
 
 
@@ -834,7 +828,7 @@ def volume_to_f16(vol_cl: torch.Tensor, vis_sum: Optional[torch.Tensor] = None) 
     """fp32 volume [B,D,H,W,8] (divided by vis_sum + 1e-6 first when given) -> fp16 in a new buffer, clamped to the fp16 range."""
     B, D, H, W, G = vol_cl.shape
     out = torch.empty(B, D, H, W, G, dtype=torch.float16, device=vol_cl.device)
-    check(lib().mvs_volume_to_f16(ptr(vol_cl), ptr(vis_sum), ptr(out), B, D, H, W, G, stream_of(vol_cl)), "mvs_volume_to_f16")
+    lib().mvs_volume_to_f16(ptr(vol_cl), ptr(vis_sum), ptr(out), B, D, H, W, G, stream_of(vol_cl))
     return out
 
 
@@ -848,8 +842,7 @@ def slab_pack(vol_cl: torch.Tensor, vis_sum: torch.Tensor, send_bufs, rows) -> N
     ptrs = (C.c_void_p * n)(*[None if b is None else ptr(b) for b in send_bufs])
     r0 = (C.c_int * n)(*[int(r[0]) for r in rows])
     r1 = (C.c_int * n)(*[int(r[1]) for r in rows])
-    check(fn(ptr(vol_cl), ptr(vis_sum), C.cast(ptrs, C.c_void_p), C.cast(r0, C.c_void_p), C.cast(r1, C.c_void_p), n, B, D, H, W, G,
-             stream_of(vol_cl)), "mvs_slab_pack")
+    fn(ptr(vol_cl), ptr(vis_sum), C.cast(ptrs, C.c_void_p), C.cast(r0, C.c_void_p), C.cast(r1, C.c_void_p), n, B, D, H, W, G, stream_of(vol_cl))
 
 
 def slab_reduce(vol_cl: torch.Tensor, vis_sum: torch.Tensor, recv_bufs, my_rank: int, out: torch.Tensor, r0: int, r1: int) -> torch.Tensor:
@@ -860,8 +853,7 @@ def slab_reduce(vol_cl: torch.Tensor, vis_sum: torch.Tensor, recv_bufs, my_rank:
     n = len(recv_bufs)
     fn = lib().mvs_slab_reduce        # before the pointer array, see slab_pack
     ptrs = (C.c_void_p * n)(*[None if b is None else ptr(b) for b in recv_bufs])
-    check(fn(ptr(vol_cl), ptr(vis_sum), C.cast(ptrs, C.c_void_p), n, my_rank, ptr(out), r0, r1, B, D, H, W, G, stream_of(vol_cl)),
-          "mvs_slab_reduce")
+    fn(ptr(vol_cl), ptr(vis_sum), C.cast(ptrs, C.c_void_p), n, my_rank, ptr(out), r0, r1, B, D, H, W, G, stream_of(vol_cl))
     return out
 
 
@@ -897,8 +889,8 @@ def conv3d_bn_relu(x_cl: torch.Tensor, w_packed: torch.Tensor, bias: torch.Tenso
     pd = kd // 2
     od, oh, ow = (D + 2 * pd - kd) // sd + 1, (H - 1) // sh + 1, (W - 1) // sw + 1
     y = torch.empty(B, od, oh, ow, cout, dtype=_act_dtype(x_cl, precision), device=x_cl.device)
-    check(lib().mvs_conv3d_bn_relu_fwd(ptr(x_cl), ptr(w_packed), ptr(bias), ptr(y), B, cin, cout, D, H, W, kd, sd, sh, sw,
-                                       1 if relu else 0, precision, stream_of(x_cl)), "mvs_conv3d_bn_relu_fwd")
+    lib().mvs_conv3d_bn_relu_fwd(ptr(x_cl), ptr(w_packed), ptr(bias), ptr(y), B, cin, cout, D, H, W, kd, sd, sh, sw,
+                                 1 if relu else 0, precision, stream_of(x_cl))
     return y
 
 
@@ -908,8 +900,8 @@ def deconv3d_bn_relu_add(x_cl: torch.Tensor, w_packed: torch.Tensor, bias: torch
     y = torch.empty(B, D * sd, 2 * H, 2 * W, cout, dtype=_act_dtype(x_cl, precision), device=x_cl.device)
     if skip_cl is not None:
         assert tuple(skip_cl.shape) == tuple(y.shape) and skip_cl.dtype == y.dtype, "skip tensor shape / dtype mismatch"
-    check(lib().mvs_deconv3d_bn_relu_add_fwd(ptr(x_cl), ptr(w_packed), ptr(bias), ptr(skip_cl), ptr(y), B, cin, cout, D, H, W,
-                                             sd, precision, stream_of(x_cl)), "mvs_deconv3d_bn_relu_add_fwd")
+    lib().mvs_deconv3d_bn_relu_add_fwd(ptr(x_cl), ptr(w_packed), ptr(bias), ptr(skip_cl), ptr(y), B, cin, cout, D, H, W,
+                                       sd, precision, stream_of(x_cl))
     return y
 
 
@@ -942,9 +934,8 @@ def conv3d_generic(x_cl: torch.Tensor, w_tck: torch.Tensor, bias: Optional[torch
     y = torch.empty(B, out[0], out[1], out[2], cout, dtype=torch.float32, device=x_cl.device)
     if skip_cl is not None and (tuple(skip_cl.shape) != tuple(y.shape) or skip_cl.dtype != torch.float32):
         raise _lib.MvsHipError("skip tensor %s / %s does not match the layer output %s fp32" % (tuple(skip_cl.shape), skip_cl.dtype, tuple(y.shape)))
-    check(lib().mvs_conv3d_generic_fwd(ptr(x_cl), ptr(w_tck), ptr(bias), ptr(skip_cl), ptr(y), B, cin, cout, D, H, W, out[0], out[1], out[2],
-                                       k[0], k[1], k[2], s[0], s[1], s[2], p[0], p[1], p[2], 1 if transposed else 0, 1 if relu else 0,
-                                       stream_of(x_cl)), "mvs_conv3d_generic_fwd")
+    lib().mvs_conv3d_generic_fwd(ptr(x_cl), ptr(w_tck), ptr(bias), ptr(skip_cl), ptr(y), B, cin, cout, D, H, W, out[0], out[1], out[2], k[0], k[1],
+                                 k[2], s[0], s[1], s[2], p[0], p[1], p[2], 1 if transposed else 0, 1 if relu else 0, stream_of(x_cl))
     return y
 
 
@@ -955,8 +946,8 @@ def deconv3d_prob(x_cl: torch.Tensor, w_packed: torch.Tensor, bias: torch.Tensor
     _act_dtype(x_cl, precision)
     _act_dtype(skip_cl, precision)
     logits = torch.empty(B, D * sd, 2 * H, 2 * W, dtype=torch.float32, device=x_cl.device)
-    check(lib().mvs_deconv3d_prob_fwd(ptr(x_cl), ptr(w_packed), ptr(bias), ptr(skip_cl), ptr(prob_w), ptr(prob_b), ptr(logits), B, cin, D, H, W,
-                                      sd, precision, stream_of(x_cl)), "mvs_deconv3d_prob_fwd")
+    lib().mvs_deconv3d_prob_fwd(ptr(x_cl), ptr(w_packed), ptr(bias), ptr(skip_cl), ptr(prob_w), ptr(prob_b), ptr(logits), B, cin, D, H, W,
+                                sd, precision, stream_of(x_cl))
     return logits
 
 
@@ -965,8 +956,7 @@ def deconv3d_linear(x_cl: torch.Tensor, w_packed: torch.Tensor, zero_bias: torch
     """ConvTranspose3d(k3, padding 1, stride (sd,2,2), output_padding (sd-1,1,1)) without bias / BatchNorm / ReLU."""
     B, D, H, W, cin = x_cl.shape
     y = torch.empty(B, D * sd, 2 * H, 2 * W, cout, dtype=torch.float32, device=x_cl.device)
-    check(lib().mvs_deconv3d_linear_fwd(ptr(x_cl), ptr(w_packed), ptr(zero_bias), ptr(y), B, cin, cout, D, H, W, sd, precision, stream_of(x_cl)),
-          "mvs_deconv3d_linear_fwd")
+    lib().mvs_deconv3d_linear_fwd(ptr(x_cl), ptr(w_packed), ptr(zero_bias), ptr(y), B, cin, cout, D, H, W, sd, precision, stream_of(x_cl))
     return y
 
 
@@ -974,7 +964,7 @@ def bn_stats(x_cl: torch.Tensor, groups: int = 1) -> torch.Tensor:
     """-> float64 [groups, 2C] (or [2C]): per-channel [sum x | sum x^2] of each of `groups` equal slices along the leading axis."""
     Cc = x_cl.shape[-1]
     sums = torch.empty(groups, 2 * Cc, dtype=torch.float64, device=x_cl.device)
-    check(lib().mvs_bn_stats(ptr(x_cl), ptr(sums), x_cl.numel() // Cc // groups, Cc, groups, stream_of(x_cl)), "mvs_bn_stats")
+    lib().mvs_bn_stats(ptr(x_cl), ptr(sums), x_cl.numel() // Cc // groups, Cc, groups, stream_of(x_cl))
     return sums if groups > 1 else sums[0]
 
 
@@ -984,8 +974,8 @@ def bn_finalize(sums: torch.Tensor, count: float, eps: float, running_mean=None,
     groups = sums.shape[0] if sums.dim() == 2 else 1
     Cc = sums.shape[-1] // 2
     buf = torch.empty(3, groups, Cc, dtype=torch.float32, device=sums.device)
-    check(lib().mvs_bn_finalize(ptr(sums), float(count), float(eps), ptr(buf[0]), ptr(buf[1]), ptr(buf[2]), ptr(running_mean), ptr(running_var),
-                                float(momentum), Cc, groups, stream_of(sums)), "mvs_bn_finalize")
+    lib().mvs_bn_finalize(ptr(sums), float(count), float(eps), ptr(buf[0]), ptr(buf[1]), ptr(buf[2]), ptr(running_mean), ptr(running_var),
+                          float(momentum), Cc, groups, stream_of(sums))
     if sums.dim() == 2:
         return buf[0], buf[1], buf[2]
     return buf[0, 0], buf[1, 0], buf[2, 0]
@@ -993,8 +983,8 @@ def bn_finalize(sums: torch.Tensor, count: float, eps: float, running_mean=None,
 
 def bn_running_update(mean, var, count: float, momentum: float, running_mean, running_var) -> None:
     groups = mean.shape[0] if mean.dim() == 2 else 1
-    check(lib().mvs_bn_running_update(ptr(mean), ptr(var), float(count), float(momentum), ptr(running_mean), ptr(running_var), mean.shape[-1],
-                                      groups, stream_of(mean)), "mvs_bn_running_update")
+    lib().mvs_bn_running_update(ptr(mean), ptr(var), float(count), float(momentum), ptr(running_mean), ptr(running_var), mean.shape[-1],
+                                groups, stream_of(mean))
 
 
 def _bn_groups(mean):
@@ -1005,8 +995,8 @@ def bn_relu_apply(z_cl, mean, invstd, gamma, beta, skip_cl=None, relu=True) -> t
     """mean / invstd [C], or [groups, C] for `groups` equal slices of z_cl along its leading axis."""
     Cc, groups = z_cl.shape[-1], _bn_groups(mean)
     y = torch.empty_like(z_cl)
-    check(lib().mvs_bn_relu_apply(ptr(z_cl), ptr(mean), ptr(invstd), ptr(gamma), ptr(beta), ptr(skip_cl), ptr(y), z_cl.numel() // Cc // groups, Cc,
-                                  1 if relu else 0, groups, stream_of(z_cl)), "mvs_bn_relu_apply")
+    lib().mvs_bn_relu_apply(ptr(z_cl), ptr(mean), ptr(invstd), ptr(gamma), ptr(beta), ptr(skip_cl), ptr(y), z_cl.numel() // Cc // groups, Cc,
+                            1 if relu else 0, groups, stream_of(z_cl))
     return y
 
 
@@ -1014,17 +1004,16 @@ def bn_relu_bwd_reduce(dy_cl, z_cl, mean, invstd, gamma, beta, relu=True) -> tor
     """-> float64 [2C] (or [groups, 2C]): [sum g | sum g * xhat] with g = dy through the ReLU mask (= [d beta | d gamma] of these voxels)."""
     Cc, groups = z_cl.shape[-1], _bn_groups(mean)
     sums = torch.empty(groups, 2 * Cc, dtype=torch.float64, device=z_cl.device)
-    check(lib().mvs_bn_relu_bwd(ptr(dy_cl), ptr(z_cl), ptr(mean), ptr(invstd), ptr(gamma), ptr(beta), ptr(sums), 1.0, None,
-                                z_cl.numel() // Cc // groups, Cc, 1 if relu else 0, 1, 0, groups, stream_of(z_cl)), "mvs_bn_relu_bwd")
+    lib().mvs_bn_relu_bwd(ptr(dy_cl), ptr(z_cl), ptr(mean), ptr(invstd), ptr(gamma), ptr(beta), ptr(sums), 1.0, None,
+                          z_cl.numel() // Cc // groups, Cc, 1 if relu else 0, 1, 0, groups, stream_of(z_cl))
     return sums if mean.dim() == 2 else sums[0]
 
 
 def bn_relu_bwd_apply(dy_cl, z_cl, mean, invstd, gamma, beta, sums, count: float, relu=True, use_batch_stats=True) -> torch.Tensor:
     Cc, groups = z_cl.shape[-1], _bn_groups(mean)
     dz = torch.empty_like(z_cl)
-    check(lib().mvs_bn_relu_bwd(ptr(dy_cl), ptr(z_cl), ptr(mean), ptr(invstd), ptr(gamma), ptr(beta), ptr(sums), float(count), ptr(dz),
-                                z_cl.numel() // Cc // groups, Cc, 1 if relu else 0, 1 if use_batch_stats else 0, 1, groups, stream_of(z_cl)),
-          "mvs_bn_relu_bwd")
+    lib().mvs_bn_relu_bwd(ptr(dy_cl), ptr(z_cl), ptr(mean), ptr(invstd), ptr(gamma), ptr(beta), ptr(sums), float(count), ptr(dz),
+                          z_cl.numel() // Cc // groups, Cc, 1 if relu else 0, 1 if use_batch_stats else 0, 1, groups, stream_of(z_cl))
     return dz
 
 
@@ -1053,10 +1042,9 @@ def train_block_fwd(ws: TrainWorkspace, a_in, w, transposed: bool, kd: int, stri
     z = torch.empty(B, od, oh, ow, cout, dtype=torch.float32, device=a_in.device)
     y = torch.empty_like(z)
     stats = torch.empty(3, groups, cout, dtype=torch.float32, device=a_in.device)
-    check(lib().mvs_train_block_fwd(ptr(a_in), ptr(w), 1 if transposed else 0, cin, cout, kd, stride[0], stride[1], stride[2], B, D, H, W,
-                                    ptr(gamma), ptr(beta), float(eps), ptr(running_mean), ptr(running_var), float(momentum), ptr(skip),
-                                    ptr(ws.zero_bias), ptr(ws.wpack), ptr(ws.sums), ptr(z), ptr(stats[0]), ptr(stats[1]), ptr(stats[2]), ptr(y),
-                                    groups, stream_of(a_in)), "mvs_train_block_fwd")
+    lib().mvs_train_block_fwd(ptr(a_in), ptr(w), 1 if transposed else 0, cin, cout, kd, stride[0], stride[1], stride[2], B, D, H, W, ptr(gamma),
+                              ptr(beta), float(eps), ptr(running_mean), ptr(running_var), float(momentum), ptr(skip), ptr(ws.zero_bias),
+                              ptr(ws.wpack), ptr(ws.sums), ptr(z), ptr(stats[0]), ptr(stats[1]), ptr(stats[2]), ptr(y), groups, stream_of(a_in))
     return z, stats, y
 
 
@@ -1069,10 +1057,10 @@ def train_block_bwd(ws: TrainWorkspace, dy, a_in, z, stats, w, transposed: bool,
     dw = torch.empty(w.shape[0], w.shape[1], kd, 3, 3, dtype=torch.float32, device=z.device)
     dgb = torch.empty(2, cout, dtype=torch.float32, device=z.device)
     da = torch.empty_like(a_in) if need_da else None
-    check(lib().mvs_train_block_bwd(ptr(dy), ptr(a_in), ptr(z), ptr(stats[0]), ptr(stats[1]), ptr(stats[2]), ptr(w), 1 if transposed else 0, cin, cout, kd,
-                                    stride[0], stride[1], stride[2], B, D, H, W, ptr(gamma), ptr(beta), ptr(running_mean), ptr(running_var),
-                                    float(momentum), ptr(ws.zero_bias), ptr(ws.wpack), ptr(ws.sums), ptr(dz), ptr(dw), ptr(dgb[0]), ptr(dgb[1]), ptr(da),
-                                    groups, stream_of(z)), "mvs_train_block_bwd")
+    lib().mvs_train_block_bwd(ptr(dy), ptr(a_in), ptr(z), ptr(stats[0]), ptr(stats[1]), ptr(stats[2]), ptr(w), 1 if transposed else 0, cin, cout, kd,
+                              stride[0], stride[1], stride[2], B, D, H, W, ptr(gamma), ptr(beta), ptr(running_mean), ptr(running_var),
+                              float(momentum), ptr(ws.zero_bias), ptr(ws.wpack), ptr(ws.sums), ptr(dz), ptr(dw), ptr(dgb[0]), ptr(dgb[1]), ptr(da),
+                              groups, stream_of(z))
     return dw, dgb[0], dgb[1], da
 
 
@@ -1086,7 +1074,7 @@ def pack_conv_weights_device(w: torch.Tensor, ch: int, tflip: bool = False) -> t
     if n < 0:
         raise _lib.MvsHipError("pack_conv_weights_device: unsupported shape %s / chunk %d" % (tuple(w.shape), ch))
     out = torch.empty(n, dtype=torch.bfloat16, device=w.device)
-    check(lib().mvs_pack_conv_weights(ptr(w), ptr(out), cout, cin, ntap, ch, 1 if tflip else 0, stream_of(w)), "mvs_pack_conv_weights")
+    lib().mvs_pack_conv_weights(ptr(w), ptr(out), cout, cin, ntap, ch, 1 if tflip else 0, stream_of(w))
     return out
 
 
@@ -1098,7 +1086,7 @@ def pack_deconv_weights_device(w: torch.Tensor, sd: int) -> torch.Tensor:
     if n < 0:
         raise _lib.MvsHipError("pack_deconv_weights_device: unsupported shape %s" % (tuple(w.shape),))
     out = torch.empty(n, dtype=torch.bfloat16, device=w.device)
-    check(lib().mvs_pack_deconv_weights(ptr(w), ptr(out), cin, cout, sd, stream_of(w)), "mvs_pack_deconv_weights")
+    lib().mvs_pack_deconv_weights(ptr(w), ptr(out), cin, cout, sd, stream_of(w))
     return out
 
 
@@ -1110,7 +1098,7 @@ def conv3d_wgrad(a_cl: torch.Tensor, g_cl: torch.Tensor, stride: Tuple[int, int,
     sd, sh, sw = stride
     assert tuple(g_cl.shape[:4]) == (B, (D - 1) // sd + 1, (H - 1) // sh + 1, (W - 1) // sw + 1), "wgrad: gradient shape does not match the stride"
     dw = torch.empty(CB, CA, kd, 3, 3, dtype=torch.float32, device=a_cl.device)
-    check(lib().mvs_conv3d_wgrad(ptr(a_cl), ptr(g_cl), ptr(dw), B, CA, CB, D, H, W, kd, sd, sh, sw, stream_of(a_cl)), "mvs_conv3d_wgrad")
+    lib().mvs_conv3d_wgrad(ptr(a_cl), ptr(g_cl), ptr(dw), B, CA, CB, D, H, W, kd, sd, sh, sw, stream_of(a_cl))
     return dw
 
 
@@ -1120,8 +1108,7 @@ def conv3d_logits(x_cl: torch.Tensor, w_packed: torch.Tensor, bias: torch.Tensor
     assert c == 8
     _act_dtype(x_cl, precision)
     logits = torch.empty(B, D, H, W, dtype=torch.float32, device=x_cl.device)
-    check(lib().mvs_conv3d_logits_fwd(ptr(x_cl), ptr(w_packed), ptr(bias), ptr(logits), B, D, H, W, precision, stream_of(x_cl)),
-          "mvs_conv3d_logits_fwd")
+    lib().mvs_conv3d_logits_fwd(ptr(x_cl), ptr(w_packed), ptr(bias), ptr(logits), B, D, H, W, precision, stream_of(x_cl))
     return logits
 
 
@@ -1137,10 +1124,10 @@ def regnet(kind: int, volume_cl: torch.Tensor, w_packed: Sequence[torch.Tensor],
     _act_dtype(volume_cl, precision)
     out = torch.empty_like(volume_cl)
     nbytes = lib().mvs_regnet_workspace_bytes(kind, B, D, H, W)
-    ws = torch.empty(max(nbytes // 4, 1), dtype=torch.float32, device=volume_cl.device)
+    ws = _workspace(nbytes, volume_cl.device)
     wa, ba = _ptr_array(w_packed), _ptr_array(bias)
-    check(lib().mvs_regnet_fwd(kind, ptr(volume_cl), C.cast(wa, C.c_void_p), C.cast(ba, C.c_void_p), ptr(out), ptr(ws), nbytes,
-                               B, D, H, W, precision, stream_of(volume_cl)), "mvs_regnet_fwd")
+    lib().mvs_regnet_fwd(kind, ptr(volume_cl), C.cast(wa, C.c_void_p), C.cast(ba, C.c_void_p), ptr(out), ptr(ws), nbytes,
+                         B, D, H, W, precision, stream_of(volume_cl))
     return out
 
 
@@ -1152,10 +1139,10 @@ def regnet_logits(kind: int, volume_cl: torch.Tensor, w_packed: Sequence[torch.T
     _act_dtype(volume_cl, precision)
     logits = torch.empty(B, D, H, W, dtype=torch.float32, device=volume_cl.device)
     nbytes = lib().mvs_regnet_workspace_bytes(kind, B, D, H, W)
-    ws = torch.empty(max(nbytes // 4, 1), dtype=torch.float32, device=volume_cl.device)
+    ws = _workspace(nbytes, volume_cl.device)
     wa, ba = _ptr_array(w_packed), _ptr_array(bias)
-    check(lib().mvs_regnet_logits_fwd(kind, ptr(volume_cl), C.cast(wa, C.c_void_p), C.cast(ba, C.c_void_p), ptr(prob_w), ptr(prob_b),
-                                      ptr(logits), ptr(ws), nbytes, B, D, H, W, precision, stream_of(volume_cl)), "mvs_regnet_logits_fwd")
+    lib().mvs_regnet_logits_fwd(kind, ptr(volume_cl), C.cast(wa, C.c_void_p), C.cast(ba, C.c_void_p), ptr(prob_w), ptr(prob_b),
+                                ptr(logits), ptr(ws), nbytes, B, D, H, W, precision, stream_of(volume_cl))
     return logits
 
 
@@ -1169,9 +1156,8 @@ def prob_regress(feat_cl: torch.Tensor, prob_w: torch.Tensor, prob_b: Optional[t
     need_pre = want_volumes or D not in (4, 8, 16, 32, 48)
     pv = torch.empty(B, D, H, W, dtype=torch.float32, device=dev) if want_volumes else None
     pre = torch.empty(B, D, H, W, dtype=torch.float32, device=dev) if need_pre else None
-    check(lib().mvs_prob_regress_fwd(ptr(feat_cl), ptr(prob_w), ptr(prob_b), ksize, ptr(hyp), float(tmp), mode, conf_n,
-                                     ptr(depth), ptr(conf), ptr(pv), ptr(pre), B, D, H, W, stream_of(feat_cl)),
-          "mvs_prob_regress_fwd")
+    lib().mvs_prob_regress_fwd(ptr(feat_cl), ptr(prob_w), ptr(prob_b), ksize, ptr(hyp), float(tmp), mode, conf_n,
+                               ptr(depth), ptr(conf), ptr(pv), ptr(pre), B, D, H, W, stream_of(feat_cl))
     return depth, conf, pv, pre
 
 
@@ -1186,8 +1172,7 @@ def softmax_regress(logits: torch.Tensor, hyp: torch.Tensor, tmp: float, mode: i
     conf = torch.empty(B, H, W, dtype=torch.float32, device=lg.device)
     pv = torch.empty_like(lg) if want_prob else None
     if conf_prev is None:
-        check(lib().mvs_softmax_regress_fwd(ptr(lg), ptr(hp), float(tmp), mode, conf_n, ptr(depth), ptr(conf), ptr(pv), B, D, H, W,
-                                            stream_of(lg)), "mvs_softmax_regress_fwd")
+        lib().mvs_softmax_regress_fwd(ptr(lg), ptr(hp), float(tmp), mode, conf_n, ptr(depth), ptr(conf), ptr(pv), B, D, H, W, stream_of(lg))
         return depth, conf, pv
     prev = [_f32c(c) for c in conf_prev]
     shifts = []
@@ -1198,9 +1183,9 @@ def softmax_regress(logits: torch.Tensor, hyp: torch.Tensor, tmp: float, mode: i
     avg = torch.empty(B, H, W, dtype=torch.float32, device=lg.device)
     pa = _ptr_array(prev) if prev else None
     sa = (C.c_int * max(len(shifts), 1))(*shifts)
-    check(lib().mvs_softmax_regress_confavg_fwd(ptr(lg), ptr(hp), float(tmp), mode, conf_n, ptr(depth), ptr(conf), ptr(pv),
-                                                C.cast(pa, C.c_void_p) if prev else None, C.cast(sa, C.c_void_p), len(prev), ptr(avg), B, D, H, W,
-                                                stream_of(lg)), "mvs_softmax_regress_confavg_fwd")
+    lib().mvs_softmax_regress_confavg_fwd(ptr(lg), ptr(hp), float(tmp), mode, conf_n, ptr(depth), ptr(conf), ptr(pv),
+                                          C.cast(pa, C.c_void_p) if prev else None, C.cast(sa, C.c_void_p), len(prev), ptr(avg), B, D, H, W,
+                                          stream_of(lg))
     return depth, conf, pv, avg
 
 
@@ -1213,8 +1198,8 @@ def softmax_regress_schedule(logits: torch.Tensor, hyp: torch.Tensor, tmp: float
     conf = torch.empty(B, H, W, dtype=torch.float32, device=lg.device)
     pv = torch.empty_like(lg) if want_prob else None
     nxt = torch.empty(B, next_D, 2 * H, 2 * W, dtype=torch.float32, device=lg.device)
-    check(lib().mvs_softmax_regress_schedule_fwd(ptr(lg), ptr(hp), float(tmp), mode, conf_n, ptr(depth), ptr(conf), ptr(pv), float(ratio), ptr(nxt), next_D,
-                                                 B, D, H, W, stream_of(lg)), "mvs_softmax_regress_schedule_fwd")
+    lib().mvs_softmax_regress_schedule_fwd(ptr(lg), ptr(hp), float(tmp), mode, conf_n, ptr(depth), ptr(conf), ptr(pv), float(ratio), ptr(nxt), next_D,
+                                           B, D, H, W, stream_of(lg))
     return depth, conf, pv, nxt
 
 
@@ -1228,10 +1213,9 @@ def position3d(K: torch.Tensor, hyp: torch.Tensor, depth_values: torch.Tensor, p
     compute = pe_range is None
     rng = torch.empty(6, dtype=torch.float32, device=hp.device) if compute else pe_range.clone()
     wsb = lib().mvs_position3d_workspace_bytes()
-    ws = torch.empty(wsb // 4, dtype=torch.float32, device=hp.device)
+    ws = _workspace(wsb, hp.device)
     pos = torch.empty(B, 3, D, H, W, dtype=torch.float32, device=hp.device)
-    check(lib().mvs_position3d_fwd(ptr(Kc), ptr(hp), ptr(dv), dv.numel(), ptr(rng), 1 if compute else 0, ptr(ws), wsb, ptr(pos),
-                                   B, D, H, W, stream_of(hp)), "mvs_position3d_fwd")
+    lib().mvs_position3d_fwd(ptr(Kc), ptr(hp), ptr(dv), dv.numel(), ptr(rng), 1 if compute else 0, ptr(ws), wsb, ptr(pos), B, D, H, W, stream_of(hp))
     return pos, rng
 
 
@@ -1240,7 +1224,7 @@ def position3d_raw(K: torch.Tensor, hyp: torch.Tensor) -> torch.Tensor:
     Kc, hp = _f32c(K), _f32c(hyp)
     B, D, H, W = hp.shape
     pos = torch.empty(B, 3, D, H, W, dtype=torch.float32, device=hp.device)
-    check(lib().mvs_position3d_raw_fwd(ptr(Kc), ptr(hp), ptr(pos), B, D, H, W, stream_of(hp)), "mvs_position3d_raw_fwd")
+    lib().mvs_position3d_raw_fwd(ptr(Kc), ptr(hp), ptr(pos), B, D, H, W, stream_of(hp))
     return pos
 
 
@@ -1256,8 +1240,7 @@ def position_encoding3d(position3d: torch.Tensor, Cc: int, rescale: float = 4.0)
     # the frequency table exactly as the reference builds it (fp32 exp of fp32 products, position_encoding.py:169)
     div = torch.exp(torch.arange(0, Cc, 2).float() * (-math.log(10000.0) / Cc)).to(pos.device)
     pe = torch.empty(B, 3 * Cc, D, H, W, dtype=torch.float32, device=pos.device)
-    check(lib().mvs_position_encoding3d_fwd(ptr(pos), ptr(div), ptr(pe), B, Cc, float(rescale), D * H * W, stream_of(pos)),
-          "mvs_position_encoding3d_fwd")
+    lib().mvs_position_encoding3d_fwd(ptr(pos), ptr(div), ptr(pe), B, Cc, float(rescale), D * H * W, stream_of(pos))
     return pe
 
 
@@ -1268,9 +1251,9 @@ def tr_embed(volume_cl: torch.Tensor, pos: Optional[torch.Tensor], pe_w, pe_div,
     n = (D // rd) * (H // rh) * (W // rw)
     tokens = torch.empty(B, n, 64, dtype=torch.float32, device=volume_cl.device)
     div = (C.c_float * 4)(*[float(v) for v in pe_div]) if pos is not None else None
-    check(lib().mvs_tr_embed_fwd(ptr(volume_cl), ptr(_f32c(pos)) if pos is not None else None, ptr(pe_w) if pos is not None else None,
-                                 C.cast(div, C.c_void_p) if div is not None else None, ptr(w_packed), ptr(bias), ptr(ln_w), ptr(ln_b),
-                                 ptr(tokens), B, D, H, W, rd, rh, rw, precision, stream_of(volume_cl)), "mvs_tr_embed_fwd")
+    lib().mvs_tr_embed_fwd(ptr(volume_cl), ptr(_f32c(pos)) if pos is not None else None, ptr(pe_w) if pos is not None else None,
+                           C.cast(div, C.c_void_p) if div is not None else None, ptr(w_packed), ptr(bias), ptr(ln_w), ptr(ln_b),
+                           ptr(tokens), B, D, H, W, rd, rh, rw, precision, stream_of(volume_cl))
     return tokens
 
 
@@ -1278,8 +1261,8 @@ def tr_linear(x: torch.Tensor, w_packed, bias, epilogue: int, N: int, precision:
               ln_eps: float = 1e-5):
     B, n, K = x.shape
     y = torch.empty(B, n, N, dtype=torch.float32, device=x.device)
-    check(lib().mvs_tr_linear_fwd(ptr(x), ptr(w_packed), ptr(bias), epilogue, ptr(residual), ptr(gamma), ptr(ln_w), ptr(ln_b),
-                                  float(ln_eps), ptr(y), B, n, K, N, precision, stream_of(x)), "mvs_tr_linear_fwd")
+    lib().mvs_tr_linear_fwd(ptr(x), ptr(w_packed), ptr(bias), epilogue, ptr(residual), ptr(gamma), ptr(ln_w), ptr(ln_b),
+                            float(ln_eps), ptr(y), B, n, K, N, precision, stream_of(x))
     return y
 
 
@@ -1291,11 +1274,10 @@ def tr_attention(x: torch.Tensor, wqkv_packed, heads: int, softmax_scale: float,
     ap = precision if attn_precision is None else attn_precision
     nb = lib().mvs_tr_attention_operand_bytes(B, n, heads)
     buf = torch.empty(3, nb // 2, dtype=torch.bfloat16, device=x.device)
-    check(lib().mvs_tr_qkv_fwd(ptr(x), ptr(wqkv_packed), ptr(buf[0]), ptr(buf[1]), ptr(buf[2]), float(softmax_scale), B, n, heads,
-                               precision, ap, stream_of(x)), "mvs_tr_qkv_fwd")
+    lib().mvs_tr_qkv_fwd(ptr(x), ptr(wqkv_packed), ptr(buf[0]), ptr(buf[1]), ptr(buf[2]), float(softmax_scale), B, n, heads,
+                         precision, ap, stream_of(x))
     out = torch.empty(B, n, Cc, dtype=torch.float32, device=x.device)
-    check(lib().mvs_tr_attention_fwd(ptr(buf[0]), ptr(buf[1]), ptr(buf[2]), ptr(out), B, n, heads, ap, stream_of(x)),
-          "mvs_tr_attention_fwd")
+    lib().mvs_tr_attention_fwd(ptr(buf[0]), ptr(buf[1]), ptr(buf[2]), ptr(out), B, n, heads, ap, stream_of(x))
     return out
 
 
@@ -1305,8 +1287,7 @@ def tr_attention_bwd(qkv: torch.Tensor, o: torch.Tensor, d_o: torch.Tensor, head
     qkv, o, d_o = _f32c(qkv), _f32c(o), _f32c(d_o)
     d_qkv = torch.empty_like(qkv)
     ws = torch.empty(2, B * heads * n, dtype=torch.float32, device=qkv.device)
-    check(lib().mvs_tr_attention_bwd(ptr(qkv), ptr(o), ptr(d_o), ptr(d_qkv), ptr(ws[0]), ptr(ws[1]), B, n, heads, float(softmax_scale),
-                                     stream_of(qkv)), "mvs_tr_attention_bwd")
+    lib().mvs_tr_attention_bwd(ptr(qkv), ptr(o), ptr(d_o), ptr(d_qkv), ptr(ws[0]), ptr(ws[1]), B, n, heads, float(softmax_scale), stream_of(qkv))
     return d_qkv
 
 
@@ -1314,8 +1295,8 @@ def tr_up_prob(tokens: torch.Tensor, w_packed, up_bias, ln_w, ln_b, prob_w, prob
     B = tokens.shape[0]
     D, H, W = dhw
     logits = torch.empty(B, D, H, W, dtype=torch.float32, device=tokens.device)
-    check(lib().mvs_tr_up_prob_fwd(ptr(tokens), ptr(w_packed), ptr(up_bias), ptr(ln_w), ptr(ln_b), ptr(prob_w), ptr(prob_b), ptr(logits),
-                                   B, D, H, W, rate[0], rate[1], rate[2], precision, stream_of(tokens)), "mvs_tr_up_prob_fwd")
+    lib().mvs_tr_up_prob_fwd(ptr(tokens), ptr(w_packed), ptr(up_bias), ptr(ln_w), ptr(ln_b), ptr(prob_w), ptr(prob_b), ptr(logits),
+                             B, D, H, W, rate[0], rate[1], rate[2], precision, stream_of(tokens))
     return logits
 
 
@@ -1325,7 +1306,7 @@ def fusion_pack_cams(cams: torch.Tensor) -> torch.Tensor:
     c = _f32c(cams).reshape(-1, 2, 4, 4)
     nf = lib().mvs_fusion_campack_floats()
     out = torch.empty(c.shape[0], nf, dtype=torch.float32, device=c.device)
-    check(lib().mvs_fusion_prepare_cams(ptr(c), c.shape[0], ptr(out), stream_of(c)), "mvs_fusion_prepare_cams")
+    lib().mvs_fusion_prepare_cams(ptr(c), c.shape[0], ptr(out), stream_of(c))
     return out
 
 
@@ -1356,10 +1337,10 @@ def fusion_filter(dynamic: bool, ref_depth, srcs_depth, ref_cam, srcs_cam, *, re
         if want_points and rc is not None:
             out["points"] = torch.empty(n, 3, h, w, dtype=torch.float32, device=dev)
     g = out.get
-    check(lib().mvs_fusion_filter_fwd(1 if dynamic else 0, ptr(ref_depth), ptr(ref_conf), ptr(srcs_depth), ptr(srcs_conf), ptr(rc), ptr(sc),
-                                      ptr(xyd_in), ptr(in_range_in), float(conf_thresh), float(p0), float(p1), float(vthresh),
-                                      ptr(g("reproj_xyd")), ptr(g("in_range")), ptr(g("vis_masks")), ptr(g("depth")), ptr(g("geo_mask")),
-                                      ptr(g("mask")), ptr(g("points")), n, v, h, w, stream_of(ref_depth)), "mvs_fusion_filter_fwd")
+    lib().mvs_fusion_filter_fwd(1 if dynamic else 0, ptr(ref_depth), ptr(ref_conf), ptr(srcs_depth), ptr(srcs_conf), ptr(rc), ptr(sc),
+                                ptr(xyd_in), ptr(in_range_in), float(conf_thresh), float(p0), float(p1), float(vthresh),
+                                ptr(g("reproj_xyd")), ptr(g("in_range")), ptr(g("vis_masks")), ptr(g("depth")), ptr(g("geo_mask")),
+                                ptr(g("mask")), ptr(g("points")), n, v, h, w, stream_of(ref_depth))
     return out
 
 
@@ -1367,7 +1348,7 @@ def fusion_ave(ref_depth, reproj_xyd, masks):
     n, h, w = ref_depth.shape
     x = _f32c(reproj_xyd)
     out = torch.empty(n, h, w, dtype=torch.float32, device=ref_depth.device)
-    check(lib().mvs_fusion_ave_fwd(ptr(ref_depth), ptr(x), ptr(masks), ptr(out), n, x.shape[1], h, w, stream_of(ref_depth)), "mvs_fusion_ave_fwd")
+    lib().mvs_fusion_ave_fwd(ptr(ref_depth), ptr(x), ptr(masks), ptr(out), n, x.shape[1], h, w, stream_of(ref_depth))
     return out
 
 
@@ -1385,9 +1366,9 @@ def pointcloud_append(mask, points, rgb, records, counter, view_counts=None, vie
     pts, col = _f32c(points).reshape(3, h, w), rgb.reshape(h, w, 3).contiguous()
     assert m.dtype == torch.uint8 and col.dtype == torch.uint8 and records.dtype == torch.uint8 and counter.dtype == torch.int32
     nbytes = lib().mvs_pointcloud_workspace_bytes(h, w)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=m.device)
-    check(lib().mvs_pointcloud_append(ptr(m), ptr(pts), ptr(col), h, w, ptr(ws), nbytes, ptr(counter), ptr(view_counts), int(view_slot),
-                                      ptr(records), records.numel() // PLY_RECORD_BYTES, stream_of(m)), "mvs_pointcloud_append")
+    ws = _workspace(nbytes, m.device)
+    lib().mvs_pointcloud_append(ptr(m), ptr(pts), ptr(col), h, w, ptr(ws), nbytes, ptr(counter), ptr(view_counts), int(view_slot),
+                                ptr(records), records.numel() // PLY_RECORD_BYTES, stream_of(m))
 
 
 # ---- gipuma route (misc/gipuma.py) -------------------------------------------
@@ -1400,7 +1381,7 @@ def gipuma_prepare_cams(cams) -> Tuple[torch.Tensor, torch.Tensor]:
     vf, pf = lib().mvs_gipuma_view_floats(), lib().mvs_gipuma_pair_floats()
     views = np.zeros((n, vf), np.float32)
     pairs = np.zeros((n, n, pf), np.float32)
-    check(lib().mvs_gipuma_prepare_cams(c.ctypes.data, n, views.ctypes.data, pairs.ctypes.data), "mvs_gipuma_prepare_cams")
+    lib().mvs_gipuma_prepare_cams(c.ctypes.data, n, views.ctypes.data, pairs.ctypes.data)
     return torch.from_numpy(views), torch.from_numpy(pairs)
 
 
@@ -1415,8 +1396,7 @@ def gipuma_prepare_view(depth, keep, rgb, depth_out, color_out) -> None:
     col = rgb.reshape(h, w, 3).contiguous()
     assert col.dtype == torch.uint8 and depth_out.dtype == torch.float32 and color_out.dtype == torch.int32
     assert depth_out.is_contiguous() and color_out.is_contiguous() and depth_out.numel() == h * w == color_out.numel()
-    check(lib().mvs_gipuma_prepare_view(ptr(d), ptr(k), ptr(col), h, w, ptr(depth_out), ptr(color_out), stream_of(d)),
-          "mvs_gipuma_prepare_view")
+    lib().mvs_gipuma_prepare_view(ptr(d), ptr(k), ptr(col), h, w, ptr(depth_out), ptr(color_out), stream_of(d))
 
 
 def gipuma_fuse_view(depths, colors, used, view_consts, pair_consts, r: int, *, depth_min: float, depth_max: float, disp_thresh: float,
@@ -1432,9 +1412,9 @@ def gipuma_fuse_view(depths, colors, used, view_consts, pair_consts, r: int, *, 
     assert view_consts.shape[0] == n and pair_consts.shape[:2] == (n, n)
     if skipped is not None:
         assert skipped.dtype == torch.uint8 and skipped.is_contiguous() and skipped.numel() == h * w
-    check(lib().mvs_gipuma_fuse_view(ptr(depths), ptr(colors), ptr(used), ptr(view_consts), ptr(pair_consts), n, h, w, int(r),
-                                     float(depth_min), float(depth_max), float(disp_thresh), float(num_consistent), ptr(mask), ptr(points),
-                                     ptr(rgb), ptr(skipped), stream_of(depths)), "mvs_gipuma_fuse_view")
+    lib().mvs_gipuma_fuse_view(ptr(depths), ptr(colors), ptr(used), ptr(view_consts), ptr(pair_consts), n, h, w, int(r),
+                               float(depth_min), float(depth_max), float(disp_thresh), float(num_consistent), ptr(mask), ptr(points),
+                               ptr(rgb), ptr(skipped), stream_of(depths))
 
 
 # ---- colmap2mvsnet (colmap2mvsnet.py) ----------------------------------------
@@ -1456,7 +1436,7 @@ def colmap_depths(obs_img, obs_pt, xyz, erow) -> torch.Tensor:
     each image's extrinsic).  Stream-ordered."""
     oi, op, x, e = _i32c(obs_img), _i32c(obs_pt), _f64c(xyz), _f64c(erow)
     z = torch.empty(oi.numel(), dtype=torch.float64, device=oi.device)
-    check(lib().mvs_colmap_depths(ptr(oi), ptr(op), oi.numel(), ptr(x), ptr(e), ptr(z), stream_of(oi)), "mvs_colmap_depths")
+    lib().mvs_colmap_depths(ptr(oi), ptr(op), oi.numel(), ptr(x), ptr(e), ptr(z), stream_of(oi))
     return z
 
 
@@ -1472,13 +1452,12 @@ def colmap_scores(img_ptr, img_pts, img_mult, pt_ptr, pt_imgs, xyz, centres, *, 
     nbytes = lib().mvs_colmap_workspace_bytes(n)
     if nbytes == 0:
         raise ValueError("colmap_scores: %d images (1..%d)" % (n, COLMAP_MAX_IMAGES))
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ws = _workspace(nbytes, dev)
     flags = torch.empty(n * n, dtype=torch.uint8, device=dev)
     pairs = torch.empty(max(int(max_pairs), 1), dtype=torch.int32, device=dev)
     score = torch.empty(n, n, dtype=torch.float64, device=dev)
-    check(lib().mvs_colmap_scores(ptr(ip), ptr(ipt), ptr(im), n, ptr(pp), ptr(pim), p, ptr(x), ptr(c), float(theta0), float(den1),
-                                  float(den2), int(max_pairs), ptr(flags), ptr(pairs), ptr(ws), nbytes, ptr(score), stream_of(ip)),
-          "mvs_colmap_scores")
+    lib().mvs_colmap_scores(ptr(ip), ptr(ipt), ptr(im), n, ptr(pp), ptr(pim), p, ptr(x), ptr(c), float(theta0), float(den1),
+                            float(den2), int(max_pairs), ptr(flags), ptr(pairs), ptr(ws), nbytes, ptr(score), stream_of(ip))
     return score
 
 
@@ -1487,7 +1466,7 @@ def depth_regression(p: torch.Tensor, depth_values: torch.Tensor) -> torch.Tenso
     pp, dv = _f32c(p), _f32c(depth_values)
     B, D, H, W = pp.shape
     out = torch.empty(B, H, W, dtype=torch.float32, device=pp.device)
-    check(lib().mvs_depth_regression_fwd(ptr(pp), ptr(dv), ptr(out), B, D, H, W, stream_of(pp)), "mvs_depth_regression_fwd")
+    lib().mvs_depth_regression_fwd(ptr(pp), ptr(dv), ptr(out), B, D, H, W, stream_of(pp))
     return out
 
 
@@ -1495,7 +1474,7 @@ def conf_regression(p: torch.Tensor, n: int) -> torch.Tensor:
     pp = _f32c(p)
     B, D, H, W = pp.shape
     out = torch.empty(B, H, W, dtype=torch.float32, device=pp.device)
-    check(lib().mvs_conf_regression_fwd(ptr(pp), int(n), ptr(out), B, D, H, W, stream_of(pp)), "mvs_conf_regression_fwd")
+    lib().mvs_conf_regression_fwd(ptr(pp), int(n), ptr(out), B, D, H, W, stream_of(pp))
     return out
 
 
@@ -1507,11 +1486,11 @@ def init_range(depth_values: torch.Tensor, ndepths: int, H: int, W: int, inverse
         if (h, w) != (H, W):
             raise _lib.MvsHipError("per-pixel initial ranges %s do not match the %dx%d hypothesis maps" % (tuple(dv.shape), H, W))
         hyp = torch.empty(B, ndepths, H, W, dtype=torch.float32, device=dv.device)
-        check(lib().mvs_init_range_pixel_fwd(ptr(dv), N, 1 if inverse else 0, ptr(hyp), B, ndepths, H, W, stream_of(dv)), "mvs_init_range_pixel_fwd")
+        lib().mvs_init_range_pixel_fwd(ptr(dv), N, 1 if inverse else 0, ptr(hyp), B, ndepths, H, W, stream_of(dv))
         return hyp
     B, N = dv.shape
     hyp = torch.empty(B, ndepths, H, W, dtype=torch.float32, device=dv.device)
-    check(lib().mvs_init_range_fwd(ptr(dv), N, 1 if inverse else 0, ptr(hyp), B, ndepths, H, W, stream_of(dv)), "mvs_init_range_fwd")
+    lib().mvs_init_range_fwd(ptr(dv), N, 1 if inverse else 0, ptr(hyp), B, ndepths, H, W, stream_of(dv))
     return hyp
 
 
@@ -1521,8 +1500,7 @@ def schedule_inverse_range(prev_depth: torch.Tensor, prev_hyp: torch.Tensor, nde
     B, Dp = h.shape[:2]
     assert tuple(d.shape[-2:]) == (H // 2, W // 2) and tuple(h.shape[-2:]) == (H // 2, W // 2)
     hyp = torch.empty(B, ndepths, H, W, dtype=torch.float32, device=d.device)
-    check(lib().mvs_schedule_inverse_range_fwd(ptr(d), ptr(h), Dp, float(ratio), 1 if shift else 0, ptr(hyp), B, ndepths, H, W, stream_of(d)),
-          "mvs_schedule_inverse_range_fwd")
+    lib().mvs_schedule_inverse_range_fwd(ptr(d), ptr(h), Dp, float(ratio), 1 if shift else 0, ptr(hyp), B, ndepths, H, W, stream_of(d))
     return hyp
 
 
@@ -1537,7 +1515,7 @@ def schedule_range(prev_depth: torch.Tensor, ndepths: int, interval: torch.Tenso
     else:
         itv = _f32c(interval.reshape(-1).expand(B) if interval.numel() == 1 else interval.reshape(B))
     hyp = torch.empty(B, ndepths, H, W, dtype=torch.float32, device=d.device)
-    check(lib().mvs_schedule_range_fwd(ptr(d), ptr(itv), 1 if per_pixel else 0, ptr(hyp), B, ndepths, H, W, stream_of(d)), "mvs_schedule_range_fwd")
+    lib().mvs_schedule_range_fwd(ptr(d), ptr(itv), 1 if per_pixel else 0, ptr(hyp), B, ndepths, H, W, stream_of(d))
     return hyp
 
 
@@ -1552,8 +1530,7 @@ def confidence_average(confs: Sequence[torch.Tensor], H: int, W: int) -> torch.T
     out = torch.empty(B, H, W, dtype=torch.float32, device=confs[0].device)
     pa = _ptr_array(confs)
     sa = (C.c_int * len(shifts))(*shifts)
-    check(lib().mvs_confidence_average(C.cast(pa, C.c_void_p), C.cast(sa, C.c_void_p), len(confs), ptr(out), B, H, W,
-                                       stream_of(out)), "mvs_confidence_average")
+    lib().mvs_confidence_average(C.cast(pa, C.c_void_p), C.cast(sa, C.c_void_p), len(confs), ptr(out), B, H, W, stream_of(out))
     return out
 
 
@@ -1561,14 +1538,14 @@ def ncdhw_to_cl(x: torch.Tensor) -> torch.Tensor:
     x = _f32c(x)
     B, Cc, D, H, W = x.shape
     y = torch.empty(B, D, H, W, Cc, dtype=torch.float32, device=x.device)
-    check(lib().mvs_ncdhw_to_cl(ptr(x), ptr(y), B, Cc, D, H, W, stream_of(x)), "mvs_ncdhw_to_cl")
+    lib().mvs_ncdhw_to_cl(ptr(x), ptr(y), B, Cc, D, H, W, stream_of(x))
     return y
 
 
 def cl_to_ncdhw(x_cl: torch.Tensor) -> torch.Tensor:
     B, D, H, W, Cc = x_cl.shape
     y = torch.empty(B, Cc, D, H, W, dtype=torch.float32, device=x_cl.device)
-    check(lib().mvs_cl_to_ncdhw(ptr(x_cl), ptr(y), B, Cc, D, H, W, stream_of(x_cl)), "mvs_cl_to_ncdhw")
+    lib().mvs_cl_to_ncdhw(ptr(x_cl), ptr(y), B, Cc, D, H, W, stream_of(x_cl))
     return y
 
 
@@ -1588,8 +1565,8 @@ def resize_bicubic(img: torch.Tensor, h: int, w: int) -> torch.Tensor:
         raise ValueError("resize_bicubic: the output size must be at least 1 x 1; got %d x %d" % (h, w))
     N, Cc, H, W = img.shape
     out = torch.empty(N, Cc, h, w, dtype=torch.float32, device=img.device)
-    check(lib().mvs_resize_bicubic_fwd(_base_ptr(img), img.stride(0), img.stride(1), img.stride(2), img.stride(3), ptr(out), N, Cc, H, W, h, w,
-                                       stream_of(img)), "mvs_resize_bicubic_fwd")
+    lib().mvs_resize_bicubic_fwd(_base_ptr(img), img.stride(0), img.stride(1), img.stride(2), img.stride(3), ptr(out), N, Cc, H, W, h, w,
+                                 stream_of(img))
     return out
 
 
@@ -1604,8 +1581,8 @@ def resize_bilinear_add(base: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
     base = base.contiguous()
     N, Cc, h, w = base.shape
     out = torch.empty_like(base)
-    check(lib().mvs_resize_bilinear_add_fwd(ptr(base), _base_ptr(x), x.stride(0), x.stride(1), x.stride(2), x.stride(3), ptr(out), N, Cc, h, w,
-                                            x.shape[2], x.shape[3], stream_of(base)), "mvs_resize_bilinear_add_fwd")
+    lib().mvs_resize_bilinear_add_fwd(ptr(base), _base_ptr(x), x.stride(0), x.stride(1), x.stride(2), x.stride(3), ptr(out), N, Cc, h, w,
+                                      x.shape[2], x.shape[3], stream_of(base))
     return out
 
 
@@ -1643,8 +1620,7 @@ def image_prepare(src: torch.Tensor, H: int, W: int, table: torch.Tensor, pad_ro
     for t, dt, shape, what in ((planar, torch.float32, (3, H, W), "planar"), (resized, torch.uint8, (H, W, 3), "resized")):
         if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous() or t.device != src.device:
             raise ValueError("image_prepare: %s must be a contiguous %s tensor %s on the image's device" % (what, dt, list(shape)))
-    check(lib().mvs_image_prepare_fwd(ptr(src), src.shape[0], src.shape[1], pad_rows, ptr(table), ptr(planar), ptr(resized), H, W,
-                                      stream_of(src)), "mvs_image_prepare_fwd")
+    lib().mvs_image_prepare_fwd(ptr(src), src.shape[0], src.shape[1], pad_rows, ptr(table), ptr(planar), ptr(resized), H, W, stream_of(src))
     return planar, resized
 
 
@@ -1662,8 +1638,8 @@ def depth_outputs_pack(depth: torch.Tensor, conf: torch.Tensor, reg_conf: Option
         out = torch.empty(5 * H * W, dtype=torch.uint8, device=depth.device)
     elif out.dtype != torch.uint8 or out.numel() != 5 * H * W or not out.is_contiguous() or out.device != depth.device:
         raise ValueError("depth_outputs_pack: out must be a contiguous uint8 tensor of 5 H W = %d bytes on the maps' device" % (5 * H * W))
-    check(lib().mvs_depth_outputs_pack_fwd(ptr(depth.contiguous()), ptr(conf.contiguous()), ptr(None if reg_conf is None else reg_conf.contiguous()),
-                                           ptr(out), H, W, stream_of(depth)), "mvs_depth_outputs_pack_fwd")
+    lib().mvs_depth_outputs_pack_fwd(ptr(depth.contiguous()), ptr(conf.contiguous()), ptr(None if reg_conf is None else reg_conf.contiguous()),
+                                     ptr(out), H, W, stream_of(depth))
     return out
 
 
@@ -1694,7 +1670,7 @@ def _loss_workspace(pixels: int, like: torch.Tensor):
     nbytes = lib().mvs_loss_workspace_bytes(pixels)
     if nbytes == 0:
         raise ValueError("the losses take 1 <= B H W < 2^31 pixels; got %d" % pixels)
-    return torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=like.device), nbytes     # 8-byte aligned; sized from the launch grid
+    return _workspace(nbytes, like.device), nbytes                                              # sized from the launch grid
 
 
 def ce_loss_fwd(logits: torch.Tensor, hyp: torch.Tensor, gt: torch.Tensor, mask: torch.Tensor, inverse: bool, weight: float = 1.0):
@@ -1712,8 +1688,8 @@ def ce_loss_fwd(logits: torch.Tensor, hyp: torch.Tensor, gt: torch.Tensor, mask:
     lse = torch.empty(B, H, W, dtype=torch.float32, device=x.device)
     loss = torch.empty(1, dtype=torch.float32, device=x.device)
     count = torch.empty(1, dtype=torch.int32, device=x.device)
-    check(lib().mvs_ce_loss_fwd(ptr(x), ptr(h), ptr(g), ptr(m), 1 if inverse else 0, float(weight), ptr(index), ptr(lse), ptr(ws), nbytes,
-                                ptr(loss), ptr(count), B, D, H, W, stream_of(x)), "mvs_ce_loss_fwd")
+    lib().mvs_ce_loss_fwd(ptr(x), ptr(h), ptr(g), ptr(m), 1 if inverse else 0, float(weight), ptr(index), ptr(lse), ptr(ws), nbytes,
+                          ptr(loss), ptr(count), B, D, H, W, stream_of(x))
     return loss, count, index, lse
 
 
@@ -1730,8 +1706,8 @@ def ce_loss_bwd(logits: torch.Tensor, index: torch.Tensor, lse: torch.Tensor, gr
     l = _loss_map(lse, "lse", "ce_loss_bwd", (B, H, W))
     g = _f32c(grad_loss).reshape(1)
     grad = torch.empty_like(x)
-    check(lib().mvs_ce_loss_bwd(ptr(x), ptr(index.contiguous()), ptr(l), ptr(g), ptr(count.contiguous()), float(weight), ptr(grad), B, D, H, W,
-                                stream_of(x)), "mvs_ce_loss_bwd")
+    lib().mvs_ce_loss_bwd(ptr(x), ptr(index.contiguous()), ptr(l), ptr(g), ptr(count.contiguous()), float(weight), ptr(grad), B, D, H, W,
+                          stream_of(x))
     return grad
 
 
@@ -1757,8 +1733,8 @@ def reg_loss_fwd(depth: torch.Tensor, gt: torch.Tensor, mask: torch.Tensor, inte
     ws, nbytes = _loss_workspace(B * H * W, d)
     loss = torch.empty(1, dtype=torch.float32, device=d.device)
     count = torch.empty(1, dtype=torch.int32, device=d.device)
-    check(lib().mvs_reg_loss_fwd(ptr(d), ptr(g), ptr(m), ptr(itv), ptr(h), 1 if inverse else 0, float(weight), ptr(ws), nbytes, ptr(loss),
-                                 ptr(count), B, D, H, W, stream_of(d)), "mvs_reg_loss_fwd")
+    lib().mvs_reg_loss_fwd(ptr(d), ptr(g), ptr(m), ptr(itv), ptr(h), 1 if inverse else 0, float(weight), ptr(ws), nbytes, ptr(loss),
+                           ptr(count), B, D, H, W, stream_of(d))
     return loss, count
 
 
@@ -1771,8 +1747,8 @@ def reg_loss_bwd(depth: torch.Tensor, gt: torch.Tensor, mask: torch.Tensor, inte
         raise ValueError("reg_loss_bwd: count must be an int32 tensor of one element")
     go = _f32c(grad_loss).reshape(1)
     grad = torch.empty_like(d)
-    check(lib().mvs_reg_loss_bwd(ptr(d), ptr(g), ptr(m), ptr(itv), ptr(h), 1 if inverse else 0, ptr(go), ptr(count.contiguous()), float(weight),
-                                 ptr(grad), B, D, H, W, stream_of(d)), "mvs_reg_loss_bwd")
+    lib().mvs_reg_loss_bwd(ptr(d), ptr(g), ptr(m), ptr(itv), ptr(h), 1 if inverse else 0, ptr(go), ptr(count.contiguous()), float(weight),
+                           ptr(grad), B, D, H, W, stream_of(d))
     return grad
 
 
@@ -1806,11 +1782,11 @@ def depth_metrics(depth_est: torch.Tensor, depth_gt: torch.Tensor, mask: torch.T
     nbytes = lib().mvs_depth_metrics_workspace_bytes(B, H, W, T)
     if nbytes == 0:
         raise ValueError("depth_metrics: 1 <= B <= 65535 images and B H W < 2^31 pixels; got %s" % ([B, H, W],))
-    ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=e.device)
+    ws = _workspace(nbytes, e.device)
     counts = torch.empty(B, 1 + 2 * T, dtype=torch.int32, device=e.device)
     sums = torch.empty(B, T, dtype=torch.float64, device=e.device)
     means = torch.empty(B + 1, 2 * T, dtype=torch.float32, device=e.device)
-    check(lib().mvs_depth_metrics(ptr(e), ptr(g), ptr(m), 0 if m.dtype == torch.float32 else 1, ptr(interval), float(divisor),
-                                  1 if per_sample else 0, C.cast(th, C.c_void_p), C.cast(lo, C.c_void_p), C.cast(hi, C.c_void_p), T, ptr(ws),
-                                  nbytes, ptr(counts), ptr(sums), ptr(means), B, H, W, stream_of(e)), "mvs_depth_metrics")
+    lib().mvs_depth_metrics(ptr(e), ptr(g), ptr(m), 0 if m.dtype == torch.float32 else 1, ptr(interval), float(divisor),
+                            1 if per_sample else 0, C.cast(th, C.c_void_p), C.cast(lo, C.c_void_p), C.cast(hi, C.c_void_p), T, ptr(ws),
+                            nbytes, ptr(counts), ptr(sums), ptr(means), B, H, W, stream_of(e))
     return counts, sums, means

@@ -243,9 +243,14 @@ def case_generic_conv_layers(device):
             raise AssertionError("a mismatching weight / skip tensor must be refused")
     xc = dev(torch.randn(1, 4, 4, 4, 3, generator=g), device)
     y = torch.empty(1, 9, 9, 9, 5, device=xc.device)
-    rc = _lib.lib().mvs_conv3d_generic_fwd(_lib.ptr(xc), _lib.ptr(dev(torch.randn(27, 3, 5, generator=g), device)), None, None, _lib.ptr(y), 1, 3, 5, 4, 4, 4,
-                                           9, 9, 9, 3, 3, 3, 2, 2, 2, 1, 1, 1, 1, 0, None)
-    assert rc == 1, "output size 9 of a stride-2 k3 p1 transposed layer on 4 inputs (valid: 7, 8) must be MVS_ERR_ARG"
+    try:                                                               # the bound library raises on a status other than MVS_OK
+        _lib.lib().mvs_conv3d_generic_fwd(_lib.ptr(xc), _lib.ptr(dev(torch.randn(27, 3, 5, generator=g), device)), None, None, _lib.ptr(y), 1, 3, 5, 4, 4, 4,
+                                          9, 9, 9, 3, 3, 3, 2, 2, 2, 1, 1, 1, 1, 0, None)
+        err = ""
+    except _lib.MvsHipError as e:
+        err = str(e)
+    assert err.startswith("mvs_conv3d_generic_fwd failed (code 1)"), \
+        "output size 9 of a stride-2 k3 p1 transposed layer on 4 inputs (valid: 7, 8) must be MVS_ERR_ARG; got '%s'" % err
 
 
 def case_generic_conv_fuzz(device, n_cases=60, seed=0):

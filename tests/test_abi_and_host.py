@@ -1,12 +1,13 @@
 """CPU: the C-ABI library loads and exports every symbol include/mvs_hip.h declares (no compute without a GPU),
 plus host-side logic: weight packing, BN folding, view sharding, state-dict contract, loud failure without a device."""
+import ctypes as C
 import os
 import re
 
 import pytest
 import torch
 
-from mvsformerplusplus_amd import _lib, module as M, ops, packing, synth
+from mvsformerplusplus_amd import _header, _lib, module as M, ops, packing, synth
 from mvsformerplusplus_amd.cost_volume import StageNet, shard_views
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -105,7 +106,112 @@ def test_auto_policy_decisions():
 
 
 def test_header_matches_binding_table():
-    assert header_symbols() == sorted(_lib.SIGNATURES)
+    """The binding table IS the parsed header; this file's own regex must find the same names, so a declaration the parser skips shows."""
+    assert header_symbols() == sorted(_header.PROTOTYPES)
+    assert _header.STATUS < set(_header.PROTOTYPES) and len(_header.STATUS) > 90
+    for name, (res, _) in _header.PROTOTYPES.items():            # predicates, counters and size queries are not status codes
+        if name.endswith(("_is_built", "_is_tuned", "_bytes", "_floats", "_elems")) or name in (
+                "mvs_abi_version", "mvs_last_error", "mvs_f16_saturation_count", "mvs_gather_is_lds_staged", "mvs_gather_keeps_correlations"):
+            assert name not in _header.STATUS, name
+        else:
+            assert name in _header.STATUS and res is C.c_int, name
+
+
+AWKWARD = """
+/* a header in miniature */
+#define MVS_ABI_VERSION 3
+#define MVS_GUARD_H
+enum { MVS_OK = 0, MVS_ERR_ARG = 1 };
+typedef int mvs_status;
+mvs_status mvs_a(const float* const* proj_host_ptrs, uint8_t* proj_mask, void* stream);
+unsigned long long mvs_b(int);
+const char* mvs_c(void);
+size_t mvs_d(void);
+mvs_status mvs_e(const float* proj, int B, int V, float* homography /*[B,V-1,12]*/,
+                 double count, long long N, /*[B,V-1,12]*/ size_t workspace_bytes,
+                 float eps /*[B,V-1,12]*/, void* stream);
+long long mvs_f(int cout, unsigned long long n);
+int mvs_g_is_built(int Cin, int Cout);
+"""
+
+
+def test_header_parser_on_awkward_declarators():
+    vp, i = C.c_void_p, C.c_int
+    protos, status, consts = _header.parse(AWKWARD)
+    assert protos == {"mvs_a": (i, [vp, vp, vp]),
+                      "mvs_b": (C.c_ulonglong, [i]),
+                      "mvs_c": (C.c_char_p, []),
+                      "mvs_d": (C.c_size_t, []),
+                      "mvs_e": (i, [vp, i, i, vp, C.c_double, C.c_longlong, C.c_size_t, C.c_float, vp]),
+                      "mvs_f": (C.c_longlong, [i, C.c_ulonglong]),
+                      "mvs_g_is_built": (i, [i, i])}
+    assert status == {"mvs_a", "mvs_e"}
+    assert consts == {"MVS_ABI_VERSION": 3, "MVS_OK": 0, "MVS_ERR_ARG": 1}
+
+
+@pytest.mark.parametrize("decl", ["short f(int);", "int f(struct cam c);", "int f(long n);", "float* f(void);", "void f(int);",
+                                  "int f(int a) { return a; }", "int f(int); int f(int);"])
+def test_header_parser_refuses_what_it_does_not_know(decl):
+    with pytest.raises(ValueError):
+        _header.parse(decl)
+
+
+def test_status_functions_raise_with_their_own_librarys_message(emu_lib):
+    """A function declared mvs_status raises from the bound library itself (argument validation runs before any launch, so this needs
+    no GPU), with the text check() gave; the message is that of the library the call went through."""
+    L = _lib.lib()
+    with pytest.raises(_lib.MvsHipError) as e:
+        L.mvs_ncdhw_to_cl(None, None, 0, 0, 1, 1, 1, None)
+    assert str(e.value).startswith("mvs_ncdhw_to_cl failed (code 1): ") and "bad arguments" in str(e.value)
+    with pytest.raises(_lib.MvsHipError) as e:                   # leaves ANOTHER message in the product library ...
+        L.mvs_cl_to_ncdhw(None, None, 0, 0, 1, 1, 1, None)
+    assert "mvs_cl_to_ncdhw" in str(e.value)
+    assert emu_lib is not L
+    with pytest.raises(_lib.MvsHipError) as e:                   # ... which a failure in a second bind() handle must not report
+        emu_lib.mvs_ncdhw_to_cl(None, None, 0, 0, 1, 1, 1, None)
+    assert "mvs_ncdhw_to_cl" in str(e.value) and "bad arguments" in str(e.value) and "mvs_cl_to_ncdhw" not in str(e.value)
+    assert L.mvs_conv3d_is_tuned(3, 3, 3, 1, 1, 1) == 0          # a predicate's int is a value, not a status
+    n = L.mvs_fmt_weights_bytes()
+    assert isinstance(n, int) and n > 0
+    with pytest.raises(_lib.MvsHipError, match=r"^x failed \(code 2\): "):     # check() on a code held in hand keeps working
+        _lib.check(2, "x")
+    _lib.check(0, "x")
+
+
+DTYPES = {"DTYPE_F32": torch.float32, "DTYPE_BF16": torch.bfloat16, "DTYPE_F16": torch.float16}
+
+
+def constant_mismatches():
+    """Every enumerator and numeric #define MVS_<X> of the header against the Python literal <X> of _lib / ops and against DTYPE_CODE."""
+    bad, seen = [], set()
+    for name, value in _header.CONSTANTS.items():
+        x = name[len("MVS_"):]
+        found = [getattr(m, x) for m in (_lib, ops) if hasattr(m, x)] + ([_lib.DTYPE_CODE[DTYPES[x]]] if x in DTYPES else [])
+        seen.update([x] if found else [])
+        bad += [(name, value, f) for f in found if f != value or type(f) is not int]
+    return bad, seen
+
+
+def test_python_constants_equal_the_headers(monkeypatch):
+    bad, seen = constant_mismatches()
+    assert not bad, bad
+    assert _lib.ABI_VERSION == _header.CONSTANTS["MVS_ABI_VERSION"] and len(_lib.DTYPE_CODE) == len(DTYPES)
+    for x in ("OK", "ABI_VERSION", "METRICS_MAX_T", "TR_EPI_BIAS", "TR_EPI_GELU", "TR_EPI_RES_LN", "HEAD_CE_EVAL", "HEAD_CE_TRAIN", "HEAD_REG",
+              "LAYOUT_PLANAR", "LAYOUT_OCTET_TILED", "REG_COSTREGNET", "REG_COSTREGNET3D", "PREC_FP32", "PREC_BF16X3", "PREC_BF16P",
+              "PREC_BF16X3_SPLIT", "PREC_F16X2", "PREC_ATTN16", "PREC_F16", "PREC_F16MIX", "VOLUME_F32", "VOLUME_SPLIT", "VOLUME_F16",
+              "CORR_F16", "CORR_F32") + tuple(DTYPES):
+        assert x in seen, "%s is no longer compared with the header" % x
+    monkeypatch.setattr(_lib, "PREC_F16", 5)                     # a changed literal is found
+    monkeypatch.setattr(ops, "METRICS_MAX_T", 16)
+    monkeypatch.setitem(_lib.DTYPE_CODE, torch.bfloat16, 2)
+    assert sorted(b[0] for b in constant_mismatches()[0]) == ["MVS_DTYPE_BF16", "MVS_METRICS_MAX_T", "MVS_PREC_F16"]
+
+
+def test_no_call_site_checks_a_status_by_hand():
+    import glob
+    for f in sorted(glob.glob(os.path.join(ROOT, "mvsformerplusplus_amd", "*.py"))):
+        txt = open(f).read()
+        assert "check(lib()" not in txt and "check(L." not in txt, f
 
 
 def test_library_exports_every_declared_symbol():
