@@ -595,6 +595,30 @@ mvs_status mvs_fpn_merge_wgrad(const float* dy, const float* prev, const float* 
                                void* workspace, size_t workspace_bytes, int N, int H, int W, void* stream);
 mvs_status mvs_fpn_up2_adjoint(const float* d_fine, float* d_coarse, int N, int H, int W, void* stream);
 
+/* ---- FPNEncoder in train mode: eleven blocks leaky_relu(BatchNorm2d(conv(x)), 0.1) with batch statistics, and
+ * their backward.  The forward convolutions, and the data gradients of the stride-1 blocks (Cin = Cout: flipped, channel-transposed taps),
+ * are mvs_fpn_conv_fwd with bias = NULL, act 0.  No atomics: bit-identical run to run.
+ * mvs_fpn_bn_leaky_fwd / _bwd: mvs_fpn_bn_swish_fwd / _bwd's arguments and workspace (mvs_fpn_bn_workspace_bytes; conv_bias may be NULL) with
+ *   y = leaky_relu(u, 0.1), u = gamma xhat + beta, and du = dy (u > 0 ? 1 : 0.1) with u recomputed from z and stats.
+ * mvs_fpn_enc_wgrad: dw [Cout][Cin][k][k] = sum_pixels dy [N,Cout,OH,OW] (x) x [N,Cin,H,W] at stride `stride`, padding k/2, OH = (H - 1) /
+ *   stride + 1; exact fp32 products.  Built: (Cout, Cin, k, stride) = (8,3,7,1), (8,8,5,1), (16,8,5,2), (16,16,3,1), (32,16,5,2), (32,32,3,1),
+ *   (64,32,3,2), (64,64,3,1).  mvs_fpn_enc_wgrad_workspace_bytes: 0 = not built or out of range.
+ * mvs_fpn_enc_dgrad: dx [N,Cin,H,W] (H, W even) = the stride-2 transposed convolution of dz [N,Cout,H/2,W/2] with the layer's weight
+ *   [Cout][Cin][k][k], padding k/2, as four parity classes of 3x3 convolutions; w_packed = packing.pack_fpn_enc_dgrad_weights(w)
+ *   (mvs_fpn_enc_dgrad_weights_bytes bytes).  Built (mvs_fpn_enc_dgrad_is_built, stride 2 only): (Cin, Cout, k) = (8,16,5), (16,32,5),
+ *   (32,64,3).                                                                                                                         */
+mvs_status mvs_fpn_bn_leaky_fwd(const float* z, const float* conv_bias, const float* gamma, const float* beta, float eps, float momentum,
+                                float* running_mean, float* running_var, float* stats, float* y, void* workspace, size_t workspace_bytes, int N, int C,
+                                int H, int W, void* stream);
+mvs_status mvs_fpn_bn_leaky_bwd(const float* dy, const float* z, const float* stats, const float* gamma, const float* beta, float* dz, float* d_gamma,
+                                float* d_beta, void* workspace, size_t workspace_bytes, int N, int C, int H, int W, void* stream);
+size_t mvs_fpn_enc_wgrad_workspace_bytes(int N, int Cin, int Cout, int k, int stride, int H, int W);
+mvs_status mvs_fpn_enc_wgrad(const float* dy, const float* x, float* dw, void* workspace, size_t workspace_bytes, int N, int Cin, int Cout, int k,
+                             int stride, int H, int W, void* stream);
+int mvs_fpn_enc_dgrad_is_built(int Cin, int Cout, int k, int stride);
+size_t mvs_fpn_enc_dgrad_weights_bytes(int Cin, int Cout, int k);
+mvs_status mvs_fpn_enc_dgrad(const float* dz, const void* w_packed, float* dx, int N, int Cin, int Cout, int k, int H, int W, void* stream);
+
 /* ==== FMT_with_pathway: stage-1 linear attention + pathway ============================================
  * models/FMT.py:35-206 with the shipped FMT_config (Linear attention, d_model 64, 4 heads, ffn, pre-norm, LayerScale).  Token
  * tensors are the feature maps themselves: planar fp32 [N, 64, n], n = h w.  Split-bf16 three-term MFMA GEMMs (fp32-equivalent);

@@ -1,5 +1,6 @@
 // The 2-D split-bf16 convolution: ONE implicit-GEMM kernel template for the feature side - the FPN layers (fpn_kernels.hip), the
-// FMT pathway (fmt_kernels.hip) and the producer-side feature emitter (feat_conv_kernels.hip) are instances of it.
+// FMT pathway (fmt_kernels.hip), the producer-side feature emitter (feat_conv_kernels.hip) and the data gradients of FPN training
+// (fpn_train_kernels.hip, fpn_encoder_train_kernels.hip) are instances of it.
 //
 // Conv2d(CIN, COUT, K = 1 | 3 | 5 | 7, stride S = 1 | 2, padding K/2), fp32-equivalent: v_mfma_f32_16x16x32_bf16 with the three-term
 // split-bf16 product (hi*hi + hi*lo + lo*hi, fp32 accumulate; the result must not depend on the input being rounded),

@@ -1,5 +1,5 @@
 // Fixed-order reduction of per-workgroup fp32 partials: the weight-gradient kernels of the feature side (fmt_kernels.hip,
-// fpn_train_kernels.hip) leave one partial per workgroup and this kernel adds them; no atomics, so a gradient is the same bits from
+// fpn_train_kernels.hip, fpn_encoder_train_kernels.hip) leave one partial per workgroup and this kernel adds them; no atomics, so a gradient is the same bits from
 // run to run.
 #pragma once
 #include "mvs_common.h"

@@ -7,9 +7,10 @@ BatchNorm folded on the host, the decoder's lateral merges as one kernel each, a
 full-resolution map is never written.
 
 Outputs are fp32 planar ``[N, C, H, W]``.  Under the reference's bf16 autocast (``test.py:250``) its own modules return bf16; these
-return the fp32-equivalent values (inputs in bf16 are widened once).  Inference only: ``train()`` mode or an input that requires
-grad raises.  ``patch_fpn(model)`` swaps a model's ``encoder`` / ``decoder`` for these and leaves everything else alone.
-``TrainableFPNDecoder`` (``patch_fpn(model, trainable_decoder=True)``) adds the decoder's train mode.
+return the fp32-equivalent values (inputs in bf16 are widened once).  ``FPNEncoder`` / ``FPNDecoder`` are inference only: ``train()``
+mode or an input that requires grad raises.  ``patch_fpn(model)`` swaps a model's ``encoder`` / ``decoder`` for these and leaves
+everything else alone.  ``TrainableFPNDecoder`` (``patch_fpn(model, trainable_decoder=True)``) adds the decoder's train mode (DESIGN.md
+section 4.18) and ``TrainableFPNEncoder`` (``trainable_encoder=True``) the encoder's (section 4.19).
 """
 from __future__ import annotations
 
@@ -183,23 +184,44 @@ class TrainableFPNDecoder(FPNDecoder):
         return super().forward(conv01, conv11, conv21, conv31)
 
 
+class TrainableFPNEncoder(FPNEncoder):
+    """FPNEncoder with a train mode: the same constructor and state-dict keys.  In train mode its forward is
+    ``training.fpn_encoder_forward_train`` (batch-statistics BatchNorm + LeakyReLU in all 11 blocks, running statistics updated, gradients
+    for all 33 parameters; the image gets none, and an image that requires grad raises).  In eval mode under no_grad it is
+    FPNEncoder.forward, bit for bit.  Eval mode with grad enabled on an input that requires grad - gradients through frozen BatchNorm
+    statistics - is not built and raises."""
+
+    def forward(self, x: torch.Tensor) -> List[torch.Tensor]:
+        if self.training:
+            from .training import fpn_encoder_forward_train
+            return fpn_encoder_forward_train(self, x)
+        if torch.is_grad_enabled() and x.requires_grad:
+            raise RuntimeError("TrainableFPNEncoder in eval() mode has no autograd: gradients through frozen (running-statistics) BatchNorm are "
+                               "not built; call .train() for batch-statistics training, or run eval() under torch.no_grad()")
+        return super().forward(x)
+
+
 def _feat_chs_of(enc: nn.Module) -> List[int]:
     return [enc.conv00.conv.out_channels, enc.downsample1.conv.out_channels, enc.downsample2.conv.out_channels,
             enc.downsample3.conv.out_channels]
 
 
-def patch_fpn(model: nn.Module, trainable_decoder: bool = False) -> nn.Module:
+def patch_fpn(model: nn.Module, trainable_decoder: bool = False, trainable_encoder: bool = False) -> nn.Module:
     """Swap ``model.encoder`` / ``model.decoder`` (the reference's FPNEncoder / FPNDecoder) for the native modules: parameters carried
     over by ``load_state_dict(strict=True)``, device and train / eval mode preserved.  The ViT, CrossVITDecoder, FMT, the
     ``conv31 + vit_feat`` add and the fusions are left as they are.  Returns ``model``: ``model = patch_fpn(patch_model(model))``.
-    trainable_decoder=True installs ``TrainableFPNDecoder`` as the decoder and leaves ``model.encoder`` untouched: the native encoder
-    cannot train, so the reference's stays."""
+    With neither flag both inference forms are installed.  trainable_decoder=True installs ``TrainableFPNDecoder`` as the decoder,
+    trainable_encoder=True ``TrainableFPNEncoder`` as the encoder (DESIGN.md sections 4.18, 4.19); with one flag alone the other module
+    is left untouched, the very same object."""
     enc, dec = model.encoder, model.decoder
     if not isinstance(enc.conv00.bn, nn.BatchNorm2d):
         raise NotImplementedError("patch_fpn: the encoder's norm is %s; the native FPNEncoder folds BatchNorm2d (norm_type='BN')" % type(enc.conv00.bn).__name__)
     feat_chs = _feat_chs_of(enc)
-    swaps = (("decoder", dec, TrainableFPNDecoder(feat_chs)),) if trainable_decoder else \
-        (("encoder", enc, FPNEncoder(feat_chs)), ("decoder", dec, FPNDecoder(feat_chs)))
+    if trainable_decoder or trainable_encoder:
+        swaps = ((("encoder", enc, TrainableFPNEncoder(feat_chs)),) if trainable_encoder else ()) + \
+            ((("decoder", dec, TrainableFPNDecoder(feat_chs)),) if trainable_decoder else ())
+    else:
+        swaps = (("encoder", enc, FPNEncoder(feat_chs)), ("decoder", dec, FPNDecoder(feat_chs)))
     for name, old, new in swaps:
         new.load_state_dict(old.state_dict(), strict=True)
         ref = next(old.parameters())

@@ -250,6 +250,84 @@ def fpn_up2_adjoint(d_fine: torch.Tensor, out: Optional[torch.Tensor] = None) ->
     return out
 
 
+# ---- FPNEncoder in train mode ----
+
+
+def fpn_bn_leaky_fwd(z: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float, running_mean: Optional[torch.Tensor] = None,
+                     running_var: Optional[torch.Tensor] = None, momentum: float = 0.0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Batch-statistics BatchNorm2d + leaky_relu(0.1) of a planar fp32 map z [N,C,H,W] (C <= 64) -> (y, stats [3, C] = mean | biased
+    variance | invstd); running statistics as in fpn_bn_swish_fwd (the encoder's convolutions have no bias).  Sums in fp64, fixed order."""
+    z = _planar32(z)
+    N, C, H, W = z.shape
+    L = lib()
+    nbytes = L.mvs_fpn_bn_workspace_bytes(N, C, H, W)
+    ws = _workspace(nbytes, z.device, unbuilt="mvs_fpn_bn_leaky_fwd")
+    stats, y = torch.empty(3, C, dtype=torch.float32, device=z.device), torch.empty_like(z)
+    L.mvs_fpn_bn_leaky_fwd(ptr(z), None, ptr(gamma), ptr(beta), float(eps), float(momentum), ptr(running_mean), ptr(running_var),
+                           ptr(stats), ptr(y), ptr(ws), nbytes, N, C, H, W, stream_of(z))
+    return y, stats
+
+
+def fpn_bn_leaky_bwd(d_y: torch.Tensor, z: torch.Tensor, stats: torch.Tensor, gamma: torch.Tensor,
+                     beta: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Backward of fpn_bn_leaky_fwd -> (d_z, d_gamma, d_beta); du = dy (u > 0 ? 1 : 0.1) with u recomputed from z and stats."""
+    z, d_y = _planar32(z), _planar32(d_y)
+    if d_y.shape != z.shape:
+        raise ValueError("d_y must have z's shape %s; got %s" % (tuple(z.shape), tuple(d_y.shape)))
+    N, C, H, W = z.shape
+    L = lib()
+    nbytes = L.mvs_fpn_bn_workspace_bytes(N, C, H, W)
+    ws = _workspace(nbytes, z.device, unbuilt="mvs_fpn_bn_leaky_bwd")
+    d_z = torch.empty_like(z)
+    d_gamma, d_beta = torch.empty(C, dtype=torch.float32, device=z.device), torch.empty(C, dtype=torch.float32, device=z.device)
+    L.mvs_fpn_bn_leaky_bwd(ptr(d_y), ptr(z), ptr(stats), ptr(gamma), ptr(beta), ptr(d_z), ptr(d_gamma), ptr(d_beta), ptr(ws), nbytes,
+                           N, C, H, W, stream_of(z))
+    return d_z, d_gamma, d_beta
+
+
+def fpn_enc_wgrad(d_y: torch.Tensor, x: torch.Tensor, k: int, stride: int = 1) -> torch.Tensor:
+    """d_w [Cout, Cin, k, k] of Conv2d(Cin, Cout, k, stride, padding k//2): the correlation of d_y [N,Cout,OH,OW] with x [N,Cin,H,W], exact
+    fp32 products; built for the FPNEncoder's eight distinct layers.  Deterministic."""
+    d_y, x = _planar32(d_y), _planar32(x)
+    N, cin, H, W = x.shape
+    cout = d_y.shape[1]
+    if d_y.shape != (N, cout, (H - 1) // stride + 1, (W - 1) // stride + 1):
+        raise ValueError("d_y %s does not belong to x %s at stride %d" % (tuple(d_y.shape), tuple(x.shape), stride))
+    L = lib()
+    nbytes = L.mvs_fpn_enc_wgrad_workspace_bytes(N, cin, cout, int(k), int(stride), H, W)
+    ws = _workspace(nbytes, x.device, unbuilt="mvs_fpn_enc_wgrad (Cout %d, Cin %d, k %d, stride %d)" % (cout, cin, k, stride))
+    d_w = torch.empty(cout, cin, k, k, dtype=torch.float32, device=x.device)
+    L.mvs_fpn_enc_wgrad(ptr(d_y), ptr(x), ptr(d_w), ptr(ws), nbytes, N, cin, cout, int(k), int(stride), H, W, stream_of(x))
+    return d_w
+
+
+def fpn_enc_dgrad_is_built(cin: int, cout: int, k: int, stride: int) -> bool:
+    """Stride 1: the inference list's Cin = Cout instance; stride 2: the parity-class kernels."""
+    if stride == 1:
+        return cin == cout and fpn_conv_is_built(cin, cout, k, 1)
+    return bool(lib().mvs_fpn_enc_dgrad_is_built(int(cin), int(cout), int(k), int(stride)))
+
+
+def fpn_enc_dgrad(d_z: torch.Tensor, w: torch.Tensor, stride: int = 1) -> torch.Tensor:
+    """d_x of Conv2d(Cin, Cout, k, stride, padding k//2) with weight w [Cout, Cin, k, k] (fp32; packed here, on its device) from d_z
+    [N,Cout,OH,OW].  Stride 1 (Cin = Cout): mvs_fpn_conv_fwd on the flipped, channel-transposed taps -> [N,Cin,OH,OW].  Stride 2: the four
+    parity classes of the transposed convolution (mvs_fpn_enc_dgrad) -> [N,Cin,2 OH,2 OW]."""
+    d_z = _planar32(d_z)
+    N, cout, OH, OW = d_z.shape
+    cin, k = w.shape[1], w.shape[2]
+    if w.shape[0] != cout or w.shape[3] != k:
+        raise ValueError("w %s does not belong to d_z %s" % (tuple(w.shape), tuple(d_z.shape)))
+    if not fpn_enc_dgrad_is_built(cin, cout, k, stride):
+        raise _lib.MvsHipError("mvs_fpn_enc_dgrad: not built for (Cin %d, Cout %d, k %d, stride %d)" % (cin, cout, k, stride))
+    if stride == 1:
+        return fpn_conv(d_z, packing.pack_fpn_conv_weights(w.float().flip(2, 3).transpose(0, 1).contiguous(), 1), None, cin, k, 1, FPN_ACT_NONE)
+    wp = packing.pack_fpn_enc_dgrad_weights(w)
+    assert wp.numel() * wp.element_size() == lib().mvs_fpn_enc_dgrad_weights_bytes(cin, cout, k), (wp.numel(), cin, cout, k)
+    d_x = torch.empty(N, cin, 2 * OH, 2 * OW, dtype=torch.float32, device=d_z.device)
+    lib().mvs_fpn_enc_dgrad(ptr(d_z), ptr(wp), ptr(d_x), N, cin, cout, k, 2 * OH, 2 * OW, stream_of(d_z))
+    return d_x
+
+
 def _fmt_tokens(x: torch.Tensor) -> torch.Tensor:
     x = _planar32(x)
     if x.dim() < 3 or x.shape[1] != 64:

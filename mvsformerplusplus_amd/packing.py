@@ -124,6 +124,31 @@ def pack_fpn_conv_weights(w: torch.Tensor, stride: int) -> torch.Tensor:
     return pack_conv_weights_bf16x3(w.float().unsqueeze(2), fpn_chunk(cin, stride))
 
 
+def fpn_enc_dgrad_class_taps(w: torch.Tensor) -> torch.Tensor:
+    """The four parity classes of a stride-2 layer's data gradient (DESIGN.md section 4.19): w [Cout, Cin, k, k] (k = 3 | 5, padding k // 2)
+    -> [4, Cin, Cout, 3, 3], class 2 py + px.  Row 2 i + py of dx takes tap ky from row o = i + r - 1 of dz with ky = py + k // 2 + 2 - 2 r
+    (r = 0, 1, 2; a ky outside 0 .. k - 1 is a zero tap), and the same along x: each class is a 3x3 stride-1 padding-1 correlation of dz."""
+    cout, cin, k = w.shape[0], w.shape[1], w.shape[2]
+    assert w.shape[3] == k and k in (3, 5), tuple(w.shape)
+    wt = w.float().transpose(0, 1)                                               # [Cin, Cout, k, k]
+    out = wt.new_zeros(4, cin, cout, 3, 3)
+    for py in range(2):
+        for px in range(2):
+            for r in range(3):
+                ky = py + k // 2 + 2 - 2 * r
+                for s in range(3):
+                    kx = px + k // 2 + 2 - 2 * s
+                    if 0 <= ky < k and 0 <= kx < k:
+                        out[2 * py + px, :, :, r, s] = wt[:, :, ky, kx]
+    return out
+
+
+def pack_fpn_enc_dgrad_weights(w: torch.Tensor) -> torch.Tensor:
+    """Stride-2 layer weight [Cout, Cin, k, k] -> the four classes' ``pack_fpn_conv_weights(.., 1)`` one after the other
+    (``mvs_fpn_enc_dgrad``)."""
+    return torch.cat([pack_fpn_conv_weights(c.contiguous(), 1) for c in fpn_enc_dgrad_class_taps(w)])
+
+
 def pack_linear_bf16x3(w: torch.Tensor, split=None) -> torch.Tensor:
     """w [N, K] (y = x @ w.T; N % 16 == 0, K % 32 == 0) -> bf16 1-D tensor for ``tr_gemm_kernel``:
 

@@ -912,6 +912,71 @@ def fpn_decoder_forward_train(module, conv01, conv11, conv21, conv31):
     return [out0, out1, out2, out3]
 
 
+# --------------------------------------------------------------------------------------------------
+# FPNEncoder (features.py): where fpn_decoder_forward_train's input gradients go
+# --------------------------------------------------------------------------------------------------
+class FpnEncBlockTrain(torch.autograd.Function):
+    """One encoder block leaky_relu(BatchNorm2d(Conv2d(no bias)(x)), 0.1) in train mode (module.py:47-86).  Forward: the inference
+    convolution on the un-folded weights -> z, then the planar batch-statistics BatchNorm + LeakyReLU.  Kept: x, z, the statistics, the
+    weight, gamma and beta.  Backward: mvs_fpn_bn_leaky_bwd (u recomputed from z and the statistics), the weight gradient on fp32 MFMA, and
+    the data gradient - the forward convolution on flipped, channel-transposed taps at stride 1, four parity classes of 3x3 convolutions at
+    stride 2 - unless the input needs none (conv00: the image)."""
+
+    @staticmethod
+    def forward(ctx, x, bn, w, gamma, beta, stride):
+        x0, w32, g, bt = ops._f32c(x.detach()), w.detach().float().contiguous(), _fpn_vec(gamma), _fpn_vec(beta)
+        k = w32.shape[2]
+        z = ops.fpn_conv(x0, packing.pack_fpn_conv_weights(w32, stride), None, w32.shape[0], k, stride, ops.FPN_ACT_NONE)
+        rm, rv, momentum = bn.running_mean, bn.running_var, 0.0
+        if rm is not None:
+            if rm.dtype != torch.float32 or not rm.is_contiguous() or not rv.is_contiguous():
+                raise NotImplementedError("FPNEncoder training: BatchNorm running statistics must be contiguous fp32 buffers")
+            with torch.no_grad():
+                bn.num_batches_tracked += 1
+            momentum = float(bn.momentum) if bn.momentum is not None else 1.0 / float(bn.num_batches_tracked)
+        y, stats = ops.fpn_bn_leaky_fwd(z, g, bt, bn.eps, rm, rv, momentum)
+        ctx.save_for_backward(x0, z, stats, w32, g, bt)
+        ctx.stride = stride
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, d_y):
+        x0, z, stats, w32, g, bt = ctx.saved_tensors
+        d_z, d_g, d_b = ops.fpn_bn_leaky_bwd(d_y, z, stats, g, bt)
+        d_w = ops.fpn_enc_wgrad(d_z, x0, w32.shape[2], ctx.stride)
+        d_x = ops.fpn_enc_dgrad(d_z, w32, ctx.stride) if ctx.needs_input_grad[0] else None
+        return d_x, None, d_w, d_g, d_b, None
+
+
+def fpn_encoder_forward_train(module, x):
+    """FPNEncoder.forward in train mode with autograd: `module` is a features.FPNEncoder (feat_chs [8, 16, 32, 64], norm_type "BN"), x the
+    images [N, 3, H, W] with H and W multiples of 8 -> [conv01, conv11, conv21, conv31], fp32 contiguous.  nn.BatchNorm2d's train-mode
+    semantics in each of the 11 blocks: the batch mean and biased variance per channel over all N H W samples of the call (the reference's
+    training branch calls the encoder once on [B V, 3, H, W]), one momentum step of the running statistics with the unbiased variance,
+    num_batches_tracked + 1.  One autograd node per block (``FpnEncBlockTrain``): an output consumed several times (conv01 by downsample1
+    and by the decoder) has its gradients summed by autograd.  Gradients reach all 33 parameters.  The image's gradient is not built: an x
+    that requires grad raises; bf16 / fp16 images are widened once.  No double backward.  Single process only: with torch.distributed
+    initialised on more than one rank this raises (SyncBatchNorm on the feature side is not built)."""
+    if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
+        raise NotImplementedError("fpn_encoder_forward_train: batch statistics are per process; SyncBatchNorm / multi-GPU training of the "
+                                  "feature side is not built")
+    if x.dim() != 4 or x.shape[1] != 3:
+        raise ValueError("FPNEncoder takes images [N, 3, H, W]; got %s" % (tuple(x.shape),))
+    H, W = x.shape[-2:]
+    if H % 8 or W % 8:
+        raise ValueError("the native FPNEncoder needs H and W multiples of 8; got %d x %d" % (H, W))
+    if x.requires_grad and torch.is_grad_enabled():
+        raise NotImplementedError("fpn_encoder_forward_train: the image's gradient is not built (conv00's data gradient is never computed); "
+                                  "pass an image that does not require grad")
+    outs, t = {}, x.detach().float()
+    for name, _, stride in module.LAYERS:
+        blk = getattr(module, name)
+        t = FpnEncBlockTrain.apply(t, blk.bn, blk.conv.weight, blk.bn.weight, blk.bn.bias, stride)
+        outs[name] = t
+    return [outs["conv01"], outs["conv11"], outs["conv21"], outs["conv31"]]
+
+
 _FP32_TRAIN_WARNED = False
 
 
