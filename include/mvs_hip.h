@@ -671,8 +671,9 @@ mvs_status mvs_fmt_smooth_wgrad(const float* dy, const float* prev, const float*
  *   (nullable) and xn_packed = packed(LayerNorm(ln_w, ln_b, eps 1e-5)(x)) (nullable).  Row r = (b * in_views + j) * n + t is read at
  *   in + b * in_batch_stride + (in_v0 + j) * in_view_stride + t * in_row_stride (elements of in_dtype, 768 contiguous) and x_packed is
  *   written at row (b * out_V + out_v0 + j) * n + t.  prev_value lives in device memory.
- * mvs_vitdec_linear_fwd: y = epilogue(a W^T), K -> N = 768 -> 768 | 1536 | 3072 or 3072 -> 768.  epilogue 0: fp32 [M, N], elu(.) + 1 on
- *   columns < elu_cols; 1: fp32 residual + gamma * (. + bias); 2: packed-split GELU(. + bias).
+ * mvs_vitdec_linear_fwd: y = epilogue(a W^T), K -> N = 768 -> 768 | 1536 | 3072 or 1536 | 3072 -> 768.  epilogue 0: fp32 [M, N], elu(.) + 1
+ *   on columns < elu_cols; 1: fp32 residual + gamma * (. + bias); 2: packed-split GELU(. + bias).  A linear layer's data gradient
+ *   dX = dY W is this call on pack_linear_bf16x3(W^T) (1536 -> 768: [k_proj; v_proj]).
  * mvs_vitdec_kv_fwd: kv [NV * n, 1536] fp32 (elu(k) + 1 | v) -> summary [NV][12][KV_h 64 x 64 | ksum_h 64] fp32 from exact fp32
  *   products; per-slab partials in `workspace` (mvs_vitdec_kv_workspace_bytes) added in a fixed order: no atomics.
  * mvs_vitdec_apply_fwd: a = (q . KV_h) / (q . ksum_h + 1e-6), q [NV * n, 768] fp32, view i uses summary[i / kv_div] -> packed-split.
@@ -692,6 +693,27 @@ mvs_status mvs_vitdec_kv_fwd(const float* kv, void* workspace, size_t workspace_
 mvs_status mvs_vitdec_apply_fwd(const float* q, const float* summary, void* a_packed, int NV, int n, int kv_div, int channels, void* stream);
 mvs_status mvs_vitdec_conv_fwd(const void* x_packed, const void* w_packed, const float* bias, void* y, int layer, int planar, int NV, int H, int W,
                                void* stream);
+
+/* ---- training of the CrossVITDecoder's blocks ---------------------------------------------------------
+ * mvs_vitdec_wgrad: the weight gradient of a linear layer over tokens: dy [M, N] and x [M, K] fp32, token-major and contiguous ->
+ *   dw [N, K] = sum_m dy[m, n] x[m, k] fp32 and, when dbias is not null, dbias [N] = sum_m dy[m, n].  N and K multiples of 128
+ *   (in use: N = 768 | 1536 | 3072, K = 768 | 3072), any M >= 1.  Three-term split-bf16 products, the operands split while they are
+ *   staged, fp32 accumulation.  The tokens are cut into slabs of whole 32-token chunks (enough slabs for 512 workgroups over the
+ *   (N / 128) (K / 128) tiles, never more than chunks); every workgroup leaves its partial tile in `workspace`
+ *   (mvs_vitdec_wgrad_workspace_bytes = slabs * (N K + N) floats) and a second launch adds the slabs in slab order: no atomics, the
+ *   same bits from run to run and on any stream; a launch of one slab writes dw directly.
+ * mvs_vitdec_ln_bwd: LayerNorm backward over rows of 768 (one wave per row; mean and rstd recomputed from x): d_y, x [M, 768], w [768],
+ *   eps -> d_x [M, 768] = the gradient into x [+ add [M, 768], nullable: the residual branch's gradient] and d_wb [2, 768] = d_w | d_b,
+ *   from per-workgroup partials in `workspace` (mvs_vitdec_ln_bwd_workspace_bytes) added in a fixed order: no atomics.
+ * mvs_vitdec_pack_fwd: fp32 [M, channels] (768 | 1536 | 3072) -> packed-split rows: a gradient as the row operand of its data-gradient
+ *   GEMM.                                                                                                                          */
+size_t mvs_vitdec_wgrad_workspace_bytes(long long M, int N, int K);
+mvs_status mvs_vitdec_wgrad(const float* dy, const float* x, float* dw, float* dbias, void* workspace, size_t workspace_bytes, long long M, int N,
+                            int K, void* stream);
+size_t mvs_vitdec_ln_bwd_workspace_bytes(long long M, int channels);
+mvs_status mvs_vitdec_ln_bwd(const float* d_y, const float* x, const float* w, float eps, const float* add, float* d_x, float* d_wb, void* workspace,
+                             size_t workspace_bytes, long long M, int channels, void* stream);
+mvs_status mvs_vitdec_pack_fwd(const float* x, void* x_packed, long long M, int channels, void* stream);
 
 /* ==== DINOv2 ViT-B/14 backbone: forward_interval_features ==============================================
  * models/dino/dinov2.py vit_base(patch_size=14) with the shipped dino_cfg: 14 x 14 patch embedding + interpolated position embedding,

@@ -15,8 +15,8 @@ from .ops import PackedFeatures, pack_features
 from .handoff import TiledFeatureHead
 from .features import FPNDecoder, FPNEncoder, TrainableFPNDecoder, TrainableFPNEncoder, patch_fpn
 from .fmt import FMT_with_pathway, TrainableFMT_with_pathway, patch_fmt
-from .training import fmt_forward_train, fpn_decoder_forward_train, fpn_encoder_forward_train
-from .vit_decoder import CrossVITDecoder, patch_vit_decoder
+from .training import fmt_forward_train, fpn_decoder_forward_train, fpn_encoder_forward_train, vitdec_forward_train
+from .vit_decoder import CrossVITDecoder, TrainableCrossVITDecoder, patch_vit_decoder
 from .vit import DinoVisionTransformer, patch_all, patch_vit, vit_base
 from .network import DINOv2MVSNet, checkpoint_state_dict, patch_network
 from .position_encoding import PositionEncoding3D, get_position_3d
@@ -27,7 +27,7 @@ from .metrics import AbsDepthError_metrics, Thres_metrics, ValidationMeter, vali
 __all__ = ["CascadeDepthHead", "patch_model", "StageNet", "Conv3d", "Deconv3d", "ConvBnReLU", "CostRegNet", "CostRegNet3D", "CostRegNet2D",
            "PureTransformerCostReg", "get_position_3d", "PositionEncoding3D", "fusion", "PackedFeatures", "pack_features", "TiledFeatureHead", "FPNEncoder", "FPNDecoder", "TrainableFPNDecoder", "TrainableFPNEncoder", "patch_fpn", "fpn_decoder_forward_train",
            "fpn_encoder_forward_train",
-           "FMT_with_pathway", "TrainableFMT_with_pathway", "patch_fmt", "fmt_forward_train", "CrossVITDecoder", "patch_vit_decoder", "DinoVisionTransformer", "vit_base", "patch_vit", "patch_all",
+           "FMT_with_pathway", "TrainableFMT_with_pathway", "patch_fmt", "fmt_forward_train", "CrossVITDecoder", "TrainableCrossVITDecoder", "patch_vit_decoder", "vitdec_forward_train", "DinoVisionTransformer", "vit_base", "patch_vit", "patch_all",
            "DINOv2MVSNet", "patch_network", "checkpoint_state_dict",
            "depth_regression", "conf_regression", "init_range", "init_inverse_range", "schedule_inverse_range", "schedule_range",
            "homo_warping_3D_with_mask", "homo_warping_3D", "diff_homo_warping_3D_with_mask",

@@ -575,9 +575,10 @@ extern "C" int mvs_vit_rows_fwd(const void* in, int in_dtype, long long in_batch
 
 extern "C" int mvs_vitdec_linear_fwd(const void* a_packed, const void* w_packed, const float* bias, const float* gamma, const float* residual,
                                      void* y, int M, int K, int N, int epilogue, int elu_cols, void* stream) {
-    const bool shape = (K == VD_C && (N == VD_C || N == 2 * VD_C || N == VD_HID)) || (K == VD_HID && N == VD_C);
+    // 1536 -> 768 is the data gradient of [k_proj; v_proj]: the same kernel on the transposed weight
+    const bool shape = (K == VD_C && (N == VD_C || N == 2 * VD_C || N == VD_HID)) || ((K == VD_HID || K == 2 * VD_C) && N == VD_C);
     if (!shape || epilogue < VD_EPI_F32 || epilogue > VD_EPI_SPLIT) {
-        set_error("mvs_vitdec_linear_fwd: built for the CrossBlock linears at d_model 768 (K -> N = 768 -> 768 | 1536 | 3072, 3072 -> 768) with "
+        set_error("mvs_vitdec_linear_fwd: built for the CrossBlock linears at d_model 768 (K -> N = 768 -> 768 | 1536 | 3072, 1536 | 3072 -> 768) with "
                   "epilogue 0 (fp32, elu + 1 on the leading columns), 1 (residual + gamma (. + bias)) or 2 (packed-split GELU(. + bias)) "
                   "[block.py:294-329]; got K = %d, N = %d, epilogue %d", K, N, epilogue);
         return MVS_ERR_UNSUPPORTED;

@@ -602,6 +602,73 @@ def vitdec_conv(x_packed: torch.Tensor, w_packed: torch.Tensor, bias: torch.Tens
     return out
 
 
+# ---- training of the CrossVITDecoder's blocks (csrc/vitdec_train_kernels.hip) ----
+def _vitdec_tokens(t: torch.Tensor, cols: Optional[int], what: str) -> None:
+    if t is None or t.dtype != torch.float32 or t.dim() != 2 or not t.is_contiguous() or t.shape[0] < 1 or (cols is not None and t.shape[1] != cols):
+        raise ValueError("%s must be contiguous fp32 [M, %s]; got %s" % (what, "C" if cols is None else cols,
+                                                                          None if t is None else (t.dtype, tuple(t.shape))))
+
+
+def vitdec_wgrad_slabs(M: int, N: int, K: int) -> int:
+    """Token slabs of vitdec_wgrad's launch at these sizes; 0 = not built.  The header states the workspace as slabs * (N K + N) floats;
+    the ABI's naming rule leaves no room for a count that is neither a status nor a size, so it is read off that size."""
+    return lib().mvs_vitdec_wgrad_workspace_bytes(int(M), int(N), int(K)) // ((N * K + N) * 4)
+
+
+def vitdec_wgrad(dy: torch.Tensor, x: torch.Tensor, want_bias: bool = False):
+    """Weight gradient of a linear layer over tokens: dy fp32 [M, N], x fp32 [M, K] -> dw fp32 [N, K] = dy^T x (three-term split-bf16
+    products, per-slab partials added in slab order: no atomics), and with want_bias (dw, dbias [N] = column sums of dy)."""
+    _vitdec_tokens(dy, None, "dy")
+    _vitdec_tokens(x, None, "x")
+    if x.shape[0] != dy.shape[0] or x.device != dy.device:
+        raise ValueError("dy %s and x %s must have the same rows and device" % (tuple(dy.shape), tuple(x.shape)))
+    M, N, K = dy.shape[0], dy.shape[1], x.shape[1]
+    L = lib()
+    ws_bytes = L.mvs_vitdec_wgrad_workspace_bytes(M, N, K)
+    ws = _workspace(ws_bytes, dy.device, unbuilt="mvs_vitdec_wgrad: built for N and K multiples of 128 (dw [%d, %d])" % (N, K))
+    dw = torch.empty(N, K, dtype=torch.float32, device=dy.device)
+    db = torch.empty(N, dtype=torch.float32, device=dy.device) if want_bias else None
+    L.mvs_vitdec_wgrad(ptr(dy), ptr(x), ptr(dw), ptr(db), ptr(ws), ws_bytes, M, N, K, stream_of(dy))
+    return (dw, db) if want_bias else dw
+
+
+def vitdec_ln_bwd(d_y: torch.Tensor, x: torch.Tensor, w: torch.Tensor, eps: float, add: Optional[torch.Tensor] = None):
+    """LayerNorm backward over rows of 768: d_y, x fp32 [M, 768], w [768] -> (d_x [+ add], d_w, d_b); mean and rstd are recomputed from
+    x, d_w / d_b come from per-workgroup partials added in a fixed order."""
+    _vitdec_tokens(d_y, 768, "d_y")
+    _vitdec_tokens(x, 768, "x")
+    if add is not None:
+        _vitdec_tokens(add, 768, "add")
+    M = d_y.shape[0]
+    if x.shape[0] != M or (add is not None and add.shape[0] != M):
+        raise ValueError("d_y, x and add must have the same rows")
+    _vitdec_vec(w, 768, "w", d_y)
+    L = lib()
+    ws_bytes = L.mvs_vitdec_ln_bwd_workspace_bytes(M, 768)
+    ws = _workspace(ws_bytes, d_y.device)
+    d_x = torch.empty_like(d_y)
+    d_wb = torch.empty(2, 768, dtype=torch.float32, device=d_y.device)
+    L.mvs_vitdec_ln_bwd(ptr(d_y), ptr(x), ptr(w), float(eps), ptr(add), ptr(d_x), ptr(d_wb), ptr(ws), ws_bytes, M, 768, stream_of(d_y))
+    return d_x, d_wb[0], d_wb[1]
+
+
+def vitdec_pack(x: torch.Tensor) -> torch.Tensor:
+    """fp32 [M, C] (C = 768 | 1536 | 3072) -> the packed-split row operand of vitdec_linear."""
+    _vitdec_tokens(x, None, "x")
+    M, C = x.shape
+    if C not in (768, 1536, 3072):
+        raise ValueError("vitdec_pack is built for rows of 768, 1536 or 3072 channels; got %d" % C)
+    out = torch.empty(lib().mvs_vitdec_packed_bytes(M, C), dtype=torch.uint8, device=x.device)
+    lib().mvs_vitdec_pack_fwd(ptr(x), ptr(out), M, C, stream_of(x))
+    return out
+
+
+def vitdec_dgrad(dy: torch.Tensor, wt_packed: torch.Tensor, N_in: int, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Data gradient of a linear layer y = x W^T (W [N_out, N_in]): dy fp32 [M, N_out] -> dx fp32 [M, N_in] = dy W, the forward GEMM on
+    wt_packed = packing.pack_linear_bf16x3(W.t())."""
+    return vitdec_linear(vitdec_pack(dy), dy.shape[0], wt_packed, dy.shape[1], N_in, VITDEC_EPI_F32, bias=bias)
+
+
 VIT_KEY_STEP = 32          # the attention core's key step: every view's rows are padded to a multiple of it
 VIT_KPAD = 640             # the patch embedding's K = 588 padded to the GEMM's chunk
 

@@ -319,6 +319,24 @@ def pack_vitdec_block(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
     return out
 
 
+def pack_vitdec_block_train(sd: Dict[str, torch.Tensor], transposed: bool = True) -> Dict[str, torch.Tensor]:
+    """pack_vitdec_block for a training step: packed WHERE THE PARAMETERS LIVE (plain tensor ops: no host copy,
+    no synchronisation; the same bits as the host form), from the values they hold now - never cached, an optimiser updates them in
+    place - plus, with `transposed`, "qT" / "kvT" / "projT" / "fc1T" / "fc2T" = pack_linear_bf16x3 of the transposed weights, the
+    operands of the data gradients dX = dY W."""
+    f32 = lambda t: t.detach().float()
+    mats = {"q": f32(sd["attn.q_proj.weight"]), "kv": torch.cat([f32(sd["attn.k_proj.weight"]), f32(sd["attn.v_proj.weight"])], 0),
+            "proj": f32(sd["attn.proj.weight"]), "fc1": f32(sd["mlp.fc1.weight"]), "fc2": f32(sd["mlp.fc2.weight"])}
+    want = {"q": (768, 768), "kv": (1536, 768), "proj": (768, 768), "fc1": (3072, 768), "fc2": (768, 3072)}
+    assert {k: tuple(v.shape) for k, v in mats.items()} == want, {k: tuple(v.shape) for k, v in mats.items()}
+    out = {k: pack_linear_bf16x3(v) for k, v in mats.items()}
+    if transposed:
+        out.update({k + "T": pack_linear_bf16x3(v.t()) for k, v in mats.items()})
+    for k in VITDEC_VECTORS:
+        out[k] = f32(sd[k]).reshape(-1).contiguous()
+    return out
+
+
 def _fold_conv_bn(w: torch.Tensor, b: torch.Tensor, bn: Dict[str, torch.Tensor], out_dim: int):
     """Conv (with bias) + eval BatchNorm -> (w * scale, (b - mean) * scale + beta), computed in fp64."""
     scale = bn["weight"].double() / torch.sqrt(bn["running_var"].double() + float(bn.get("eps", BN_EPS)))

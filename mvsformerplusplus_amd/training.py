@@ -42,7 +42,8 @@ lateral, ``mvs_fmt_path_bwd`` - the interpolation's exact adjoint as a gather - 
 ``mvs_fmt_smooth_wgrad`` on fp32 MFMA for the 3x3 weights, the merged map recomputed in its staging; no atomics).  Its input gradients
 go on into ``fpn_decoder_forward_train``, the train-mode FPNDecoder: planar batch-statistics BatchNorm + Swish,
 weight gradients on fp32 MFMA, the upsample's adjoint as a gather, the last level fused so that its 64-channel full-resolution map is
-never written in either direction.  The FPN encoder, the ViT and its decoder have no training form.
+never written in either direction.  The FPN encoder trains in ``fpn_encoder_forward_train`` (section 4.19) and the ViT decoder in
+``vitdec_forward_train`` (section 4.20: block backward native, head on PyTorch ops); the ViT backbone is frozen and has no training form.
 """
 from __future__ import annotations
 
@@ -975,6 +976,180 @@ def fpn_encoder_forward_train(module, x):
         t = FpnEncBlockTrain.apply(t, blk.bn, blk.conv.weight, blk.bn.weight, blk.bn.bias, stride)
         outs[name] = t
     return [outs["conv01"], outs["conv11"], outs["conv21"], outs["conv31"]]
+
+
+# --------------------------------------------------------------------------------------------------
+# CrossVITDecoder (vit_decoder.py): the ViT feature decoder whose output is added to the FPN's conv31
+# --------------------------------------------------------------------------------------------------
+VITDEC_BLOCK_PARAMS = FMT_BLOCK_PARAMS          # a CrossBlock's 15 parameters, the same names at d_model 768
+
+
+def _vitdec_block_launches(pb, x0, r0, kv_div, n):
+    """CrossVITDecoder.block on tokens x0 [NVq n, 768] with the keys / values of r0 [NVkv n, 768] (None: self attention on norm1(x0))."""
+    from .vit_decoder import CrossVITDecoder
+    NVq = x0.shape[0] // n
+    xn = ops.vitdec_rows(x0.view(1, NVq, n, 768), 0, NVq, ln=(pb["norm1.weight"], pb["norm1.bias"]), want_x=False)[2]
+    if r0 is None:
+        return CrossVITDecoder.block(pb, x0, xn, xn, NVq, NVq, n, 1)
+    NVkv = r0.shape[0] // n
+    keys = ops.vitdec_rows(r0.view(1, NVkv, n, 768), 0, NVkv, want_x=False, want_packed=True)[1]
+    return CrossVITDecoder.block(pb, x0, xn, keys, NVq, NVkv, n, kv_div)
+
+
+class VitdecBlockTrain(torch.autograd.Function):
+    """One pre-norm CrossBlock of the ViT decoder (vit_decoder.py, tests/vit_decoder_ref.py::block) on tokens x fp32 [N, n, 768].
+    ref = None: self attention, keys and values from norm1(x).  ref [N / kv_div, n, 768]: cross attention, view i reads the summary of
+    ref[i // kv_div] UN-normalised (pre_norm_query).  Forward = CrossVITDecoder.block's own launches on weights packed on the device from
+    the live parameters: the inference bits.  Kept for the backward: x and ref.  The backward packs W and W^T again, recomputes the
+    forward (every GEMM on mvs_vitdec_linear_fwd, pre-activations from epilogue 0), and is hand-written: every linear layer's weight
+    gradient on mvs_vitdec_wgrad, every data gradient on mvs_vitdec_linear_fwd with the transposed weight, both LayerNorms on
+    mvs_vitdec_ln_bwd (the residual branch's gradient added in the same pass); elu + 1, GELU, LayerScale and the linear-attention core's
+    adjoints are fp32 tensor expressions.  d_ref is summed over the kv_div views that share a reference.  No double backward."""
+
+    @staticmethod
+    def forward(ctx, x, ref, kv_div, *params):
+        P = [p.detach() for p in params]
+        pb = packing.pack_vitdec_block_train(dict(zip(VITDEC_BLOCK_PARAMS, P)), transposed=False)
+        N, n = x.shape[:2]
+        x0 = ops._f32c(x.detach()).reshape(N * n, 768)
+        r0 = None if ref is None else ops._f32c(ref.detach()).reshape(-1, 768)
+        y = _vitdec_block_launches(pb, x0, r0, kv_div, n)
+        ctx.save_for_backward(x0, r0, *P)
+        ctx.kv_div, ctx.n = kv_div, n
+        return y.view(N, n, 768)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, d_y):
+        x0, r0 = ctx.saved_tensors[:2]
+        pb = packing.pack_vitdec_block_train(dict(zip(VITDEC_BLOCK_PARAMS, ctx.saved_tensors[2:])))
+        n1w, n1b, bp, g1, n2w, n2b, b1, b2, g2 = (pb[k] for k in packing.VITDEC_VECTORS)
+        n, kv_div, eps, F32 = ctx.n, ctx.kv_div, 1e-5, ops.VITDEC_EPI_F32
+        M = x0.shape[0]
+        NVq = M // n
+        dy = ops._f32c(d_y).reshape(M, 768)
+        ln = lambda t, w, b: F.layer_norm(t, (768,), w, b, eps)
+        # ---- recompute the forward: attention half
+        xn = ln(x0, n1w, n1b)
+        xn_p = ops.vitdec_rows(x0.view(1, NVq, n, 768), 0, NVq, ln=(n1w, n1b), want_x=False)[2]
+        kvn, kv_p = (xn, xn_p) if r0 is None else (r0, ops.vitdec_pack(r0))
+        Mk = kvn.shape[0]
+        Nr = Mk // n
+        heads = lambda t, views: t.reshape(Nr, views * n, 12, 64)
+        q = ops.vitdec_linear(xn_p, M, pb["q"], 768, 768, F32, elu_cols=768)
+        kv = ops.vitdec_linear(kv_p, Mk, pb["kv"], 768, 1536, F32, elu_cols=768)
+        k, v = kv[:, :768], kv[:, 768:]
+        qh, kh, vh = heads(q, kv_div), heads(k, 1), heads(v, 1)
+        summary = ops.vitdec_kv(kv, Nr, n)
+        KV, ks = summary[:, :, :4096].reshape(Nr, 12, 64, 64), summary[:, :, 4096:]
+        Z = 1.0 / (torch.einsum("blhd,bhd->blh", qh, ks) + 1e-6)
+        num = torch.einsum("blhd,bhdm->blhm", qh, KV)
+        a = (num * Z.unsqueeze(-1)).reshape(M, 768)
+        yp = ops.vitdec_linear(ops.vitdec_pack(a), M, pb["proj"], 768, 768, F32, bias=bp)
+        x1 = x0 + g1 * yp
+        # ---- FFN half, forward and backward
+        u = ln(x1, n2w, n2b)
+        u_p = ops.vitdec_rows(x1.view(1, NVq, n, 768), 0, NVq, ln=(n2w, n2b), want_x=False)[2]
+        pre = ops.vitdec_linear(u_p, M, pb["fc1"], 768, 3072, F32, bias=b1)
+        hdn = F.gelu(pre)
+        y2 = ops.vitdec_linear(ops.vitdec_pack(hdn), M, pb["fc2"], 3072, 768, F32, bias=b2)
+        d_g2, d_y2 = (dy * y2).sum(0), dy * g2
+        d_w2, d_b2 = ops.vitdec_wgrad(d_y2, hdn, want_bias=True)
+        d_pre = ops.vitdec_dgrad(d_y2, pb["fc2T"], 3072) * \
+            (0.5 * (1.0 + torch.erf(pre * 0.7071067811865476)) + pre * torch.exp(-0.5 * pre * pre) * 0.3989422804014327)
+        d_w1, d_b1 = ops.vitdec_wgrad(d_pre, u, want_bias=True)
+        d_x1, d_n2w, d_n2b = ops.vitdec_ln_bwd(ops.vitdec_dgrad(d_pre, pb["fc1T"], 768), x1, n2w, eps, add=dy)
+        # ---- attention half
+        d_g1, d_yp = (d_x1 * yp).sum(0), d_x1 * g1
+        d_wp, d_bp = ops.vitdec_wgrad(d_yp, a, want_bias=True)
+        d_a = heads(ops.vitdec_dgrad(d_yp, pb["projT"], 768), kv_div)
+        d_num = d_a * Z.unsqueeze(-1)
+        d_den = -(d_a * num).sum(-1) * Z * Z
+        d_q = torch.einsum("blhm,bhdm->blhd", d_num, KV) + d_den.unsqueeze(-1) * ks.unsqueeze(1)
+        d_KV = torch.einsum("blhd,blhm->bhdm", qh, d_num)
+        d_ks = torch.einsum("blhd,blh->bhd", qh, d_den)
+        d_k = torch.einsum("bhdm,bshm->bshd", d_KV, vh) + d_ks.unsqueeze(1)
+        d_v = torch.einsum("bshd,bhdm->bshm", kh, d_KV)
+        # out = elu(pre) + 1: the derivative is 1 where out > 1 and exp(pre) = out elsewhere
+        d_qp = d_q.reshape(M, 768) * torch.where(q > 1, torch.ones_like(q), q)
+        d_kpv = torch.cat([d_k.reshape(Mk, 768) * torch.where(k > 1, torch.ones_like(k), k), d_v.reshape(Mk, 768)], 1)
+        d_wq = ops.vitdec_wgrad(d_qp, xn)
+        d_wkv = ops.vitdec_wgrad(d_kpv, kvn.contiguous())
+        # the data gradients into norm1: always needed for d_norm1 (and d_x) on the query side; on the key side only where the keys are
+        # norm1(x) (self attention) or the reference needs a gradient (level 0's is the frozen backbone's output)
+        d_xn, d_ref = ops.vitdec_dgrad(d_qp, pb["qT"], 768), None
+        if r0 is None:
+            d_xn = d_xn + ops.vitdec_dgrad(d_kpv, pb["kvT"], 768)
+        elif ctx.needs_input_grad[1]:
+            d_ref = ops.vitdec_dgrad(d_kpv, pb["kvT"], 768).view(Nr, n, 768)
+        d_x, d_n1w, d_n1b = ops.vitdec_ln_bwd(d_xn, x0, n1w, eps, add=d_x1)
+        return (d_x.view(NVq, n, 768), d_ref, None, d_n1w, d_n1b, d_wq, d_wkv[:768], d_wkv[768:], d_wp, d_bp, d_g1, d_n2w, d_n2b, d_w1, d_b1,
+                d_w2, d_b2, d_g2)
+
+
+class VitdecMixTrain(torch.autograd.Function):
+    """The AAS step norm_layers[i - 1](prev_values[i - 1] * prev + x_i) (module.py:349-352): prev fp32 [N, n, 768], x_i the level's ViT
+    feature [B, views, n, 768] (N = B views; fp32 / bf16 / fp16, read in place with its strides) -> [N, n, 768].  Forward = the row kernel.
+    Backward: mvs_vitdec_ln_bwd on the recomputed mix for d_mix_w, d_mix_b and the mix's gradient, then d_prev = prev_value * that and
+    d_prev_value = <that, prev>.  x_i (the frozen backbone's output) gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, prev, x_i, prev_value, mix_w, mix_b):
+        N, n = prev.shape[:2]
+        p0 = ops._f32c(prev.detach()).reshape(N * n, 768)
+        pv, w, b = prev_value.detach().float().reshape(1), _fpn_vec(mix_w), _fpn_vec(mix_b)
+        y = ops.vitdec_rows(x_i, 0, x_i.shape[1], prev=p0, prev_value=pv, mix=(w, b))[0]
+        ctx.save_for_backward(p0, x_i, pv, w)
+        ctx.pv_shape = prev_value.shape
+        return y.view(N, n, 768)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, d_y):
+        p0, x_i, pv, w = ctx.saved_tensors
+        s = pv * p0 + x_i.float().reshape(p0.shape)
+        d_s, d_w, d_b = ops.vitdec_ln_bwd(ops._f32c(d_y).reshape(p0.shape), s, w, 1e-6)
+        return (pv * d_s).view(d_y.shape), None, (d_s * p0).sum().reshape(ctx.pv_shape), d_w, d_b
+
+
+def vitdec_forward_train(module, x, vit_shape):
+    """CrossVITDecoder.forward in train mode with autograd: `module` is a vit_decoder.CrossVITDecoder, x the three [B, V, h w, 768] ViT
+    interval features (fp32 / bf16 / fp16, read in place with their strides), vit_shape = [B, V, h, w, 768] -> fp32 [B V, 64, 4 h, 4 w].
+    The reference views run the two self blocks, all B (V - 1) source views one node per cross level (``VitdecBlockTrain``), the AAS
+    steps are ``VitdecMixTrain`` nodes; ref_feat_list[i] collects its gradient from the next self block, the cross block of level i and,
+    for the last level, the output tokens - autograd sums them, as it sums the gradients of prev_values / norm_layers, which the
+    reference path and the source path share.  The head (proj, upsampler0, upsampler1) runs on the module's own nn.Sequential layers in
+    train mode: PyTorch ops with batch-statistics BatchNorm over all B V views, exactly what the reference runs; its native train-mode
+    form is not built yet.  The backbone is frozen (the reference runs it under torch.no_grad()): an input that requires grad raises.
+    V = 1 runs no cross block, so their parameters get no gradient.  No double backward.  Single process only: with torch.distributed
+    initialised on more than one rank this raises (the BatchNorm statistics are per process)."""
+    if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
+        raise NotImplementedError("vitdec_forward_train: batch statistics are per process; SyncBatchNorm / multi-GPU training of the "
+                                  "feature side is not built")
+    B, V, h, w = module._check_shapes(x, None, vit_shape)
+    if torch.is_grad_enabled() and any(t.requires_grad for t in x):
+        raise NotImplementedError("vitdec_forward_train: the gradient into the ViT features is not built (the DINOv2 backbone is frozen and "
+                                  "runs under torch.no_grad()); pass inputs that do not require grad")
+    n = h * w
+    xs = [module._rows_input(t.detach()) for t in x]
+    params = lambda blk: [blk.get_parameter(k) for k in VITDEC_BLOCK_PARAMS]
+    mix = lambda i: (module.prev_values[i - 1], module.norm_layers[i - 1].weight, module.norm_layers[i - 1].bias)
+    cur = xs[0][:, 0].float()
+    refs = [cur]                                                      # ref_feat_list: the cross blocks' keys / values
+    for i in range(1, len(module.cross_attn_blocks)):
+        y = VitdecBlockTrain.apply(cur, None, 1, *params(module.self_attn_blocks[i - 1]))
+        cur = VitdecMixTrain.apply(y, xs[i][:, :1], *mix(i))
+        refs.append(cur)
+    views = [cur.unsqueeze(1)]
+    if V > 1:
+        # every source view of the batch in one node per level: view b (V - 1) + j attends to reference view b
+        S, y = V - 1, None
+        for i, blk in enumerate(module.cross_attn_blocks):
+            q = xs[0][:, 1:].float().reshape(B * S, n, 768) if i == 0 else VitdecMixTrain.apply(y, xs[i][:, 1:], *mix(i))
+            y = VitdecBlockTrain.apply(q, refs[i], S, *params(blk))
+        views.append(y.reshape(B, S, n, 768))
+    tokens = torch.cat(views, 1).reshape(B * V, h, w, 768).permute(0, 3, 1, 2)
+    return module.upsampler1(module.upsampler0(module.proj(tokens)))
 
 
 _FP32_TRAIN_WARNED = False

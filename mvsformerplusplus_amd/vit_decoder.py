@@ -7,7 +7,8 @@ blocks on the reference views of the batch, three cross-attention blocks on all 
 cross block's key/value summary is computed once per reference view), then ``proj`` and the two transposed convolutions as implicit
 GEMMs.  The output is fp32 contiguous ``[B * V, 64, 4 h, 4 w]``.  The inputs (fp32 / bf16 / fp16) are read IN PLACE with their batch,
 view and row strides - the reference hands over ``x[:, 1:]`` views of the ViT's output, which are not contiguous - and widened as they
-are read: nothing is copied.  Inference only: ``train()`` mode or an input that requires grad raises.  ``prev_values`` are read on the
+are read: nothing is copied.  ``CrossVITDecoder`` is the inference form: ``train()`` mode or an input that requires grad raises;
+``TrainableCrossVITDecoder`` (``patch_vit_decoder(model, trainable=True)``) trains.  ``prev_values`` are read on the
 device; there is no host synchronisation, every launch goes to the current stream, and the forward is one linear chain of launches,
 capturable by ``torch.cuda.graph`` after one warm call (packed weights are built and uploaded on first use).
 ``patch_vit_decoder(model)`` swaps a model's ``decoder_vit`` and leaves everything else alone.
@@ -105,7 +106,7 @@ class CrossVITDecoder(nn.Module):
             return p
         return self._cache.get(self, build)
 
-    def _check(self, x, Fmats, vit_shape):
+    def _check_shapes(self, x, Fmats, vit_shape):
         if Fmats is not None:
             raise ValueError("CrossVITDecoder.forward: Fmats must be None (the reference ignores it)")
         if vit_shape is None or len(vit_shape) != 5:
@@ -116,6 +117,10 @@ class CrossVITDecoder(nn.Module):
             raise ValueError("CrossVITDecoder.forward takes x = three [B, V, h w, 768] tensors and vit_shape = [B, V, h, w, 768]; got %s, %s"
                              % ([tuple(t.shape) if torch.is_tensor(t) else type(t) for t in x] if isinstance(x, (list, tuple)) else type(x),
                                 list(vit_shape)))
+        return B, V, h, w
+
+    def _check(self, x, Fmats, vit_shape):
+        B, V, h, w = self._check_shapes(x, Fmats, vit_shape)
         if self.training or (torch.is_grad_enabled() and any(t.requires_grad for t in x)):
             raise RuntimeError(_TRAIN_MSG % type(self).__name__)
         return B, V, h, w
@@ -187,11 +192,28 @@ class CrossVITDecoder(nn.Module):
             return ops.vitdec_conv(t, *p["upsampler1"], ops.VITDEC_UP1, B * V, 2 * h, 2 * w, planar=True)
 
 
-def patch_vit_decoder(model: nn.Module) -> nn.Module:
+class TrainableCrossVITDecoder(CrossVITDecoder):
+    """CrossVITDecoder with autograd: the same constructor, state-dict keys and configuration refusals.  In
+    eval() mode its forward is the inference path; in train() mode it is ``training.vitdec_forward_train``: the five blocks and the AAS
+    steps forward and backward on the library's kernels, weights packed on the device from the live parameters at every call, the head
+    (proj, upsampler0, upsampler1) on its own PyTorch layers with batch-statistics BatchNorm.  The ViT features get no gradient (the
+    backbone is frozen): an input that requires grad raises."""
+
+    def forward(self, x, Fmats=None, vit_shape=None):
+        if not self.training:
+            return super().forward(x, Fmats, vit_shape)
+        from .training import vitdec_forward_train
+        if Fmats is not None:
+            raise ValueError("CrossVITDecoder.forward: Fmats must be None (the reference ignores it)")
+        return vitdec_forward_train(self, x, vit_shape)                     # checks the shapes itself
+
+
+def patch_vit_decoder(model: nn.Module, trainable: bool = False) -> nn.Module:
     """Swap ``model.decoder_vit`` (the reference's CrossVITDecoder) for the native module: parameters and buffers carried over by
     ``load_state_dict(strict=True)``, device and train / eval mode preserved.  What the old module's blocks do (post_norm, pre_norm_query)
     and its no_combine_norm flag are read from the old module, because the state dict does not show them.  Everything else is left as
-    it is.  Returns ``model``: ``model = patch_vit_decoder(patch_fmt(patch_fpn(patch_model(model))))``."""
+    it is.  Returns ``model``: ``model = patch_vit_decoder(patch_fmt(patch_fpn(patch_model(model))))``.  trainable=True installs
+    ``TrainableCrossVITDecoder`` instead of the inference form."""
     old = model.decoder_vit
     blocks = list(getattr(old, "self_attn_blocks", [])) + list(getattr(old, "cross_attn_blocks", []))
     sd = old.state_dict()
@@ -210,7 +232,7 @@ def patch_vit_decoder(model: nn.Module) -> nn.Module:
                self_cross_types=getattr(old, "self_cross_types", None))
     args = {"dino_cfg": dict(dino, decoder_cfg=cfg, cross_interval_layers=len(getattr(old, "cross_attn_blocks", []))),
             "out_ch": sd["upsampler1.0.weight"].shape[1], "vit_ch": sd["proj.0.weight"].shape[1]}
-    new = CrossVITDecoder(args)
+    new = (TrainableCrossVITDecoder if trainable else CrossVITDecoder)(args)
     new.load_state_dict(sd, strict=True)
     ref = next(old.parameters())
     model.decoder_vit = new.to(ref.device).train(old.training)
