@@ -155,38 +155,60 @@ def fpn_merge_conv(prev: torch.Tensor, lateral: torch.Tensor, w_inner: torch.Ten
 # ---- FPNDecoder in train mode ----
 
 
-def fpn_bn_swish_fwd(z: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float, conv_bias: Optional[torch.Tensor] = None,
-                     running_mean: Optional[torch.Tensor] = None, running_var: Optional[torch.Tensor] = None,
-                     momentum: float = 0.0) -> Tuple[torch.Tensor, torch.Tensor]:
-    """Batch-statistics BatchNorm2d + Swish of a planar fp32 map z [N,C,H,W] (C <= 64) -> (y, stats [3, C] = mean | biased variance |
-    invstd).  Given running_mean / running_var (fp32, contiguous; updated in place), one step of `momentum` with mean + conv_bias and the
-    unbiased variance - what nn.BatchNorm2d does behind a convolution with that bias.  Sums in fp64, fixed order."""
+def _planar_bn_fwd(entry, z, gamma, beta, eps, conv_bias, running_mean, running_var, momentum):
+    """The body of the planar batch-statistics BatchNorm forwards; `entry` names the library's function (it fixes the activation)."""
     z = _planar32(z)
     N, C, H, W = z.shape
     L = lib()
     nbytes = L.mvs_fpn_bn_workspace_bytes(N, C, H, W)
-    ws = _workspace(nbytes, z.device, unbuilt="mvs_fpn_bn_swish_fwd")
+    ws = _workspace(nbytes, z.device, unbuilt=entry)
     stats, y = torch.empty(3, C, dtype=torch.float32, device=z.device), torch.empty_like(z)
-    L.mvs_fpn_bn_swish_fwd(ptr(z), ptr(conv_bias), ptr(gamma), ptr(beta), float(eps), float(momentum), ptr(running_mean), ptr(running_var),
-                           ptr(stats), ptr(y), ptr(ws), nbytes, N, C, H, W, stream_of(z))
+    getattr(L, entry)(ptr(z), ptr(conv_bias), ptr(gamma), ptr(beta), float(eps), float(momentum), ptr(running_mean), ptr(running_var),
+                      ptr(stats), ptr(y), ptr(ws), nbytes, N, C, H, W, stream_of(z))
     return y, stats
 
 
-def fpn_bn_swish_bwd(d_y: torch.Tensor, z: torch.Tensor, stats: torch.Tensor, gamma: torch.Tensor,
-                     beta: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-    """Backward of fpn_bn_swish_fwd -> (d_z, d_gamma, d_beta)."""
+def _planar_bn_bwd(entry, d_y, z, stats, gamma, beta):
+    """The body of the planar BatchNorm backwards -> (d_z, d_gamma, d_beta)."""
     z, d_y = _planar32(z), _planar32(d_y)
     if d_y.shape != z.shape:
         raise ValueError("d_y must have z's shape %s; got %s" % (tuple(z.shape), tuple(d_y.shape)))
     N, C, H, W = z.shape
     L = lib()
     nbytes = L.mvs_fpn_bn_workspace_bytes(N, C, H, W)
-    ws = _workspace(nbytes, z.device, unbuilt="mvs_fpn_bn_swish_bwd")
+    ws = _workspace(nbytes, z.device, unbuilt=entry)
     d_z = torch.empty_like(z)
     d_gamma, d_beta = torch.empty(C, dtype=torch.float32, device=z.device), torch.empty(C, dtype=torch.float32, device=z.device)
-    L.mvs_fpn_bn_swish_bwd(ptr(d_y), ptr(z), ptr(stats), ptr(gamma), ptr(beta), ptr(d_z), ptr(d_gamma), ptr(d_beta), ptr(ws), nbytes,
-                           N, C, H, W, stream_of(z))
+    getattr(L, entry)(ptr(d_y), ptr(z), ptr(stats), ptr(gamma), ptr(beta), ptr(d_z), ptr(d_gamma), ptr(d_beta), ptr(ws), nbytes,
+                      N, C, H, W, stream_of(z))
     return d_z, d_gamma, d_beta
+
+
+def _planar_wgrad(entry, what, variant, d_y, x, k, cols):
+    """The body of the planar weight gradients: d_w [Cout, cols, k, k] on `entry`, built per (Cout, Cin, k, variant = `what`: ones | stride)."""
+    N, cin, H, W = x.shape
+    cout = d_y.shape[1]
+    L = lib()
+    nbytes = getattr(L, entry + "_workspace_bytes")(N, cin, cout, int(k), variant, H, W)
+    ws = _workspace(nbytes, x.device, unbuilt="%s (Cout %d, Cin %d, k %d, %s %d)" % (entry, cout, cin, k, what, variant))
+    d_w = torch.empty(cout, cols, k, k, dtype=torch.float32, device=x.device)
+    getattr(L, entry)(ptr(d_y), ptr(x), ptr(d_w), ptr(ws), nbytes, N, cin, cout, int(k), variant, H, W, stream_of(x))
+    return d_w
+
+
+def fpn_bn_swish_fwd(z: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float, conv_bias: Optional[torch.Tensor] = None,
+                     running_mean: Optional[torch.Tensor] = None, running_var: Optional[torch.Tensor] = None,
+                     momentum: float = 0.0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Batch-statistics BatchNorm2d + Swish of a planar fp32 map z [N,C,H,W] (C <= 64) -> (y, stats [3, C] = mean | biased variance |
+    invstd).  Given running_mean / running_var (fp32, contiguous; updated in place), one step of `momentum` with mean + conv_bias and the
+    unbiased variance - what nn.BatchNorm2d does behind a convolution with that bias.  Sums in fp64, fixed order."""
+    return _planar_bn_fwd("mvs_fpn_bn_swish_fwd", z, gamma, beta, eps, conv_bias, running_mean, running_var, momentum)
+
+
+def fpn_bn_swish_bwd(d_y: torch.Tensor, z: torch.Tensor, stats: torch.Tensor, gamma: torch.Tensor,
+                     beta: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Backward of fpn_bn_swish_fwd -> (d_z, d_gamma, d_beta)."""
+    return _planar_bn_bwd("mvs_fpn_bn_swish_bwd", d_y, z, stats, gamma, beta)
 
 
 def fpn_train_conv_is_built(cin: int, cout: int, k: int) -> bool:
@@ -215,12 +237,7 @@ def fpn_wgrad(d_y: torch.Tensor, x: torch.Tensor, k: int, ones: bool = False) ->
     N, cout, H, W = d_y.shape
     cin = x.shape[1]
     assert x.shape == (N, cin, H, W), (tuple(d_y.shape), tuple(x.shape))
-    L = lib()
-    nbytes = L.mvs_fpn_wgrad_workspace_bytes(N, cin, cout, int(k), int(ones), H, W)
-    ws = _workspace(nbytes, x.device, unbuilt="mvs_fpn_wgrad (Cout %d, Cin %d, k %d, ones %d)" % (cout, cin, k, ones))
-    d_w = torch.empty(cout, cin + int(ones), k, k, dtype=torch.float32, device=x.device)
-    L.mvs_fpn_wgrad(ptr(d_y), ptr(x), ptr(d_w), ptr(ws), nbytes, N, cin, cout, int(k), int(ones), H, W, stream_of(x))
-    return d_w
+    return _planar_wgrad("mvs_fpn_wgrad", "ones", int(ones), d_y, x, k, cin + int(ones))
 
 
 def fpn_merge_wgrad(d_y: torch.Tensor, prev: torch.Tensor, lateral: torch.Tensor, w_inner: torch.Tensor, b_inner: torch.Tensor) -> torch.Tensor:
@@ -257,32 +274,13 @@ def fpn_bn_leaky_fwd(z: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, e
                      running_var: Optional[torch.Tensor] = None, momentum: float = 0.0) -> Tuple[torch.Tensor, torch.Tensor]:
     """Batch-statistics BatchNorm2d + leaky_relu(0.1) of a planar fp32 map z [N,C,H,W] (C <= 64) -> (y, stats [3, C] = mean | biased
     variance | invstd); running statistics as in fpn_bn_swish_fwd (the encoder's convolutions have no bias).  Sums in fp64, fixed order."""
-    z = _planar32(z)
-    N, C, H, W = z.shape
-    L = lib()
-    nbytes = L.mvs_fpn_bn_workspace_bytes(N, C, H, W)
-    ws = _workspace(nbytes, z.device, unbuilt="mvs_fpn_bn_leaky_fwd")
-    stats, y = torch.empty(3, C, dtype=torch.float32, device=z.device), torch.empty_like(z)
-    L.mvs_fpn_bn_leaky_fwd(ptr(z), None, ptr(gamma), ptr(beta), float(eps), float(momentum), ptr(running_mean), ptr(running_var),
-                           ptr(stats), ptr(y), ptr(ws), nbytes, N, C, H, W, stream_of(z))
-    return y, stats
+    return _planar_bn_fwd("mvs_fpn_bn_leaky_fwd", z, gamma, beta, eps, None, running_mean, running_var, momentum)
 
 
 def fpn_bn_leaky_bwd(d_y: torch.Tensor, z: torch.Tensor, stats: torch.Tensor, gamma: torch.Tensor,
                      beta: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """Backward of fpn_bn_leaky_fwd -> (d_z, d_gamma, d_beta); du = dy (u > 0 ? 1 : 0.1) with u recomputed from z and stats."""
-    z, d_y = _planar32(z), _planar32(d_y)
-    if d_y.shape != z.shape:
-        raise ValueError("d_y must have z's shape %s; got %s" % (tuple(z.shape), tuple(d_y.shape)))
-    N, C, H, W = z.shape
-    L = lib()
-    nbytes = L.mvs_fpn_bn_workspace_bytes(N, C, H, W)
-    ws = _workspace(nbytes, z.device, unbuilt="mvs_fpn_bn_leaky_bwd")
-    d_z = torch.empty_like(z)
-    d_gamma, d_beta = torch.empty(C, dtype=torch.float32, device=z.device), torch.empty(C, dtype=torch.float32, device=z.device)
-    L.mvs_fpn_bn_leaky_bwd(ptr(d_y), ptr(z), ptr(stats), ptr(gamma), ptr(beta), ptr(d_z), ptr(d_gamma), ptr(d_beta), ptr(ws), nbytes,
-                           N, C, H, W, stream_of(z))
-    return d_z, d_gamma, d_beta
+    return _planar_bn_bwd("mvs_fpn_bn_leaky_bwd", d_y, z, stats, gamma, beta)
 
 
 def fpn_enc_wgrad(d_y: torch.Tensor, x: torch.Tensor, k: int, stride: int = 1) -> torch.Tensor:
@@ -293,12 +291,7 @@ def fpn_enc_wgrad(d_y: torch.Tensor, x: torch.Tensor, k: int, stride: int = 1) -
     cout = d_y.shape[1]
     if d_y.shape != (N, cout, (H - 1) // stride + 1, (W - 1) // stride + 1):
         raise ValueError("d_y %s does not belong to x %s at stride %d" % (tuple(d_y.shape), tuple(x.shape), stride))
-    L = lib()
-    nbytes = L.mvs_fpn_enc_wgrad_workspace_bytes(N, cin, cout, int(k), int(stride), H, W)
-    ws = _workspace(nbytes, x.device, unbuilt="mvs_fpn_enc_wgrad (Cout %d, Cin %d, k %d, stride %d)" % (cout, cin, k, stride))
-    d_w = torch.empty(cout, cin, k, k, dtype=torch.float32, device=x.device)
-    L.mvs_fpn_enc_wgrad(ptr(d_y), ptr(x), ptr(d_w), ptr(ws), nbytes, N, cin, cout, int(k), int(stride), H, W, stream_of(x))
-    return d_w
+    return _planar_wgrad("mvs_fpn_enc_wgrad", "stride", int(stride), d_y, x, k, cin)
 
 
 def fpn_enc_dgrad_is_built(cin: int, cout: int, k: int, stride: int) -> bool:

@@ -498,6 +498,11 @@ class AttentionTrain(torch.autograd.Function):
         return (d2 @ w).reshape(B, n, C), d2.t() @ t.reshape(B * n, C), None, None
 
 
+def _gelu_bwd(pre):
+    """d gelu(pre) / d pre of the erf form: Phi(pre) + pre phi(pre)."""
+    return 0.5 * (1.0 + torch.erf(pre * 0.7071067811865476)) + pre * torch.exp(-0.5 * pre * pre) * 0.3989422804014327
+
+
 def _layer_norm_bwd(d_y, u, w, eps):
     """Backward of y = LayerNorm(u) over the last axis (weight w): -> (d_u, d_w, d_b)."""
     mu = u.mean(-1, keepdim=True)
@@ -546,7 +551,7 @@ class TransformerBlockTrain(torch.autograd.Function):
         d_g2 = (d_u2 * y2).sum()
         d_y2 = g2 * d_u2
         d_w2, d_b2 = d_y2.t() @ hdn, d_y2.sum(0)
-        d_pre = (d_y2 @ w2) * (0.5 * (1.0 + torch.erf(pre * 0.7071067811865476)) + pre * torch.exp(-0.5 * pre * pre) * 0.3989422804014327)
+        d_pre = (d_y2 @ w2) * _gelu_bwd(pre)
         d_w1, d_b1 = d_pre.t() @ flat(t1), d_pre.sum(0)
         d_t1 = d_u2 + d_pre @ w1
         # ---- attention half
@@ -610,9 +615,28 @@ def _tokens(x: torch.Tensor) -> torch.Tensor:
     return x.reshape(x.shape[0], 64, -1).transpose(1, 2).reshape(-1, 64)
 
 
-def _elu1_bwd(d_out, pre, out):
-    """Backward of out = elu(pre) + 1: the derivative is 1 above zero and exp(pre) = out below."""
-    return d_out * torch.where(pre > 0, torch.ones_like(out), out)
+def _elu1_bwd(d_out, out):
+    """Backward of out = elu(pre) + 1: the derivative is 1 where out > 1 and exp(pre) = out elsewhere (out = 1 exactly: both give 1)."""
+    return d_out * torch.where(out > 1, torch.ones_like(out), out)
+
+
+def _linattn_fwd(qh, KV, ks):
+    """Linear-attention core: qh [B, l, H, d], KV = sum_s k_s (x) v_s [B, H, d, m], ks = sum_s k_s [B, H, d] -> (Z, num, a = num Z)."""
+    Z = 1.0 / (torch.einsum("blhd,bhd->blh", qh, ks) + 1e-6)
+    num = torch.einsum("blhd,bhdm->blhm", qh, KV)
+    return Z, num, num * Z.unsqueeze(-1)
+
+
+def _linattn_bwd(d_a, qh, kh, vh, KV, ks, Z, num):
+    """Adjoint of _linattn_fwd and of the summaries KV, ks of kh, vh [B, s, H, .]: (d_q, d_k, d_v) on heads."""
+    d_num = d_a * Z.unsqueeze(-1)
+    d_den = -(d_a * num).sum(-1) * Z * Z
+    d_q = torch.einsum("blhm,bhdm->blhd", d_num, KV) + d_den.unsqueeze(-1) * ks.unsqueeze(1)
+    d_KV = torch.einsum("blhd,blhm->bhdm", qh, d_num)
+    d_ks = torch.einsum("blhd,blh->bhd", qh, d_den)
+    d_k = torch.einsum("bhdm,bshm->bshd", d_KV, vh) + d_ks.unsqueeze(1)
+    d_v = torch.einsum("bshd,bhdm->bshm", kh, d_KV)
+    return d_q, d_k, d_v
 
 
 class FmtBlockTrain(torch.autograd.Function):
@@ -657,9 +681,8 @@ class FmtBlockTrain(torch.autograd.Function):
         qh, kh, vh = heads(q, kv_div), heads(k, 1), heads(v, 1)
         KV = torch.einsum("bshd,bshm->bhdm", kh, vh)
         ks = kh.sum(1)
-        Z = 1.0 / (torch.einsum("blhd,bhd->blh", qh, ks) + 1e-6)
-        num = torch.einsum("blhd,bhdm->blhm", qh, KV)
-        a = (num * Z.unsqueeze(-1)).reshape(-1, 64)
+        Z, num, a = _linattn_fwd(qh, KV, ks)
+        a = a.reshape(-1, 64)
         yp = a @ wp.t() + bp
         x1 = x0 + g1 * yp
         # ---- FFN half, forward and backward
@@ -669,22 +692,16 @@ class FmtBlockTrain(torch.autograd.Function):
         y2 = hdn @ w2.t() + b2
         d_g2, d_y2 = (dy * y2).sum(0), dy * g2
         d_w2, d_b2 = d_y2.t() @ hdn, d_y2.sum(0)
-        d_pre = (d_y2 @ w2) * (0.5 * (1.0 + torch.erf(pre * 0.7071067811865476)) + pre * torch.exp(-0.5 * pre * pre) * 0.3989422804014327)
+        d_pre = (d_y2 @ w2) * _gelu_bwd(pre)
         d_w1, d_b1 = d_pre.t() @ u, d_pre.sum(0)
         d_x1n, d_n2w, d_n2b = _layer_norm_bwd(d_pre @ w1, x1, n2w, eps)
         d_x1 = dy + d_x1n
         # ---- attention half
         d_g1, d_yp = (d_x1 * yp).sum(0), d_x1 * g1
         d_wp, d_bp = d_yp.t() @ a, d_yp.sum(0)
-        d_a = heads(d_yp @ wp, kv_div)
-        d_num = d_a * Z.unsqueeze(-1)
-        d_den = -(d_a * num).sum(-1) * Z * Z
-        d_q = torch.einsum("blhm,bhdm->blhd", d_num, KV) + d_den.unsqueeze(-1) * ks.unsqueeze(1)
-        d_KV = torch.einsum("blhd,blhm->bhdm", qh, d_num)
-        d_ks = torch.einsum("blhd,blh->bhd", qh, d_den)
-        d_k = torch.einsum("bhdm,bshm->bshd", d_KV, vh) + d_ks.unsqueeze(1)
-        d_v = torch.einsum("bshd,bhdm->bshm", kh, d_KV).reshape(-1, 64)
-        d_qp, d_kp = _elu1_bwd(d_q.reshape(-1, 64), qp, q), _elu1_bwd(d_k.reshape(-1, 64), kp, k)
+        d_q, d_k, d_v = _linattn_bwd(heads(d_yp @ wp, kv_div), qh, kh, vh, KV, ks, Z, num)
+        d_v = d_v.reshape(-1, 64)
+        d_qp, d_kp = _elu1_bwd(d_q.reshape(-1, 64), q), _elu1_bwd(d_k.reshape(-1, 64), k)
         d_wq, d_wk, d_wv = d_qp.t() @ xn, d_kp.t() @ kvn, d_v.t() @ kvn
         d_xn, d_kvn = d_qp @ wq, d_kp @ wk + d_v @ wv
         d_ref = None
@@ -771,20 +788,32 @@ def fmt_forward_train(module, features: Dict[str, torch.Tensor]) -> Dict[str, to
 # --------------------------------------------------------------------------------------------------
 # FPNDecoder (features.py): where fmt_forward_train's input gradients go
 # --------------------------------------------------------------------------------------------------
+def _require_single_process(what):
+    if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
+        raise NotImplementedError("%s: batch statistics are per process; SyncBatchNorm / multi-GPU training of the feature side is not built"
+                                  % what)
+
+
+def _bn_train_step(bn, what):
+    """One train-mode BatchNorm2d call of module `what`: checks the running buffers, num_batches_tracked + 1 -> (mean, var, momentum)."""
+    rm, rv = bn.running_mean, bn.running_var
+    if rm is None:
+        return None, None, 0.0
+    if rm.dtype != torch.float32 or not rm.is_contiguous() or not rv.is_contiguous():
+        raise NotImplementedError("%s training: BatchNorm running statistics must be contiguous fp32 buffers" % what)
+    with torch.no_grad():
+        bn.num_batches_tracked += 1
+    return rm, rv, float(bn.momentum) if bn.momentum is not None else 1.0 / float(bn.num_batches_tracked)
+
+
 def _fpn_bn_swish(z, bn, conv_bias, gamma, beta):
     """Train-mode BatchNorm2d + Swish of the pre-activation z = conv(x) WITHOUT its bias: batch statistics (the bias cancels in
     z - mean), one momentum step of the running statistics with mean + bias and the unbiased variance, num_batches_tracked + 1."""
-    rm, rv, momentum = bn.running_mean, bn.running_var, 0.0
-    if rm is not None:
-        if rm.dtype != torch.float32 or not rm.is_contiguous() or not rv.is_contiguous():
-            raise NotImplementedError("FPNDecoder training: BatchNorm running statistics must be contiguous fp32 buffers")
-        with torch.no_grad():
-            bn.num_batches_tracked += 1
-        momentum = float(bn.momentum) if bn.momentum is not None else 1.0 / float(bn.num_batches_tracked)
+    rm, rv, momentum = _bn_train_step(bn, "FPNDecoder")
     return ops.fpn_bn_swish_fwd(z, gamma, beta, bn.eps, conv_bias if rm is not None else None, rm, rv, momentum)
 
 
-def _fpn_vec(p):
+def _vec32(p):
     return p.detach().float().contiguous()
 
 
@@ -797,10 +826,10 @@ class FpnHeadTrain(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, bn, w, b, gamma, beta):
-        x0, w32, g, bt = ops._f32c(x.detach()), w.detach().float(), _fpn_vec(gamma), _fpn_vec(beta)
+        x0, w32, g, bt = ops._f32c(x.detach()), w.detach().float(), _vec32(gamma), _vec32(beta)
         k = w32.shape[2]
         z = ops.fpn_conv(x0, packing.pack_fpn_conv_weights(w32, 1), None, w32.shape[0], k, 1, ops.FPN_ACT_NONE)
-        y, stats = _fpn_bn_swish(z, bn, _fpn_vec(b), g, bt)
+        y, stats = _fpn_bn_swish(z, bn, _vec32(b), g, bt)
         ctx.save_for_backward(x0, z, stats, w32, g, bt)
         ctx.b_like = (b.shape, b.dtype)
         return y
@@ -826,7 +855,7 @@ class FpnMergeTrain(torch.autograd.Function):
         wi2 = wi.detach().float().reshape(wi.shape[0], -1).contiguous()
         ctx.save_for_backward(l, wi2)
         ctx.wi_shape = wi.shape
-        return ops.fpn_merge(ops._f32c(prev.detach()), l, wi2, _fpn_vec(bi))
+        return ops.fpn_merge(ops._f32c(prev.detach()), l, wi2, _vec32(bi))
 
     @staticmethod
     @once_differentiable
@@ -853,10 +882,10 @@ class FpnLevel3Train(torch.autograd.Function):
     @staticmethod
     def forward(ctx, prev, lat, bn, wi, bi, w, b, gamma, beta):
         p, l = ops._f32c(prev.detach()), ops._f32c(lat.detach())
-        wi2, bi1 = wi.detach().float().reshape(64, 8).contiguous(), _fpn_vec(bi)
-        w32, g, bt = w.detach().float(), _fpn_vec(gamma), _fpn_vec(beta)
+        wi2, bi1 = wi.detach().float().reshape(64, 8).contiguous(), _vec32(bi)
+        w32, g, bt = w.detach().float(), _vec32(gamma), _vec32(beta)
         z = ops.fpn_merge_conv(p, l, wi2, bi1, packing.pack_fpn_conv_weights(w32, 1), None, 8, ops.FPN_ACT_NONE)
-        y, stats = _fpn_bn_swish(z, bn, _fpn_vec(b), g, bt)
+        y, stats = _fpn_bn_swish(z, bn, _vec32(b), g, bt)
         ctx.save_for_backward(p, l, z, stats, wi2, bi1, w32, g, bt)
         ctx.like = (wi.shape, b.shape, b.dtype)
         return y
@@ -895,9 +924,7 @@ def fpn_decoder_forward_train(module, conv01, conv11, conv21, conv31):
     ``out_k.0.bias`` sit in front of a batch-statistics BatchNorm, so their true gradient is exactly zero and an exact zero tensor is
     returned for them.  No double backward.  Single process only: with torch.distributed initialised on more than one rank this
     raises (SyncBatchNorm on the feature side is not built)."""
-    if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
-        raise NotImplementedError("fpn_decoder_forward_train: batch statistics are per process; SyncBatchNorm / multi-GPU training of the "
-                                  "feature side is not built")
+    _require_single_process("fpn_decoder_forward_train")
     module._check_inputs(conv01, conv11, conv21, conv31)
     c01, c11, c21, c31 = (t.float() for t in (conv01, conv11, conv21, conv31))
     head = lambda k, x: FpnHeadTrain.apply(x, getattr(module, "out%d" % k)[1], getattr(module, "out%d" % k)[0].weight,
@@ -925,16 +952,10 @@ class FpnEncBlockTrain(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, bn, w, gamma, beta, stride):
-        x0, w32, g, bt = ops._f32c(x.detach()), w.detach().float().contiguous(), _fpn_vec(gamma), _fpn_vec(beta)
+        x0, w32, g, bt = ops._f32c(x.detach()), w.detach().float().contiguous(), _vec32(gamma), _vec32(beta)
         k = w32.shape[2]
         z = ops.fpn_conv(x0, packing.pack_fpn_conv_weights(w32, stride), None, w32.shape[0], k, stride, ops.FPN_ACT_NONE)
-        rm, rv, momentum = bn.running_mean, bn.running_var, 0.0
-        if rm is not None:
-            if rm.dtype != torch.float32 or not rm.is_contiguous() or not rv.is_contiguous():
-                raise NotImplementedError("FPNEncoder training: BatchNorm running statistics must be contiguous fp32 buffers")
-            with torch.no_grad():
-                bn.num_batches_tracked += 1
-            momentum = float(bn.momentum) if bn.momentum is not None else 1.0 / float(bn.num_batches_tracked)
+        rm, rv, momentum = _bn_train_step(bn, "FPNEncoder")
         y, stats = ops.fpn_bn_leaky_fwd(z, g, bt, bn.eps, rm, rv, momentum)
         ctx.save_for_backward(x0, z, stats, w32, g, bt)
         ctx.stride = stride
@@ -959,9 +980,7 @@ def fpn_encoder_forward_train(module, x):
     and by the decoder) has its gradients summed by autograd.  Gradients reach all 33 parameters.  The image's gradient is not built: an x
     that requires grad raises; bf16 / fp16 images are widened once.  No double backward.  Single process only: with torch.distributed
     initialised on more than one rank this raises (SyncBatchNorm on the feature side is not built)."""
-    if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
-        raise NotImplementedError("fpn_encoder_forward_train: batch statistics are per process; SyncBatchNorm / multi-GPU training of the "
-                                  "feature side is not built")
+    _require_single_process("fpn_encoder_forward_train")
     if x.dim() != 4 or x.shape[1] != 3:
         raise ValueError("FPNEncoder takes images [N, 3, H, W]; got %s" % (tuple(x.shape),))
     H, W = x.shape[-2:]
@@ -1042,9 +1061,8 @@ class VitdecBlockTrain(torch.autograd.Function):
         qh, kh, vh = heads(q, kv_div), heads(k, 1), heads(v, 1)
         summary = ops.vitdec_kv(kv, Nr, n)
         KV, ks = summary[:, :, :4096].reshape(Nr, 12, 64, 64), summary[:, :, 4096:]
-        Z = 1.0 / (torch.einsum("blhd,bhd->blh", qh, ks) + 1e-6)
-        num = torch.einsum("blhd,bhdm->blhm", qh, KV)
-        a = (num * Z.unsqueeze(-1)).reshape(M, 768)
+        Z, num, a = _linattn_fwd(qh, KV, ks)
+        a = a.reshape(M, 768)
         yp = ops.vitdec_linear(ops.vitdec_pack(a), M, pb["proj"], 768, 768, F32, bias=bp)
         x1 = x0 + g1 * yp
         # ---- FFN half, forward and backward
@@ -1055,24 +1073,15 @@ class VitdecBlockTrain(torch.autograd.Function):
         y2 = ops.vitdec_linear(ops.vitdec_pack(hdn), M, pb["fc2"], 3072, 768, F32, bias=b2)
         d_g2, d_y2 = (dy * y2).sum(0), dy * g2
         d_w2, d_b2 = ops.vitdec_wgrad(d_y2, hdn, want_bias=True)
-        d_pre = ops.vitdec_dgrad(d_y2, pb["fc2T"], 3072) * \
-            (0.5 * (1.0 + torch.erf(pre * 0.7071067811865476)) + pre * torch.exp(-0.5 * pre * pre) * 0.3989422804014327)
+        d_pre = ops.vitdec_dgrad(d_y2, pb["fc2T"], 3072) * _gelu_bwd(pre)
         d_w1, d_b1 = ops.vitdec_wgrad(d_pre, u, want_bias=True)
         d_x1, d_n2w, d_n2b = ops.vitdec_ln_bwd(ops.vitdec_dgrad(d_pre, pb["fc1T"], 768), x1, n2w, eps, add=dy)
         # ---- attention half
         d_g1, d_yp = (d_x1 * yp).sum(0), d_x1 * g1
         d_wp, d_bp = ops.vitdec_wgrad(d_yp, a, want_bias=True)
-        d_a = heads(ops.vitdec_dgrad(d_yp, pb["projT"], 768), kv_div)
-        d_num = d_a * Z.unsqueeze(-1)
-        d_den = -(d_a * num).sum(-1) * Z * Z
-        d_q = torch.einsum("blhm,bhdm->blhd", d_num, KV) + d_den.unsqueeze(-1) * ks.unsqueeze(1)
-        d_KV = torch.einsum("blhd,blhm->bhdm", qh, d_num)
-        d_ks = torch.einsum("blhd,blh->bhd", qh, d_den)
-        d_k = torch.einsum("bhdm,bshm->bshd", d_KV, vh) + d_ks.unsqueeze(1)
-        d_v = torch.einsum("bshd,bhdm->bshm", kh, d_KV)
-        # out = elu(pre) + 1: the derivative is 1 where out > 1 and exp(pre) = out elsewhere
-        d_qp = d_q.reshape(M, 768) * torch.where(q > 1, torch.ones_like(q), q)
-        d_kpv = torch.cat([d_k.reshape(Mk, 768) * torch.where(k > 1, torch.ones_like(k), k), d_v.reshape(Mk, 768)], 1)
+        d_q, d_k, d_v = _linattn_bwd(heads(ops.vitdec_dgrad(d_yp, pb["projT"], 768), kv_div), qh, kh, vh, KV, ks, Z, num)
+        d_qp = _elu1_bwd(d_q.reshape(M, 768), q)
+        d_kpv = torch.cat([_elu1_bwd(d_k.reshape(Mk, 768), k), d_v.reshape(Mk, 768)], 1)
         d_wq = ops.vitdec_wgrad(d_qp, xn)
         d_wkv = ops.vitdec_wgrad(d_kpv, kvn.contiguous())
         # the data gradients into norm1: always needed for d_norm1 (and d_x) on the query side; on the key side only where the keys are
@@ -1097,7 +1106,7 @@ class VitdecMixTrain(torch.autograd.Function):
     def forward(ctx, prev, x_i, prev_value, mix_w, mix_b):
         N, n = prev.shape[:2]
         p0 = ops._f32c(prev.detach()).reshape(N * n, 768)
-        pv, w, b = prev_value.detach().float().reshape(1), _fpn_vec(mix_w), _fpn_vec(mix_b)
+        pv, w, b = prev_value.detach().float().reshape(1), _vec32(mix_w), _vec32(mix_b)
         y = ops.vitdec_rows(x_i, 0, x_i.shape[1], prev=p0, prev_value=pv, mix=(w, b))[0]
         ctx.save_for_backward(p0, x_i, pv, w)
         ctx.pv_shape = prev_value.shape
@@ -1123,9 +1132,7 @@ def vitdec_forward_train(module, x, vit_shape):
     form is not built yet.  The backbone is frozen (the reference runs it under torch.no_grad()): an input that requires grad raises.
     V = 1 runs no cross block, so their parameters get no gradient.  No double backward.  Single process only: with torch.distributed
     initialised on more than one rank this raises (the BatchNorm statistics are per process)."""
-    if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
-        raise NotImplementedError("vitdec_forward_train: batch statistics are per process; SyncBatchNorm / multi-GPU training of the "
-                                  "feature side is not built")
+    _require_single_process("vitdec_forward_train")
     B, V, h, w = module._check_shapes(x, None, vit_shape)
     if torch.is_grad_enabled() and any(t.requires_grad for t in x):
         raise NotImplementedError("vitdec_forward_train: the gradient into the ViT features is not built (the DINOv2 backbone is frozen and "
