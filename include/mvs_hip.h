@@ -715,6 +715,39 @@ mvs_status mvs_vitdec_ln_bwd(const float* d_y, const float* x, const float* w, f
                              size_t workspace_bytes, long long M, int channels, void* stream);
 mvs_status mvs_vitdec_pack_fwd(const float* x, void* x_packed, long long M, int channels, void* stream);
 
+/* ---- training of the CrossVITDecoder's head -----------------------------------------------------------
+ * layer 0 = proj (Conv2d 768 -> 256, 3x3, padding 1), 1 / 2 = upsampler0 / 1 (ConvTranspose2d 256 -> 128 / 128 -> 64, 4x4, stride 2,
+ * padding 1), each followed by batch-statistics BatchNorm2d and SiLU.  Maps are token-major: row = (view * H + y) * W + x, fp32
+ * [rows, C] or packed-split (mvs_vitdec_packed_bytes).  [NV, H, W] is always the layer's INPUT map; a transposed convolution's output
+ * has 4 NV H W rows in fine-map order, view * 4 H W + (2 y + py) * 2 W + 2 x + px.  Three-term split-bf16 products, fp32 accumulation,
+ * k ascending; no atomics: the same bits from run to run and on any stream.
+ * mvs_vitdec_head_conv_fwd: the pre-activation z fp32 [output rows, Cout] = the convolution with raw weights and NO bias (it cancels in
+ *   the batch statistics).  w_packed = packing.pack_vitdec_conv / pack_vitdec_deconv of the weight with an identity BatchNorm.
+ * mvs_vitdec_head_dgrad: d_x fp32 [NV H W, Cin] from the packed-split d_z of the output map.  Layer 0: the 3x3 window on the flipped,
+ *   channel-transposed taps, wt_packed = pack_linear_bf16x3 of [768, 9 x 256]; layers 1 / 2: the 4x4 stride-2 window of the fine map,
+ *   input token (y, x) reads (2 y - 1 + ky, 2 x - 1 + kx), wt_packed = pack_linear_bf16x3 of [Cin, 16 Cout], column (4 ky + kx) Cout + co.
+ * mvs_vitdec_head_wgrad: d_z fp32 rows of the output map, x fp32 [NV H W, Cin] -> dw fp32; layer 0: [256, 9 x 768], column
+ *   (3 ky + kx) 768 + c; layers 1 / 2: [16 Cout, Cin], row (4 ky + kx) Cout + co.  Token slabs as mvs_vitdec_wgrad's, partials in
+ *   `workspace` (mvs_vitdec_head_wgrad_workspace_bytes = slabs * rows * columns floats) added in slab order.
+ * mvs_vitdec_head_bn_fwd: z fp32 [M, channels] (256 | 128 | 64) -> stats [3, channels] = mean | biased variance | invstd (fp64 sums,
+ *   fixed order) and SiLU(gamma xhat + beta) as y fp32 [M, channels] and / or y_packed (both nullable), or as y_planar fp32
+ *   [M / pixels_per_view, channels, pixels_per_view] alone.  running_mean / running_var (nullable) take one step of `momentum` with
+ *   mean + conv_bias and the unbiased variance, on the device.
+ * mvs_vitdec_head_bn_bwd: d_y (fp32 [M, channels], or planar with d_y_planar = 1), z, stats, gamma, beta -> d_z fp32 and / or
+ *   d_z_packed (nullable, not both null), d_gb [2, channels] = d_gamma | d_beta.  workspace: mvs_vitdec_head_bn_workspace_bytes.      */
+mvs_status mvs_vitdec_head_conv_fwd(const void* x_packed, const void* w_packed, float* z, int layer, int NV, int H, int W, void* stream);
+mvs_status mvs_vitdec_head_dgrad(const void* dz_packed, const void* wt_packed, float* d_x, int layer, int NV, int H, int W, void* stream);
+size_t mvs_vitdec_head_wgrad_workspace_bytes(int layer, int NV, int H, int W);
+mvs_status mvs_vitdec_head_wgrad(const float* d_z, const float* x, float* dw, void* workspace, size_t workspace_bytes, int layer, int NV, int H,
+                                 int W, void* stream);
+size_t mvs_vitdec_head_bn_workspace_bytes(long long M, int channels);
+mvs_status mvs_vitdec_head_bn_fwd(const float* z, const float* conv_bias, const float* gamma, const float* beta, float eps, float momentum,
+                                  float* running_mean, float* running_var, float* stats, float* y, void* y_packed, float* y_planar,
+                                  void* workspace, size_t workspace_bytes, long long M, int channels, int pixels_per_view, void* stream);
+mvs_status mvs_vitdec_head_bn_bwd(const float* d_y, int d_y_planar, const float* z, const float* stats, const float* gamma, const float* beta,
+                                  float* d_z, void* d_z_packed, float* d_gb, void* workspace, size_t workspace_bytes, long long M, int channels,
+                                  int pixels_per_view, void* stream);
+
 /* ==== DINOv2 ViT-B/14 backbone: forward_interval_features ==============================================
  * models/dino/dinov2.py vit_base(patch_size=14) with the shipped dino_cfg: 14 x 14 patch embedding + interpolated position embedding,
  * pre-norm blocks (LayerNorm eps 1e-6, qkv with bias, softmax attention over the n + 1 tokens of a view with 12 heads of 64, LayerScale,

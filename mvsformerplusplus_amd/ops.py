@@ -662,6 +662,136 @@ def vitdec_dgrad(dy: torch.Tensor, wt_packed: torch.Tensor, N_in: int, bias: Opt
     return vitdec_linear(vitdec_pack(dy), dy.shape[0], wt_packed, dy.shape[1], N_in, VITDEC_EPI_F32, bias=bias)
 
 
+# ---- training of the CrossVITDecoder's head (csrc/vitdec_head_train_kernels.hip) ----
+# [NV, H, W] is always the layer's INPUT map; the output map of VITDEC_UP0 / UP1 has 4 NV H W rows in fine-map order.
+def _vitdec_head_rows(layer: int, NV: int, H: int, W: int) -> Tuple[int, int]:
+    """(rows of the layer's input map, rows of its output map)"""
+    if layer not in _VITDEC_CONV:
+        return 1, 1                                                    # the library refuses the layer
+    M = NV * H * W
+    return M, M if layer == VITDEC_PROJ else 4 * M
+
+
+def vitdec_head_conv(x_packed: torch.Tensor, w_packed: torch.Tensor, layer: int, NV: int, H: int, W: int) -> torch.Tensor:
+    """Pre-activation of a head layer in train mode: the convolution of the packed-split tokens of the [NV, H, W] map with the RAW weights
+    and no bias -> fp32 [output rows, Cout], token-major.  w_packed = packing.pack_vitdec_head_train(...)["w"]."""
+    M, Mo = _vitdec_head_rows(layer, NV, H, W)
+    cout = 1
+    if layer in _VITDEC_CONV:
+        cin, cout, taps, classes = _VITDEC_CONV[layer]
+        _vitdec_packed(x_packed, M, cin, "x_packed")
+        want = classes * taps * cin * ((cout + 127) // 128 * 128) * 2
+        if w_packed.dtype != torch.bfloat16 or w_packed.numel() != want or not w_packed.is_contiguous():
+            raise ValueError("w_packed must hold %d bf16 elements (packing.pack_vitdec_head_train); got %s %d" % (want, w_packed.dtype, w_packed.numel()))
+    z = torch.empty(Mo, cout, dtype=torch.float32, device=x_packed.device)
+    lib().mvs_vitdec_head_conv_fwd(ptr(x_packed), ptr(w_packed), ptr(z), int(layer), NV, H, W, stream_of(x_packed))
+    return z
+
+
+def vitdec_head_dgrad(dz_packed: torch.Tensor, wt_packed: torch.Tensor, layer: int, NV: int, H: int, W: int) -> torch.Tensor:
+    """Data gradient of a head layer: the packed-split d_z of the layer's output map -> fp32 [NV H W, Cin].  wt_packed =
+    packing.pack_vitdec_head_train(...)["wT"] (proj: flipped, channel-transposed taps; upsamplers: the 4x4 stride-2 window)."""
+    M, Mo = _vitdec_head_rows(layer, NV, H, W)
+    cin = 1
+    if layer in _VITDEC_CONV:
+        cin, cout = _VITDEC_CONV[layer][:2]
+        _vitdec_packed(dz_packed, Mo, cout, "dz_packed")
+        want = (9 if layer == VITDEC_PROJ else 16) * cout * cin * 2
+        if wt_packed.dtype != torch.bfloat16 or wt_packed.numel() != want or not wt_packed.is_contiguous():
+            raise ValueError("wt_packed must hold %d bf16 elements (packing.pack_vitdec_head_train); got %s %d" % (want, wt_packed.dtype, wt_packed.numel()))
+    d_x = torch.empty(M, cin, dtype=torch.float32, device=dz_packed.device)
+    lib().mvs_vitdec_head_dgrad(ptr(dz_packed), ptr(wt_packed), ptr(d_x), int(layer), NV, H, W, stream_of(dz_packed))
+    return d_x
+
+
+def vitdec_head_wgrad_slabs(layer: int, NV: int, H: int, W: int) -> int:
+    """Token slabs of vitdec_head_wgrad's launch; 0 = not built (read off the workspace size, as vitdec_wgrad_slabs)."""
+    if layer not in _VITDEC_CONV:
+        return 0
+    cin, cout = _VITDEC_CONV[layer][:2]
+    return lib().mvs_vitdec_head_wgrad_workspace_bytes(int(layer), NV, H, W) // ((9 if layer == VITDEC_PROJ else 16) * cin * cout * 4)
+
+
+def vitdec_head_wgrad(d_z: torch.Tensor, x: torch.Tensor, layer: int, NV: int, H: int, W: int) -> torch.Tensor:
+    """Weight gradient of a head layer in the nn layout: d_z fp32 [output rows, Cout], x fp32 [NV H W, Cin] -> proj [256, 768, 3, 3],
+    upsamplers [Cin, Cout, 4, 4].  Per-slab partials added in slab order: no atomics."""
+    M, Mo = _vitdec_head_rows(layer, NV, H, W)
+    cin, cout = _VITDEC_CONV[layer][:2] if layer in _VITDEC_CONV else (None, None)
+    _vitdec_tokens(d_z, cout, "d_z")
+    _vitdec_tokens(x, cin, "x")
+    if layer in _VITDEC_CONV and (d_z.shape[0] != Mo or x.shape[0] != M or x.device != d_z.device):
+        raise ValueError("d_z %s and x %s must have %d and %d rows on one device" % (tuple(d_z.shape), tuple(x.shape), Mo, M))
+    L = lib()
+    ws_bytes = L.mvs_vitdec_head_wgrad_workspace_bytes(int(layer), NV, H, W) if layer in _VITDEC_CONV else 0
+    ws = _workspace(ws_bytes, d_z.device)
+    if layer == VITDEC_PROJ:
+        dw = torch.empty(256, 9 * 768, dtype=torch.float32, device=d_z.device)
+    else:
+        dw = torch.empty(16 * (cout or 1), cin or 1, dtype=torch.float32, device=d_z.device)
+    L.mvs_vitdec_head_wgrad(ptr(d_z), ptr(x), ptr(dw), ptr(ws), ws_bytes, int(layer), NV, H, W, stream_of(d_z))
+    if layer == VITDEC_PROJ:
+        return dw.view(256, 3, 3, 768).permute(0, 3, 1, 2).contiguous()
+    return dw.view(4, 4, cout, cin).permute(3, 2, 0, 1).contiguous()
+
+
+def vitdec_head_bn_fwd(z: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float, conv_bias: Optional[torch.Tensor] = None,
+                       running_mean: Optional[torch.Tensor] = None, running_var: Optional[torch.Tensor] = None, momentum: float = 0.0, *,
+                       want_y: bool = True, want_packed: bool = False, planar: Optional[Tuple[int, int, int]] = None):
+    """Batch-statistics BatchNorm + SiLU of token-major z fp32 [M, C] (C = 256 | 128 | 64) -> (y, y_packed, stats [3, C] = mean | biased
+    variance | invstd).  y is fp32 [M, C] (want_y) and / or packed-split (want_packed); with planar = (NV, H, W), M = NV H W, y is the
+    planar fp32 [NV, C, H, W] alone.  running_mean / running_var (updated in place, on the device) take one step of `momentum` with
+    mean + conv_bias and the unbiased variance.  Sums in fp64, fixed order."""
+    _vitdec_tokens(z, None, "z")
+    M, C = z.shape
+    for t, what in ((gamma, "gamma"), (beta, "beta")):
+        _vitdec_vec(t, C, what, z)
+    for t, what in ((conv_bias, "conv_bias"), (running_mean, "running_mean"), (running_var, "running_var")):
+        if t is not None:
+            _vitdec_vec(t, C, what, z)
+    L = lib()
+    nbytes = L.mvs_vitdec_head_bn_workspace_bytes(M, C)
+    ws = _workspace(nbytes, z.device, unbuilt="mvs_vitdec_head_bn_fwd (rows of %d channels)" % C)
+    stats = torch.empty(3, C, dtype=torch.float32, device=z.device)
+    y = yp = ypl = None
+    pixels = 1
+    if planar is not None:
+        NV, H, W = planar
+        if NV * H * W != M:
+            raise ValueError("planar = (NV, H, W) must have NV H W = %d rows; got %s" % (M, planar))
+        ypl = torch.empty(NV, C, H, W, dtype=torch.float32, device=z.device)
+        pixels = H * W
+    else:
+        y = torch.empty_like(z) if want_y else None
+        yp = torch.empty(L.mvs_vitdec_packed_bytes(M, C), dtype=torch.uint8, device=z.device) if want_packed else None
+    L.mvs_vitdec_head_bn_fwd(ptr(z), ptr(conv_bias), ptr(gamma), ptr(beta), float(eps), float(momentum), ptr(running_mean), ptr(running_var),
+                             ptr(stats), ptr(y), ptr(yp), ptr(ypl), ptr(ws), nbytes, M, C, pixels, stream_of(z))
+    return (ypl if planar is not None else y), yp, stats
+
+
+def vitdec_head_bn_bwd(d_y: torch.Tensor, z: torch.Tensor, stats: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor):
+    """Backward of vitdec_head_bn_fwd: d_y fp32 [M, C] token-major, or the planar [NV, C, H, W] cotangent of the planar form ->
+    (d_z fp32 [M, C], d_z packed-split, d_gamma, d_beta)."""
+    _vitdec_tokens(z, None, "z")
+    M, C = z.shape
+    planar = d_y.dim() == 4
+    if d_y.dtype != torch.float32 or not d_y.is_contiguous() or d_y.device != z.device or \
+            (planar and (d_y.shape[1] != C or d_y.shape[0] * d_y.shape[2] * d_y.shape[3] != M)) or (not planar and d_y.shape != z.shape):
+        raise ValueError("d_y must be contiguous fp32 %s or planar [NV, %d, H, W] with NV H W = %d; got %s %s" % (tuple(z.shape), C, M, d_y.dtype, tuple(d_y.shape)))
+    if stats.dtype != torch.float32 or tuple(stats.shape) != (3, C) or not stats.is_contiguous():
+        raise ValueError("stats must be vitdec_head_bn_fwd's fp32 [3, %d]" % C)
+    _vitdec_vec(gamma, C, "gamma", z)
+    _vitdec_vec(beta, C, "beta", z)
+    L = lib()
+    nbytes = L.mvs_vitdec_head_bn_workspace_bytes(M, C)
+    ws = _workspace(nbytes, z.device, unbuilt="mvs_vitdec_head_bn_bwd (rows of %d channels)" % C)
+    d_z = torch.empty_like(z)
+    d_zp = torch.empty(L.mvs_vitdec_packed_bytes(M, C), dtype=torch.uint8, device=z.device)
+    d_gb = torch.empty(2, C, dtype=torch.float32, device=z.device)
+    L.mvs_vitdec_head_bn_bwd(ptr(d_y), int(planar), ptr(z), ptr(stats), ptr(gamma), ptr(beta), ptr(d_z), ptr(d_zp), ptr(d_gb), ptr(ws), nbytes,
+                             M, C, d_y.shape[2] * d_y.shape[3] if planar else 1, stream_of(z))
+    return d_z, d_zp, d_gb[0], d_gb[1]
+
+
 VIT_KEY_STEP = 32          # the attention core's key step: every view's rows are padded to a multiple of it
 VIT_KPAD = 640             # the patch embedding's K = 588 padded to the GEMM's chunk
 

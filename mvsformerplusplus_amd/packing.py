@@ -374,6 +374,46 @@ def pack_vitdec_deconv(w: torch.Tensor, b: torch.Tensor, bn: Dict[str, torch.Ten
     return torch.cat(chunks), bf.contiguous()
 
 
+VITDEC_HEAD = ("proj", "upsampler0", "upsampler1")
+
+
+def pack_vitdec_head_train(sd: Dict[str, torch.Tensor], transposed: bool = True, forward: bool = True) -> Dict[str, Dict[str, torch.Tensor]]:
+    """The head's convolution weights for a training step (keys relative to the decoder: "proj.0.weight",
+    "upsampler0.0.weight", "upsampler1.0.weight", any subset), packed WHERE THE PARAMETERS LIVE from the values they hold now (plain
+    tensor ops, never cached) -> per layer {"w": the forward operand, the bits pack_vitdec_conv / pack_vitdec_deconv give for an
+    identity BatchNorm} and, with `transposed`, "wT": the data gradient's.  proj's "wT" is pack_linear_bf16x3 of [768, 9 x 256] with
+    column (3 ky + kx) 256 + co = w[co][c][2 - ky][2 - kx] (flipped, channel-transposed taps); an upsampler's is pack_linear_bf16x3 of
+    [Cin, 16 Cout] with column (4 ky + kx) Cout + co = w[c][co][ky][kx]: input token (y, x) reads the fine map at (2 y - 1 + ky,
+    2 x - 1 + kx)."""
+    out = {}
+    for name in VITDEC_HEAD:
+        if name + ".0.weight" not in sd:
+            continue
+        w = sd[name + ".0.weight"].detach().float()
+        if name == "proj":
+            cout, cin = w.shape[:2]
+            assert cout % 128 == 0 and cin % 128 == 0 and tuple(w.shape[2:]) == (3, 3), tuple(w.shape)
+            out[name] = {"w": pack_linear_bf16x3(w.permute(0, 2, 3, 1).reshape(cout, 9 * cin))} if forward else {}
+            if transposed:
+                out[name]["wT"] = pack_linear_bf16x3(w.flip(2, 3).permute(1, 2, 3, 0).reshape(cin, 9 * cout))
+            continue
+        cin, cout = w.shape[:2]
+        assert cin % 128 == 0 and cout % 64 == 0 and tuple(w.shape[2:]) == (4, 4), tuple(w.shape)
+        npad = (cout + 127) // 128 * 128
+        chunks = []
+        for cls in range(4 if forward else 0):
+            py, px = cls >> 1, cls & 1
+            m = w.new_zeros(npad, 4, cin)
+            for ay in range(2):
+                for ax in range(2):
+                    m[:cout, 2 * ay + ax] = w[:, :, 1 - py + 2 * ay, 1 - px + 2 * ax].t()
+            chunks.append(pack_linear_bf16x3(m.reshape(npad, 4 * cin)))
+        out[name] = {"w": torch.cat(chunks)} if forward else {}
+        if transposed:
+            out[name]["wT"] = pack_linear_bf16x3(w.permute(0, 2, 3, 1).reshape(cin, 16 * cout))
+    return out
+
+
 # ---- DINOv2 ViT-B/14 backbone (csrc/vitdec_kernels.hip, csrc/vit_attention_kernels.hip, DESIGN.md section 4.13) ----------------------
 VIT_VECTORS = ("norm1.weight", "norm1.bias", "attn.qkv.bias", "attn.proj.bias", "ls1.gamma", "norm2.weight", "norm2.bias", "mlp.fc1.bias",
                "mlp.fc2.bias", "ls2.gamma")

@@ -43,7 +43,8 @@ lateral, ``mvs_fmt_path_bwd`` - the interpolation's exact adjoint as a gather - 
 go on into ``fpn_decoder_forward_train``, the train-mode FPNDecoder: planar batch-statistics BatchNorm + Swish,
 weight gradients on fp32 MFMA, the upsample's adjoint as a gather, the last level fused so that its 64-channel full-resolution map is
 never written in either direction.  The FPN encoder trains in ``fpn_encoder_forward_train`` (section 4.19) and the ViT decoder in
-``vitdec_forward_train`` (section 4.20: block backward native, head on PyTorch ops); the ViT backbone is frozen and has no training form.
+``vitdec_forward_train`` (section 4.20: block backward native, head on PyTorch ops or, with ``native_head``, on ``vitdec_head_train``,
+section 4.21); the ViT backbone is frozen and has no training form.
 """
 from __future__ import annotations
 
@@ -1128,8 +1129,8 @@ def vitdec_forward_train(module, x, vit_shape):
     steps are ``VitdecMixTrain`` nodes; ref_feat_list[i] collects its gradient from the next self block, the cross block of level i and,
     for the last level, the output tokens - autograd sums them, as it sums the gradients of prev_values / norm_layers, which the
     reference path and the source path share.  The head (proj, upsampler0, upsampler1) runs on the module's own nn.Sequential layers in
-    train mode: PyTorch ops with batch-statistics BatchNorm over all B V views, exactly what the reference runs; its native train-mode
-    form is not built yet.  The backbone is frozen (the reference runs it under torch.no_grad()): an input that requires grad raises.
+    train mode: PyTorch ops with batch-statistics BatchNorm over all B V views, exactly what the reference runs; with
+    ``module.native_head`` it runs on the library's kernels instead (``vitdec_head_train``).  The backbone is frozen (the reference runs it under torch.no_grad()): an input that requires grad raises.
     V = 1 runs no cross block, so their parameters get no gradient.  No double backward.  Single process only: with torch.distributed
     initialised on more than one rank this raises (the BatchNorm statistics are per process)."""
     _require_single_process("vitdec_forward_train")
@@ -1155,8 +1156,70 @@ def vitdec_forward_train(module, x, vit_shape):
             q = xs[0][:, 1:].float().reshape(B * S, n, 768) if i == 0 else VitdecMixTrain.apply(y, xs[i][:, 1:], *mix(i))
             y = VitdecBlockTrain.apply(q, refs[i], S, *params(blk))
         views.append(y.reshape(B, S, n, 768))
-    tokens = torch.cat(views, 1).reshape(B * V, h, w, 768).permute(0, 3, 1, 2)
-    return module.upsampler1(module.upsampler0(module.proj(tokens)))
+    tokens = torch.cat(views, 1)
+    if getattr(module, "native_head", False):
+        return vitdec_head_train(module, tokens.reshape(B * V * n, 768), B * V, h, w)     # token-major through the head: no permute
+    return module.upsampler1(module.upsampler0(module.proj(tokens.reshape(B * V, h, w, 768).permute(0, 3, 1, 2))))
+
+
+class VitdecHeadLayerTrain(torch.autograd.Function):
+    """One layer of the CrossVITDecoder's head in train mode (module.py:316-321): SiLU(BatchNorm2d(conv(x) + b))
+    with batch statistics, conv = proj (layer 0: Conv2d 768 -> 256, 3x3) or upsampler0 / 1 (layers 1 / 2: ConvTranspose2d 4x4 stride 2),
+    on the token-major map x fp32 [NV H W, Cin] (x_packed = its packed-split form, or None: packed here).  Returns (y, y_packed): fp32
+    [output rows, Cout] and its packed-split form, the next layer's operand; with `last`, (planar fp32 [NV, Cout, 2 H, 2 W], None).
+    Weights are packed on the device from the live parameter at every call.  Kept: x, the pre-activation z, the statistics.  Backward:
+    mvs_vitdec_head_bn_bwd (d_z as fp32 and packed-split in one pass), the window weight gradient, the window data gradient.  The conv
+    bias sits in front of a batch-statistics BatchNorm: it enters the running mean only and its gradient is returned as exact zeros."""
+
+    @staticmethod
+    def forward(ctx, x, x_packed, bn, layer, NV, H, W, last, w, b, gamma, beta):
+        name = packing.VITDEC_HEAD[layer]
+        if not bn.training:
+            raise NotImplementedError("vitdec_forward_train: %s's BatchNorm is in eval mode while the module trains; frozen-BatchNorm "
+                                      "gradients are not built" % name)
+        x0 = ops._f32c(x.detach())
+        if layer == 0 and x0.shape[0] == 1:
+            raise ValueError("Expected more than 1 value per channel when training, got input size [1, 256, 1, 1] (proj's BatchNorm)")
+        g, bt = _vec32(gamma), _vec32(beta)
+        xp = x_packed if x_packed is not None else ops.vitdec_pack(x0)
+        wp = packing.pack_vitdec_head_train({name + ".0.weight": w}, transposed=False)[name]["w"]
+        z = ops.vitdec_head_conv(xp, wp, layer, NV, H, W)
+        rm, rv, momentum = _bn_train_step(bn, "CrossVITDecoder")
+        y, yp, stats = ops.vitdec_head_bn_fwd(z, g, bt, bn.eps, _vec32(b) if rm is not None else None, rm, rv, momentum,
+                                              want_packed=True, planar=(NV, 2 * H, 2 * W) if last else None)
+        ctx.save_for_backward(x0, z, stats, w, g, bt)
+        ctx.layer, ctx.map, ctx.b_like = layer, (NV, H, W), (b.shape, b.dtype)
+        if yp is None:
+            return y, None
+        ctx.mark_non_differentiable(yp)
+        return y, yp
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, d_y, _):
+        x0, z, stats, w, g, bt = ctx.saved_tensors
+        name = packing.VITDEC_HEAD[ctx.layer]
+        d_z, d_zp, d_g, d_b = ops.vitdec_head_bn_bwd(ops._f32c(d_y), z, stats, g, bt)
+        d_w = ops.vitdec_head_wgrad(d_z, x0, ctx.layer, *ctx.map)
+        d_x = None
+        if ctx.needs_input_grad[0]:
+            wt = packing.pack_vitdec_head_train({name + ".0.weight": w}, forward=False)[name]["wT"]
+            d_x = ops.vitdec_head_dgrad(d_zp, wt, ctx.layer, *ctx.map)
+        return d_x, None, None, None, None, None, None, None, d_w, torch.zeros(ctx.b_like[0], dtype=ctx.b_like[1], device=d_z.device), d_g, d_b
+
+
+def vitdec_head_train(module, tokens, NV, h, w):
+    """The head of the CrossVITDecoder in train mode on the library's kernels: tokens fp32 [NV h w, 768], token-major -> fp32
+    [NV, 64, 4 h, 4 w]; one ``VitdecHeadLayerTrain`` node per layer, the map token-major from the blocks to the last BatchNorm pass."""
+    for name in packing.VITDEC_HEAD:
+        if not getattr(module, name)[1].training:                   # before any running statistic moves
+            raise NotImplementedError("vitdec_forward_train: %s's BatchNorm is in eval mode while the module trains; frozen-BatchNorm "
+                                      "gradients are not built" % name)
+    t, tp = tokens, None
+    for layer, (seq, H, W) in enumerate(((module.proj, h, w), (module.upsampler0, h, w), (module.upsampler1, 2 * h, 2 * w))):
+        conv, bn = seq[0], seq[1]
+        t, tp = VitdecHeadLayerTrain.apply(t, tp, bn, layer, NV, H, W, layer == 2, conv.weight, conv.bias, bn.weight, bn.bias)
+    return t
 
 
 _FP32_TRAIN_WARNED = False

@@ -196,8 +196,14 @@ class TrainableCrossVITDecoder(CrossVITDecoder):
     """CrossVITDecoder with autograd: the same constructor, state-dict keys and configuration refusals.  In
     eval() mode its forward is the inference path; in train() mode it is ``training.vitdec_forward_train``: the five blocks and the AAS
     steps forward and backward on the library's kernels, weights packed on the device from the live parameters at every call, the head
-    (proj, upsampler0, upsampler1) on its own PyTorch layers with batch-statistics BatchNorm.  The ViT features get no gradient (the
-    backbone is frozen): an input that requires grad raises."""
+    (proj, upsampler0, upsampler1) on its own PyTorch layers with batch-statistics BatchNorm or, with ``native_head=True``, on the
+    library's kernels as well (token-major through the head, no atomics, the same bits from run to run; a head
+    BatchNorm in eval mode raises, as does a single value per channel).  The ViT features get no gradient (the backbone is frozen): an
+    input that requires grad raises."""
+
+    def __init__(self, args, native_head=False):
+        super().__init__(args)
+        self.native_head = bool(native_head)
 
     def forward(self, x, Fmats=None, vit_shape=None):
         if not self.training:
@@ -208,12 +214,15 @@ class TrainableCrossVITDecoder(CrossVITDecoder):
         return vitdec_forward_train(self, x, vit_shape)                     # checks the shapes itself
 
 
-def patch_vit_decoder(model: nn.Module, trainable: bool = False) -> nn.Module:
+def patch_vit_decoder(model: nn.Module, trainable: bool = False, native_head: bool = False) -> nn.Module:
     """Swap ``model.decoder_vit`` (the reference's CrossVITDecoder) for the native module: parameters and buffers carried over by
     ``load_state_dict(strict=True)``, device and train / eval mode preserved.  What the old module's blocks do (post_norm, pre_norm_query)
     and its no_combine_norm flag are read from the old module, because the state dict does not show them.  Everything else is left as
     it is.  Returns ``model``: ``model = patch_vit_decoder(patch_fmt(patch_fpn(patch_model(model))))``.  trainable=True installs
-    ``TrainableCrossVITDecoder`` instead of the inference form."""
+    ``TrainableCrossVITDecoder`` instead of the inference form; native_head=True (with trainable=True) makes its train-mode head run on the
+    library's kernels."""
+    if native_head and not trainable:
+        raise ValueError("patch_vit_decoder: native_head=True selects the train-mode head of TrainableCrossVITDecoder; pass trainable=True")
     old = model.decoder_vit
     blocks = list(getattr(old, "self_attn_blocks", [])) + list(getattr(old, "cross_attn_blocks", []))
     sd = old.state_dict()
@@ -232,7 +241,7 @@ def patch_vit_decoder(model: nn.Module, trainable: bool = False) -> nn.Module:
                self_cross_types=getattr(old, "self_cross_types", None))
     args = {"dino_cfg": dict(dino, decoder_cfg=cfg, cross_interval_layers=len(getattr(old, "cross_attn_blocks", []))),
             "out_ch": sd["upsampler1.0.weight"].shape[1], "vit_ch": sd["proj.0.weight"].shape[1]}
-    new = (TrainableCrossVITDecoder if trainable else CrossVITDecoder)(args)
+    new = TrainableCrossVITDecoder(args, native_head=native_head) if trainable else CrossVITDecoder(args)
     new.load_state_dict(sd, strict=True)
     ref = next(old.parameters())
     model.decoder_vit = new.to(ref.device).train(old.training)

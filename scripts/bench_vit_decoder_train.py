@@ -3,7 +3,7 @@
 needs the MI355X.
 
     python scripts/bench_vit_decoder_train.py [--cases 512x640x4,1024x1280x2] [--views 5] [--reps 30] [--out profiles/vit_decoder_train_bench.json]
-                                              [--no-profile]
+                                              [--no-profile] [--head-out profiles/vit_decoder_head_train_bench.json] [--head-only]
 
 Cases are HxWxB, images of the shipped multi-scale training list: rescale 0.4375 and patch 14 give 16 x 20 tokens at 512 x 640 and 32 x 40
 at 1024 x 1280.  Inputs are random fp32 tokens [B, V, n, 768].  One process, shapes warmed, legs alternated rep by rep, device events
@@ -18,6 +18,13 @@ for the native leg), whether two native steps give the same bits (output and all
 torch.matmul (dy^T x, fp32) on the four (N, K) shapes at the case's token count.  The per-kernel times are torch's profiler's, taken in
 this process on one step: a guide to where the time goes, not a substitute for a kernel trace in a run of its own.  Reads nothing
 outside the repository.
+
+--head-out adds the native-head comparison and writes its own record: two modules with the same weights,
+  torch_head     TrainableCrossVITDecoder(native_head=False): the parent's path, the head on PyTorch layers - the baseline
+  native_head    TrainableCrossVITDecoder(native_head=True): the head on csrc/vitdec_head_train_kernels.hip
+alternated rep by rep: step time and allocator peak; the head alone, forward + backward, on fixed tokens (nn.Sequential against
+training.vitdec_head_train); the new launches (vh_*) of one step by torch's profiler; and for both heads whether the head alone and
+the whole step give the same bits twice.  --head-only skips everything else.
 """
 import argparse
 import json
@@ -31,7 +38,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-OURS = ("vd_", "fmt_partial_reduce_kernel")
+OURS = ("vd_", "vh_", "fmt_partial_reduce_kernel")
 WGRAD_SHAPES = ((768, 768), (1536, 768), (3072, 768), (768, 3072))
 RESCALE, PATCH = 0.4375, 14
 
@@ -64,9 +71,99 @@ def profile_step(fn):
         total = sum(c[0] for c in by.values())
         ours = sum(c[0] for k, c in by.items() if any(o in k for o in OURS))
         top = dict(sorted(by.items(), key=lambda kv: -kv[1][1])[:24])
+        top.update({k: v for k, v in by.items() if "vh_" in k})       # every launch of the head's training unit, however small
         return {"kernels": total, "ours": ours, "by_kernel_count_us": top}
     except Exception as exc:                                                      # a report, never a reason to lose the timings
         return {"error": repr(exc)}
+
+
+def spread(times):
+    return {k: {"median_ms": statistics.median(v), "min_ms": min(v), "max_ms": max(v)} for k, v in times.items()}
+
+
+def head_case(mods, x, shape, cot, reps, no_profile):
+    """The native-head comparison of one case; mods = {"torch_head": module, "native_head": module} with the same weights."""
+    from mvsformerplusplus_amd import training
+    B, V, h, w, _ = shape
+
+    def clear():
+        for m in mods.values():
+            for p in m.parameters():
+                p.grad = None
+
+    def step(m):
+        return lambda: m(x, vit_shape=shape).backward(cot)
+
+    legs = {k: step(m) for k, m in mods.items()}
+    peak = {}
+    for k, fn in legs.items():
+        fn(); clear(); fn(); clear()
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        fn()
+        torch.cuda.synchronize()
+        peak[k] = (torch.cuda.max_memory_allocated() - base) / 2 ** 20
+        clear()
+    times = {k: [] for k in legs}
+    for _ in range(reps):
+        for k, fn in legs.items():
+            times[k] += timed(fn, 1)
+            clear()
+    # the head alone on fixed tokens, forward + backward
+    tokens = torch.randn(B * V * h * w, 768, generator=torch.Generator().manual_seed(h * w)).to(cot.device)
+
+    def head_torch(m=mods["torch_head"]):
+        t = tokens.clone().requires_grad_(True)
+        o = m.upsampler1(m.upsampler0(m.proj(t.reshape(B * V, h, w, 768).permute(0, 3, 1, 2))))
+        o.backward(cot)
+        return o, t
+
+    def head_native(m=mods["native_head"]):
+        t = tokens.clone().requires_grad_(True)
+        o = training.vitdec_head_train(m, t, B * V, h, w)
+        o.backward(cot)
+        return o, t
+
+    heads = {"torch_head": head_torch, "native_head": head_native}
+    for fn in heads.values():
+        fn(); clear(); fn(); clear()
+    torch.cuda.synchronize()
+    htimes = {k: [] for k in heads}
+    for _ in range(reps):
+        for k, fn in heads.items():
+            htimes[k] += timed(fn, 1)
+            clear()
+    # the same bits twice?  the head alone (output, token gradient, its 9 parameter gradients) and the whole step (output, 93 gradients)
+    identity = {}
+    for k, m in mods.items():
+        runs = []
+        for _ in range(2):
+            o, t = heads[k]()
+            runs.append([o.detach().clone(), t.grad.clone()] + [p.grad.clone() for seq in (m.proj, m.upsampler0, m.upsampler1) for p in seq.parameters()])
+            clear()
+        same = [bool(torch.equal(p, q)) for p, q in zip(*runs)]
+        steps = []
+        for _ in range(2):
+            o = m(x, vit_shape=shape)
+            o.backward(cot)
+            steps.append([o.detach().clone()] + [p.grad.clone() for p in m.parameters()])
+            clear()
+        whole = [bool(torch.equal(p, q)) for p, q in zip(*steps)]
+        identity[k] = {"head_alone_output": same[0], "head_alone_token_gradient": same[1], "head_alone_parameter_gradients": sum(same[2:]),
+                       "head_alone_parameter_gradients_of": len(same) - 2, "step_output": whole[0], "step_gradients": sum(whole[1:]),
+                       "step_gradients_of": len(whole) - 1}
+    prof = None
+    if not no_profile:
+        prof = {k: profile_step(fn) for k, fn in legs.items()}
+        by = prof["native_head"].get("by_kernel_count_us", {})
+        prof["new_launches_count_us"] = {k: v for k, v in by.items() if "vh_" in k}
+        clear()
+    st, hd = spread(times), spread(htimes)
+    base = st["torch_head"]
+    return {"tokens": [h, w], "step": st, "peak_MiB": peak, "head_alone_fwd_bwd": hd,
+            "native_step_within_baseline_spread": st["native_head"]["median_ms"] <= base["median_ms"] + (base["max_ms"] - base["min_ms"]),
+            "bit_identity": identity, "profile": prof}
 
 
 def main():
@@ -76,6 +173,8 @@ def main():
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--out", default=None)
     ap.add_argument("--no-profile", action="store_true", help="skip torch's profiler (kernel counts and per-kernel times)")
+    ap.add_argument("--head-out", default=None, help="also compare the native head with the PyTorch head and write that record here")
+    ap.add_argument("--head-only", action="store_true", help="with --head-out: skip the native / torch_fp32 legs and the wgrad comparison")
     a = ap.parse_args()
     cases = [tuple(int(v) for v in s.split("x")) for s in a.cases.split(",")]
     V = a.views
@@ -94,12 +193,24 @@ def main():
           for k, v in mod.state_dict().items()}
     leaves = [v for v in sd.values() if isinstance(v, torch.nn.Parameter)]
     result = {"device": torch.cuda.get_device_name(0), "reps": a.reps, "views": V, "cases": {}}
+    head_result = {"device": torch.cuda.get_device_name(0), "reps": a.reps, "views": V, "cases": {}}
+    if a.head_out:
+        native_mod = TrainableCrossVITDecoder(cfg, native_head=True)
+        native_mod.load_state_dict(mod.state_dict(), strict=True)
+        native_mod = native_mod.train().to(dev)
     for H, W, B in cases:
         h, w = int(H * RESCALE) // PATCH, int(W * RESCALE) // PATCH
         n, shape = h * w, [B, V, h, w, 768]
         g = torch.Generator().manual_seed(H + W)
         x = [torch.randn(B, V, n, 768, generator=g).to(dev) for _ in range(3)]
         cot = torch.randn(B * V, 64, 4 * h, 4 * w, generator=g).to(dev)
+        if a.head_out:
+            hr = head_case({"torch_head": mod, "native_head": native_mod}, x, shape, cot, a.reps, a.no_profile)
+            head_result["cases"]["%dx%d B=%d" % (H, W, B)] = hr
+            print("%dx%d B=%d V=%d head: step %s; head alone %s; peak MiB %s" % (H, W, B, V, hr["step"], hr["head_alone_fwd_bwd"], hr["peak_MiB"]),
+                  flush=True)
+            if a.head_only:
+                continue
 
         def native():
             mod(x, vit_shape=shape).backward(cot)
@@ -174,6 +285,13 @@ def main():
         print("%dx%d B=%d V=%d (%d x %d tokens): native %.3f ms, torch fp32 autograd %.3f ms per step; peak %.0f vs %.0f MiB; wgrad %s"
               % (H, W, B, V, h, w, med["native"], med["torch_fp32"], peak["native"], peak["torch_fp32"],
                  {k: (round(v["native_ms"], 3), round(v["matmul_ms"], 3)) for k, v in wg.items()}), flush=True)
+    if a.head_out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.head_out)), exist_ok=True)
+        with open(a.head_out, "w") as f:
+            json.dump(head_result, f, indent=1)
+        if a.head_only:
+            print(json.dumps(head_result))
+            return
     line = json.dumps(result)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
