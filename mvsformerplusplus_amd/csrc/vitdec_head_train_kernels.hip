@@ -10,16 +10,13 @@
 // its backward reads the planar cotangent.
 //
 // Kernels:
-//   1. vh_gemm_kernel<NREP>: vd_gemm_kernel's tile, staging and three-term products (2 x 2 waves, 32 NREP tokens x 128 channels, K in
-//      chunks of 64 through LDS, the next chunk's loads in flight during the MFMAs) with an fp32 epilogue that honours the output row
-//      mapping and no bias, and a two-level sum: every 64-k chunk is added up on its own and the chunk sums into the total, both
-//      ascending, so the roundings of a chain of up to K = 6912 happen at the size of a chunk sum.  Row operand through a 3x3 window (proj forward; proj's data gradient on the flipped, channel-transposed
-//      taps), through the 2x2 window of one parity class (upsampler forward, blockIdx.z = class) or through the 4x4 stride-2 window of
-//      the FINE map (upsampler data gradient: coarse token (y, x) reads fine (2 y - 1 + ky, 2 x - 1 + kx)).
-//   2. vh_wgrad_kernel<MODE>: vd_wgrad_kernel's 128 x 128 tile of dw over token slabs (transpose and split while staging, 32 tokens per
-//      chunk, partial tiles added in slab order by fmt_partial_reduce_kernel) with a per-tap row mapping on one operand.  MODE 0 (proj):
-//      dw[co][tap * 768 + c] = sum_m dz[m][co] x[shift_tap(m)][c]; a K tile lies inside one tap.  MODE 1 (upsamplers): dw[tap * Cout + co]
-//      [ci] = sum_m dz[fine_tap(m)][co] x[m][ci]; the tap belongs to the staged channel (a wave stages 64 consecutive channels: one tap).
+//   1. vh_gemm_kernel<NREP>: the token GEMM of token_gemm.h with the two-level sum (every 64-k chunk is added up on its own and the
+//      chunk sums into the total, both ascending, so the roundings of a chain of up to K = 6912 happen at the size of a chunk sum),
+//      Rows through a 3x3 window (proj forward; proj's data gradient on the flipped, channel-transposed taps), through the 2x2 window
+//      of one parity class (upsampler forward, blockIdx.z = class) or through the 4x4 stride-2 window of the FINE map (upsampler data
+//      gradient: coarse token (y, x) reads fine (2 y - 1 + ky, 2 x - 1 + kx)), and a Sink that stores fp32 at the output row, no bias.
+//   2. vh_wgrad_kernel<MODE>: the token weight gradient of token_wgrad.h with a window map on one operand and no bias partial.
+//      MODE 0 (proj, TW_CONV3) shifts x; MODE 1 (upsamplers, TW_FINE4) reads dz through the fine window.
 //   3. vh_bn_reduce_kernel / vh_bn_finalize_kernel / vh_bn_apply_kernel: batch-statistics BatchNorm + SiLU over [M, C] rows on
 //      64-row x 64-channel tiles.  Column sums ([sum z | sum z^2], or [sum du | sum du xhat] in the backward) are accumulated in fp64 per
 //      thread over the rows it walks, added over a workgroup's 16 row groups in group order, and the per-workgroup partials in a fixed
@@ -32,17 +29,12 @@
 // positions outside the map contribute zero from a branch, never from an out-of-range load; a window never crosses into a neighbouring
 // row or view.
 #include "mvs_common.h"
-#include "partial_reduce.h"
 #include "split_format.h"
+#include "token_gemm.h"
+#include "token_wgrad.h"
 #include "vit_split.h"
 
 namespace mvs {
-
-constexpr int VH_KC = 64;                     // contraction per LDS chunk: two MFMA k-steps
-constexpr int VH_TN = 128;                    // output channels per workgroup
-constexpr int VH_CIN[3] = {768, 256, 128}, VH_COUT[3] = {256, 128, 64};
-
-enum { VH_A_CONV3 = 0, VH_A_DECONV = 1, VH_A_FINE4 = 2 };
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // window GEMM
@@ -57,183 +49,33 @@ struct VhGemmArgs {
     size_t w_class;
 };
 
-struct VhRow {
-    int view, yx;                // view = -1: past the end; yx = (y << 16) | x
-};
-
-__device__ __forceinline__ VhRow vh_row(const VhGemmArgs& p, int row) {
-    VhRow r{-1, 0};
-    if (row >= p.M) return r;
-    const int hw = p.H * p.W, view = row / hw, pix = row - view * hw, y = pix / p.W;
-    r.view = view;
-    r.yx = (y << 16) | (pix - y * p.W);
-    return r;
-}
-
-// index (in 16-byte units) of the fragment piece (k-step, hi|lo, lane group gl) of the row that tap `tap` of class `cls` reads for the
-// staged row r, or -1 = zero
-__device__ __forceinline__ long long vh_a_piece(const VhGemmArgs& p, const VhRow& r, int tap, int cls, int steps, int kstep, int hl, int gl) {
-    if (r.view < 0) return -1;
-    const int y = r.yx >> 16, x = r.yx & 0xffff;
-    int sy, sx, SH = p.H, SW = p.W;
-    if (p.a_mode == VH_A_CONV3) {
-        sy = y + tap / 3 - 1;
-        sx = x + tap - (tap / 3) * 3 - 1;
-    } else if (p.a_mode == VH_A_DECONV) {
-        // output (2 y + py, 2 x + px) reads input (y + py - ay, x + px - ax) with ky = 1 - py + 2 ay
-        sy = y + (cls >> 1) - (tap >> 1);
-        sx = x + (cls & 1) - (tap & 1);
-    } else {
-        sy = 2 * y - 1 + (tap >> 2);
-        sx = 2 * x - 1 + (tap & 3);
-        SH = 2 * p.H;
-        SW = 2 * p.W;
+// Sink: fp32 rows of the output map, no bias
+struct VhSink {
+    const VhGemmArgs& p;
+    typedef size_t Row;
+    __device__ __forceinline__ Row row(int row, int cls) const {
+        if (p.a_mode != TG_A_DECONV) return (size_t)row;
+        int view, opix;
+        tg_deconv_out(row, p.H, p.W, cls, view, opix);
+        return (size_t)view * 4 * p.H * p.W + opix;
     }
-    if (sy < 0 || sy >= SH || sx < 0 || sx >= SW) return -1;
-    const int srow = (r.view * SH + sy) * SW + sx;
-    return ((((long long)(srow >> 4) * steps + kstep) * 2 + hl) * 64) + gl * 16 + (srow & 15);
-}
+    __device__ __forceinline__ void store4(const Row& orow, int ch, const f32x4& a) const {
+        *reinterpret_cast<float4*>(p.out + orow * p.N + ch) = make_float4(a[0], a[1], a[2], a[3]);
+    }
+};
 
 template <int NREP>
 __global__ __launch_bounds__(256) void vh_gemm_kernel(VhGemmArgs p) {
-    constexpr int NTB = 2 * NREP, TM = 16 * NTB;
-    HIP_DYNAMIC_SHARED(float4, lds4)
-    bf16x8* la = reinterpret_cast<bf16x8*>(lds4);                 // [NTB token blocks][2 steps][hi|lo][64 lanes]
-    bf16x8* lw = la + NTB * 256;                                  // [2 steps][8 channel blocks][hi|lo][64 lanes]
-    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, g = lane >> 4;
-    const int wm = wave & 1, wn = wave >> 1;
-    const int m0 = (int)blockIdx.x * TM, nb0 = (int)blockIdx.y * (VH_TN / 16), cls = (int)blockIdx.z;
-    const bf16x8* wsrc = p.w + (size_t)cls * p.w_class;
-    const int nmb = p.Npad >> 4, steps = p.C >> 5;
-    // staging: piece (token block i, tid) of the row operand; pieces tid + 256 i (i < 8) of the weight chunk
-    const int ps = tid >> 7, phl = (tid >> 6) & 1, pgl = lane >> 4;
-    bf16x8 ra[NTB], rw[8];
-    bf16x8 zero;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) zero[e] = (__bf16)0.0f;
-
-    VhRow rows[NTB];
-#pragma unroll
-    for (int i = 0; i < NTB; ++i) rows[i] = vh_row(p, m0 + 16 * i + li);
-
-    auto fetch = [&](int k0) {
-        const int tap = k0 / p.C, kstep = ((k0 - tap * p.C) >> 5) + ps;            // the chunk's tap is workgroup-uniform
-#pragma unroll
-        for (int i = 0; i < NTB; ++i) {
-            const long long idx = vh_a_piece(p, rows[i], tap, cls, steps, kstep, phl, pgl);
-            ra[i] = idx >= 0 ? p.a[idx] : zero;
-        }
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int j = tid + 256 * i, s = j >> 10, rest = j & 1023;
-            rw[i] = wsrc[((size_t)((k0 >> 5) + s) * nmb + nb0) * 128 + rest];
-        }
-    };
-
-    f32x4 acc[4][NREP];
-#pragma unroll
-    for (int mb = 0; mb < 4; ++mb)
-#pragma unroll
-        for (int nb = 0; nb < NREP; ++nb) acc[mb][nb] = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
-
-    fetch(0);
-#pragma unroll 1
-    for (int k0 = 0; k0 < p.K; k0 += VH_KC) {
-        __syncthreads();                                           // the previous chunk has been read
-#pragma unroll
-        for (int i = 0; i < NTB; ++i) la[i * 256 + tid] = ra[i];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) lw[tid + 256 * i] = rw[i];
-        __syncthreads();
-        if (k0 + VH_KC < p.K) fetch(k0 + VH_KC);                   // in flight during the MFMAs below
-        // two-level sum: the chunk's 64 k go into a fresh accumulator, k ascending, and the chunk sums into the total, chunks ascending.
-        // The chunks are the same for every tile, so an element still does not depend on the tile that computes it; the rounding of
-        // a long chain (K up to 6912) then happens at the magnitude of a chunk sum, not of the running total.
-        f32x4 seg[4][NREP];
-#pragma unroll
-        for (int mb = 0; mb < 4; ++mb)
-#pragma unroll
-            for (int nb = 0; nb < NREP; ++nb) seg[mb][nb] = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-            bf16x8 ah[4], al[4], bh[NREP], bl[NREP];
-#pragma unroll
-            for (int mb = 0; mb < 4; ++mb) {
-                ah[mb] = lw[((s * 8 + wn * 4 + mb) * 2 + 0) * 64 + lane];
-                al[mb] = lw[((s * 8 + wn * 4 + mb) * 2 + 1) * 64 + lane];
-            }
-#pragma unroll
-            for (int nb = 0; nb < NREP; ++nb) {
-                bh[nb] = la[(((wm * NREP + nb) * 2 + s) * 2 + 0) * 64 + lane];
-                bl[nb] = la[(((wm * NREP + nb) * 2 + s) * 2 + 1) * 64 + lane];
-            }
-#pragma unroll
-            for (int mb = 0; mb < 4; ++mb)
-#pragma unroll
-                for (int nb = 0; nb < NREP; ++nb) seg[mb][nb] = mfma3_bf16(ah[mb], al[mb], bh[nb], bl[nb], seg[mb][nb]);
-        }
-#pragma unroll
-        for (int mb = 0; mb < 4; ++mb)
-#pragma unroll
-            for (int nb = 0; nb < NREP; ++nb) acc[mb][nb] += seg[mb][nb];
-    }
-
-    // ---- epilogue: lane (li, g) holds channels 16 mb + 4 g .. + 3 of token li of block nb ----
-#pragma unroll
-    for (int nb = 0; nb < NREP; ++nb) {
-        const int row = m0 + (wm * NREP + nb) * 16 + li;
-        if (row >= p.M) continue;
-        size_t orow = (size_t)row;
-        if (p.a_mode == VH_A_DECONV) {
-            const int hw = p.H * p.W, view = row / hw, pix = row - view * hw, y = pix / p.W, x = pix - y * p.W;
-            orow = (size_t)view * 4 * hw + (size_t)(2 * y + (cls >> 1)) * 2 * p.W + 2 * x + (cls & 1);
-        }
-#pragma unroll
-        for (int mb = 0; mb < 4; ++mb) {
-            const int ch = (nb0 + wn * 4 + mb) * 16 + 4 * g;
-            if (ch >= p.N) continue;
-            *reinterpret_cast<float4*>(p.out + orow * p.N + ch) = make_float4(acc[mb][nb][0], acc[mb][nb][1], acc[mb][nb][2], acc[mb][nb][3]);
-        }
-    }
+    token_gemm<NREP, true>(p, TgRows<VhGemmArgs, false, true>{p}, VhSink{p});
 }
 
 static int vh_launch_gemm(const VhGemmArgs& p, int classes, hipStream_t st) {
-    const int nrep = p.M <= 32 ? 1 : (p.M <= 2048 ? 2 : 4);
-    const size_t lds = (size_t)(2 * nrep * 256 + 2048) * 16;
-    const dim3 grid(ceil_div(p.M, 32 * nrep), p.Npad / VH_TN, classes);
-    // more than 48 KB of dynamic LDS needs the attribute, once per kernel and device
-    static bool raised[3][64] = {};
-    int dev = 0;
-    hipGetDevice(&dev);
-#define MVS_VH_GO(NR, SLOT) \
-    if (nrep == NR) { \
-        if (lds > 48 * 1024 && !(dev >= 0 && dev < 64 && raised[SLOT][dev])) { \
-            hipFuncSetAttribute(reinterpret_cast<const void*>(&vh_gemm_kernel<NR>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-            if (dev >= 0 && dev < 64) raised[SLOT][dev] = true; \
-        } \
-        hipLaunchKernelGGL((vh_gemm_kernel<NR>), grid, dim3(256), lds, st, p); \
-    }
-    MVS_VH_GO(1, 0) MVS_VH_GO(2, 1) MVS_VH_GO(4, 2)
-#undef MVS_VH_GO
-    return check_launch("vh_gemm_kernel");
+    return token_gemm_launch("vh_gemm_kernel", vh_gemm_kernel<1>, vh_gemm_kernel<2>, vh_gemm_kernel<4>, p, classes, st);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // window weight gradient
 // ---------------------------------------------------------------------------------------------------------------------------------
-constexpr int VHW_T = 128;                    // dw tile: 128 x 128
-constexpr int VHW_TOK = 32;                   // tokens per staged chunk = one MFMA k-step
-constexpr int VHW_TARGET = 512;               // workgroups wanted in a launch: two per compute unit
-
-// vd_wgrad_kernel's slab rule: slabs of whole 32-token chunks, enough for VHW_TARGET workgroups over the tiles, never more than chunks
-static void vhw_slabs(long long M, int N, int K, int& slabs, int& chunks_per_slab) {
-    const int chunks = (int)ceil_div(M, VHW_TOK), tiles = (N / VHW_T) * (K / VHW_T);
-    int want = (int)ceil_div(VHW_TARGET, tiles);
-    if (want > chunks) want = chunks;
-    chunks_per_slab = (int)ceil_div(chunks, want);
-    slabs = (int)ceil_div(chunks, chunks_per_slab);
-}
-
 struct VhWgradArgs {
     const float* dz;             // MODE 0: [M, N]; MODE 1: the fine map's rows [4 M, Cy]
     const float* x;              // MODE 0: [M, Cx]; MODE 1: [M, K]
@@ -242,104 +84,10 @@ struct VhWgradArgs {
     int tok_per_slab;
 };
 
+// MODE 0: proj (3x3 shift on x); MODE 1: upsamplers (4x4 stride-2 fine window on dz)
 template <int MODE>
 __global__ __launch_bounds__(256) void vh_wgrad_kernel(VhWgradArgs p) {
-    HIP_DYNAMIC_SHARED(float4, lds4)
-    bf16x8* ly = reinterpret_cast<bf16x8*>(lds4);                 // [8 channel blocks][hi|lo][64 lanes]: dz
-    bf16x8* lx = ly + 8 * 128;                                    // the same for x
-    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, g = lane >> 4;
-    const int wn = wave >> 1, wk = wave & 1;
-    const int slab = (int)blockIdx.x, k0 = (int)blockIdx.y * VHW_T, n0 = (int)blockIdx.z * VHW_T;
-    const int t0 = slab * p.tok_per_slab, t1 = t0 + p.tok_per_slab < p.M ? t0 + p.tok_per_slab : p.M;
-    const int c = tid & 127, o0 = (tid >> 7) * 2;                 // staged channel of the tile, first of this thread's two token octets
-    // the tap of the mapped operand: of the K tile (MODE 0, workgroup-uniform) or of the staged dz column (MODE 1, wave-uniform)
-    const int tap = MODE == 0 ? k0 / p.Cx : (n0 + c) / p.Cy;
-    const float* ysrc = MODE == 0 ? p.dz + n0 + c : p.dz + (n0 + c - tap * p.Cy);
-    const float* xsrc = MODE == 0 ? p.x + (k0 - tap * p.Cx) + c : p.x + k0 + c;
-    const int ystride = MODE == 0 ? p.N : p.Cy, xstride = MODE == 0 ? p.Cx : p.K;
-    const int hw = p.H * p.W;
-    float ry[16], rx[16];
-
-    auto fetch = [&](int t) {
-        const int first = t + 8 * o0;                              // 16 consecutive tokens: (view, y, x) once, then counted on
-        int view = first / hw, pix = first - view * hw, y = pix / p.W, x = pix - y * p.W;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-            const int tok = first + e;
-            long long yr = tok, xr = tok;
-            if (MODE == 0) {
-                const int dy = tap / 3 - 1, dx = tap - (tap / 3) * 3 - 1, sy = y + dy, sx = x + dx;
-                xr = (sy < 0 || sy >= p.H || sx < 0 || sx >= p.W) ? -1 : (long long)tok + dy * p.W + dx;
-            } else {
-                const int fy = 2 * y - 1 + (tap >> 2), fx = 2 * x - 1 + (tap & 3);
-                yr = (fy < 0 || fy >= 2 * p.H || fx < 0 || fx >= 2 * p.W) ? -1 : ((long long)view * 2 * p.H + fy) * 2 * p.W + fx;
-            }
-            const bool ok = tok < t1;
-            ry[e] = ok && yr >= 0 ? ysrc[(size_t)yr * ystride] : 0.0f;
-            rx[e] = ok && xr >= 0 ? xsrc[(size_t)xr * xstride] : 0.0f;
-            if (++x == p.W) {
-                x = 0;
-                if (++y == p.H) {
-                    y = 0;
-                    ++view;
-                }
-            }
-        }
-    };
-
-    f32x4 acc[4][4];
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = 0; b < 4; ++b) acc[a][b] = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
-
-    fetch(t0);
-#pragma unroll 1
-    for (int t = t0; t < t1; t += VHW_TOK) {
-        __syncthreads();                                           // the previous chunk has been read
-#pragma unroll
-        for (int o = 0; o < 2; ++o) {
-            float vy[8], vx[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                vy[e] = ry[8 * o + e];
-                vx[e] = rx[8 * o + e];
-            }
-            bf16x8 hi, lo;
-            const int piece = (c >> 4) * 128 + (o0 + o) * 16 + (c & 15);
-            split8(vy, hi, lo);
-            ly[piece] = hi;
-            ly[piece + 64] = lo;
-            split8(vx, hi, lo);
-            lx[piece] = hi;
-            lx[piece + 64] = lo;
-        }
-        __syncthreads();
-        if (t + VHW_TOK < t1) fetch(t + VHW_TOK);                  // in flight during the MFMAs below
-        bf16x8 ah[4], al[4], bh[4], bl[4];
-#pragma unroll
-        for (int a = 0; a < 4; ++a) {
-            ah[a] = ly[(wn * 4 + a) * 128 + lane];
-            al[a] = ly[(wn * 4 + a) * 128 + 64 + lane];
-            bh[a] = lx[(wk * 4 + a) * 128 + lane];
-            bl[a] = lx[(wk * 4 + a) * 128 + 64 + lane];
-        }
-#pragma unroll
-        for (int a = 0; a < 4; ++a)
-#pragma unroll
-            for (int b = 0; b < 4; ++b) acc[a][b] = mfma3_bf16(ah[a], al[a], bh[b], bl[b], acc[a][b]);
-    }
-
-    // ---- partial tile: lane (li, g) holds dw[n = 16 a + 4 g + r][k = 16 b + li] ----
-    float* dst = p.part + (size_t)slab * p.N * p.K;
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            float* row = dst + (size_t)(n0 + wn * 64 + 16 * a + 4 * g + r) * p.K + k0 + wk * 64 + li;
-#pragma unroll
-            for (int b = 0; b < 4; ++b) row[16 * b] = acc[a][b][r];
-        }
+    token_wgrad<false>(TwMap<MODE == 0 ? TW_CONV3 : TW_FINE4>{p.dz, p.x, p.Cy, p.Cx, p.H, p.W, 0}, p.part, nullptr, p.M, p.N, p.K, p.tok_per_slab);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -616,9 +364,10 @@ extern "C" int mvs_vitdec_head_conv_fwd(const void* x_packed, const void* w_pack
     p.a = reinterpret_cast<const bf16x8*>(x_packed);
     p.w = reinterpret_cast<const bf16x8*>(w_packed);
     p.out = z;
-    p.M = NV * H * W; p.K = (layer == 0 ? 9 : 4) * VH_CIN[layer]; p.N = VH_COUT[layer]; p.Npad = (p.N + VH_TN - 1) / VH_TN * VH_TN;
-    p.a_mode = layer == 0 ? VH_A_CONV3 : VH_A_DECONV;
-    p.C = VH_CIN[layer]; p.H = H; p.W = W;
+    const VitdecHeadLayer& L = VITDEC_HEAD[layer];
+    p.M = NV * H * W; p.K = L.taps * L.cin; p.N = L.cout; p.Npad = (p.N + TG_TN - 1) / TG_TN * TG_TN;
+    p.a_mode = layer == 0 ? TG_A_CONV3 : TG_A_DECONV;
+    p.C = L.cin; p.H = H; p.W = W;
     p.w_class = (size_t)(p.K / 32) * (p.Npad / 16) * 128;
     return vh_launch_gemm(p, layer == 0 ? 1 : 4, (hipStream_t)stream);
 }
@@ -634,25 +383,26 @@ extern "C" int mvs_vitdec_head_dgrad(const void* dz_packed, const void* wt_packe
     p.a = reinterpret_cast<const bf16x8*>(dz_packed);
     p.w = reinterpret_cast<const bf16x8*>(wt_packed);
     p.out = d_x;
-    p.M = NV * H * W; p.K = (layer == 0 ? 9 : 16) * VH_COUT[layer]; p.N = VH_CIN[layer]; p.Npad = p.N;
-    p.a_mode = layer == 0 ? VH_A_CONV3 : VH_A_FINE4;
-    p.C = VH_COUT[layer]; p.H = H; p.W = W;
+    const VitdecHeadLayer& L = VITDEC_HEAD[layer];
+    p.M = NV * H * W; p.K = L.dgrad_taps * L.cout; p.N = L.cin; p.Npad = p.N;
+    p.a_mode = layer == 0 ? TG_A_CONV3 : TG_A_FINE4;
+    p.C = L.cout; p.H = H; p.W = W;
     return vh_launch_gemm(p, 1, (hipStream_t)stream);
 }
 
 // ---- window weight gradients ----------------------------------------------------------------------------------------------------------
 // dw as the kernel's [N, K]: layer 0 [256, 9 x 768], layers 1 / 2 [16 Cout, Cin]
 static void vh_wgrad_dims(int layer, int& N, int& K) {
-    N = layer == 0 ? VH_COUT[0] : 16 * VH_COUT[layer];
-    K = layer == 0 ? 9 * VH_CIN[0] : VH_CIN[layer];
+    const VitdecHeadLayer& L = VITDEC_HEAD[layer];
+    N = layer == 0 ? L.cout : L.dgrad_taps * L.cout;
+    K = layer == 0 ? L.taps * L.cin : L.cin;
 }
 
 extern "C" size_t mvs_vitdec_head_wgrad_workspace_bytes(int layer, int NV, int H, int W) {
     if (layer < 0 || layer > 2 || !vh_map(layer, NV, H, W)) return 0;
-    int N, K, slabs, per;
+    int N, K;
     vh_wgrad_dims(layer, N, K);
-    vhw_slabs((long long)NV * H * W, N, K, slabs, per);
-    return (size_t)slabs * N * K * sizeof(float);
+    return token_wgrad_workspace_bytes((long long)NV * H * W, N, K, false);
 }
 
 extern "C" int mvs_vitdec_head_wgrad(const float* d_z, const float* x, float* dw, void* workspace, size_t workspace_bytes, int layer, int NV, int H,
@@ -667,20 +417,16 @@ extern "C" int mvs_vitdec_head_wgrad(const float* d_z, const float* x, float* dw
         set_error("mvs_vitdec_head_wgrad: workspace smaller than mvs_vitdec_head_wgrad_workspace_bytes");
         return MVS_ERR_ARG;
     }
-    int N, K, slabs, per;
+    int N, K;
     vh_wgrad_dims(layer, N, K);
     const int M = NV * H * W;
-    vhw_slabs(M, N, K, slabs, per);
     hipStream_t st = (hipStream_t)stream;
-    // one slab: its "partial" is the result, written in place with no second launch
-    VhWgradArgs p{d_z, x, slabs == 1 ? dw : reinterpret_cast<float*>(workspace), M, N, K, VH_COUT[layer], VH_CIN[layer], H, W, per * VHW_TOK};
-    const dim3 grid(slabs, K / VHW_T, N / VHW_T);
-    const size_t lds = 2 * 8 * 128 * sizeof(bf16x8);
-    if (layer == 0) hipLaunchKernelGGL((vh_wgrad_kernel<0>), grid, dim3(256), lds, st, p);
-    else hipLaunchKernelGGL((vh_wgrad_kernel<1>), grid, dim3(256), lds, st, p);
-    rc = check_launch("vh_wgrad_kernel");
-    if (rc != MVS_OK || slabs == 1) return rc;
-    return ft_reduce_partials(p.part, dw, slabs, N * K, st);
+    auto launch = [&](dim3 grid, float* part, float*, int tok_per_slab) {
+        VhWgradArgs p{d_z, x, part, M, N, K, VITDEC_HEAD[layer].cout, VITDEC_HEAD[layer].cin, H, W, tok_per_slab};
+        if (layer == 0) hipLaunchKernelGGL((vh_wgrad_kernel<0>), grid, dim3(256), TW_LDS, st, p);
+        else hipLaunchKernelGGL((vh_wgrad_kernel<1>), grid, dim3(256), TW_LDS, st, p);
+    };
+    return token_wgrad_run("vh_wgrad_kernel", launch, dw, nullptr, workspace, M, N, K, st);
 }
 
 // ---- BatchNorm + SiLU -----------------------------------------------------------------------------------------------------------------

@@ -16,12 +16,12 @@
 //   1. vd_rows_kernel: one wave per token row.  [prev_value * prev +] input row (fp32 / bf16 / fp16, any batch / view / row stride)
 //      [-> LayerNorm eps 1e-6 (norm_layers)] -> x fp32 and / or packed-split(x) and / or packed-split(LayerNorm eps ln_eps (x)).
 //      prev_value is read from device memory.
-//   2. vd_gemm_kernel<NREP>: Y = epilogue(A W^T).  Workgroup = 2 x 2 waves, wave = 16 NREP tokens x 64 channels, tile 32 NREP x 128,
-//      K in chunks of 64 through LDS (both operands), the next chunk's global loads in flight during the MFMAs.  The row operand is
-//      read in place (linear layers), through a 3x3 window (proj: implicit GEMM, K = 9 x 768) or through the 2x2 window of one
-//      parity class of ConvTranspose2d(4, stride 2, padding 1) (upsampler0 / 1: K = 4 x Cin, blockIdx.z = class).  Epilogues: fp32
-//      (elu + 1 on the leading columns), residual + gamma * (. + bias), packed-split act(. + bias), planar fp32 silu(. + bias), and for
-//      the ViT backbone QKV (the attention operands of vit_split.h) and EMBED (+ bias + position row).
+//   2. vd_gemm_kernel<NREP>: Y = epilogue(A W^T), the token GEMM of token_gemm.h (tile, staging, prefetch, MFMA loop, launcher) with one
+//      running sum.  Rows: the row operand is read in place (linear layers), through a 3x3 window (proj: implicit GEMM, K = 9 x 768) or
+//      through the 2x2 window of one parity class of ConvTranspose2d(4, stride 2, padding 1) (upsampler0 / 1: K = 4 x Cin, blockIdx.z =
+//      class).  Sink, chosen at run time: fp32 (elu + 1 on the leading columns), residual + gamma * (. + bias), packed-split
+//      act(. + bias), planar fp32 silu(. + bias), and for the ViT backbone QKV (the attention operands of
+//      vit_split.h) and EMBED (+ bias + position row).
 //   3. vd_kv_partial_kernel + vd_kv_reduce_kernel: KV_h = sum_s k_s (x) v_s and ksum_h = sum_s k_s from exact fp32 products
 //      (v_mfma_f32_16x16x4_f32); per-slab partials added in slab order by the second launch: no atomics, bit-identical run to run.
 //   4. vd_apply_kernel: a = (q . KV_h) / (q . ksum_h + 1e-6) on the exact fp32 MFMA, KV_h held in registers -> packed-split.
@@ -30,17 +30,15 @@
 // Rows past the end and window positions outside the map read as zero from a branch, never from an out-of-range load.
 #include "mvs_common.h"
 #include "split_format.h"
+#include "token_gemm.h"
 #include "vit_split.h"
 
 namespace mvs {
 
 constexpr int VD_C = 768, VD_HEADS = 12, VD_HD = 64, VD_HID = 3072;
-constexpr int VD_KC = 64;                     // contraction per LDS chunk: two MFMA k-steps
-constexpr int VD_TN = 128;                    // output channels per workgroup
 constexpr int VD_KVPART = VD_HD * VD_HD + VD_HD;      // floats of one (view, head) summary: KV_h [d][m] | ksum_h [d]
 constexpr int VD_MAX_SLABS = 16;
 
-enum { VD_A_ROWS = 0, VD_A_CONV3 = 1, VD_A_DECONV = 2 };
 enum { VD_EPI_F32 = 0, VD_EPI_RESID = 1, VD_EPI_SPLIT = 2, VD_EPI_PLANAR = 3, VD_EPI_QKV = 4, VD_EPI_EMBED = 5 };
 enum { VD_ACT_NONE = 0, VD_ACT_GELU = 1, VD_ACT_SILU = 2 };
 
@@ -171,189 +169,75 @@ struct VdGemmArgs {
     float q_scale;               // QKV: the leading 768 columns (q) are multiplied by it
 };
 
-// The staged rows of one work-item, decomposed ONCE per workgroup: `base` = first source row of the row's view (windows) or the row itself
-// (ROWS), -1 = past the end; `yx` = (y << 16) | x of the row's pixel (windows).
-struct VdRow {
-    int base, yx;
+// Sink: + bias, then the run-time epilogue (epi / act / elu_cols)
+struct VdSink {
+    const VdGemmArgs& p;
+    struct Row {
+        int row, orow, view, opix, opixn;                              // view * opixn + opix = the output map's row `orow` (DECONV) or `row`
+    };
+    __device__ __forceinline__ Row row(int row, int cls) const {
+        Row o{row, row, 0, 0, 1};
+        if (p.a_mode == TG_A_DECONV) {
+            tg_deconv_out(row, p.H, p.W, cls, o.view, o.opix);
+            o.opixn = 4 * p.H * p.W;
+            o.orow = o.view * o.opixn + o.opix;
+        } else if (p.epi >= VD_EPI_PLANAR) {                          // rows per view: PLANAR H W pixels, QKV W rows, EMBED H patches
+            o.opixn = p.epi == VD_EPI_PLANAR ? p.H * p.W : (p.epi == VD_EPI_QKV ? p.W : p.H);
+            o.view = row / o.opixn;
+            o.opix = row - o.view * o.opixn;
+        }
+        return o;
+    }
+    __device__ __forceinline__ void store4(const Row& o, int ch, const f32x4& a) const {
+        const int row = o.row;
+        float v[4] = {a[0], a[1], a[2], a[3]};
+        if (p.bias) {
+            const float4 bb = *reinterpret_cast<const float4*>(p.bias + ch);
+            v[0] += bb.x; v[1] += bb.y; v[2] += bb.z; v[3] += bb.w;
+        }
+        if (p.epi == VD_EPI_F32) {
+            if (ch < p.elu_cols) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) v[k] = elu1(v[k]);
+            }
+            *reinterpret_cast<float4*>(reinterpret_cast<float*>(p.out) + (size_t)row * p.N + ch) = make_float4(v[0], v[1], v[2], v[3]);
+        } else if (p.epi == VD_EPI_RESID) {
+            const float4 gg = *reinterpret_cast<const float4*>(p.gamma + ch);
+            const float4 rr = *reinterpret_cast<const float4*>(p.res + (size_t)row * p.N + ch);
+            *reinterpret_cast<float4*>(reinterpret_cast<float*>(p.out) + (size_t)row * p.N + ch) =
+                make_float4(fmaf(gg.x, v[0], rr.x), fmaf(gg.y, v[1], rr.y), fmaf(gg.z, v[2], rr.z), fmaf(gg.w, v[3], rr.w));
+        } else if (p.epi == VD_EPI_QKV) {
+            // q (x q_scale) | k -> packed-split rows of 64 channels per (view, head); v -> transposed (vit_split.h)
+            const int vw = o.view, t = o.opix, part = ch / VD_C, c = ch - part * VD_C;
+            bf16x8* sec = reinterpret_cast<bf16x8*>(p.out) + vit_qkv_section(vw, c >> 6, part, p.W);
+            if (part == 0) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) v[k] *= p.q_scale;
+            }
+            if (part < 2) vd_store_split4(sec, VD_HD / 32, t, c & 63, v);
+            else vit_store_vt4(sec, t, c & 63, v);
+        } else if (p.epi == VD_EPI_EMBED) {
+            const int vw = o.view, patch = o.opix;
+            const float4 pp = *reinterpret_cast<const float4*>(p.res + (size_t)(patch + 1) * p.N + ch);
+            *reinterpret_cast<float4*>(reinterpret_cast<float*>(p.out) + ((size_t)vw * p.W + patch + 1) * p.N + ch) =
+                make_float4(v[0] + pp.x, v[1] + pp.y, v[2] + pp.z, v[3] + pp.w);
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) v[k] = vd_act(v[k], p.act);
+            if (p.epi == VD_EPI_SPLIT) {
+                vd_store_split4(reinterpret_cast<bf16x8*>(p.out), p.N >> 5, o.orow, ch, v);
+            } else {
+                float* dst = reinterpret_cast<float*>(p.out) + ((size_t)o.view * p.N + ch) * o.opixn + o.opix;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) dst[(size_t)k * o.opixn] = v[k];
+            }
+        }
+    }
 };
-
-__device__ __forceinline__ VdRow vd_row(const VdGemmArgs& p, int row) {
-    VdRow r{-1, 0};
-    if (row >= p.M) return r;
-    if (p.a_mode == VD_A_ROWS) {
-        r.base = row;
-    } else {
-        const int hw = p.H * p.W, view = row / hw, pix = row - view * hw, y = pix / p.W;
-        r.base = view * hw;
-        r.yx = (y << 16) | (pix - y * p.W);
-    }
-    return r;
-}
-
-// index (in 16-byte units) of the fragment piece (k-step `kstep` of the source row, hi|lo, lane group gl) of a staged row whose window
-// offset is (dy, dx), or -1 = zero
-__device__ __forceinline__ long long vd_a_piece(const VdGemmArgs& p, const VdRow& r, int dy, int dx, int steps, int kstep, int hl, int gl) {
-    if (r.base < 0) return -1;
-    int srow = r.base;
-    if (p.a_mode != VD_A_ROWS) {
-        const int sy = (r.yx >> 16) + dy, sx = (r.yx & 0xffff) + dx;
-        if (sy < 0 || sy >= p.H || sx < 0 || sx >= p.W) return -1;
-        srow += sy * p.W + sx;
-    }
-    return ((((long long)(srow >> 4) * steps + kstep) * 2 + hl) * 64) + gl * 16 + (srow & 15);
-}
 
 template <int NREP>
 __global__ __launch_bounds__(256) void vd_gemm_kernel(VdGemmArgs p) {
-    constexpr int NTB = 2 * NREP, TM = 16 * NTB;
-    HIP_DYNAMIC_SHARED(float4, lds4)
-    bf16x8* la = reinterpret_cast<bf16x8*>(lds4);                 // [NTB token blocks][2 steps][hi|lo][64 lanes]
-    bf16x8* lw = la + NTB * 256;                                  // [2 steps][8 channel blocks][hi|lo][64 lanes]
-    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, g = lane >> 4;
-    const int wm = wave & 1, wn = wave >> 1;
-    const int m0 = (int)blockIdx.x * TM, nb0 = (int)blockIdx.y * (VD_TN / 16), cls = (int)blockIdx.z;
-    const bf16x8* wsrc = p.w + (size_t)cls * p.w_class;
-    const int nmb = p.Npad >> 4;
-    // staging: piece (token block i, tid) of the row operand; pieces tid + 256 i (i < 8) of the weight chunk
-    const int ps = tid >> 7, phl = (tid >> 6) & 1, pgl = lane >> 4;
-    bf16x8 ra[NTB], rw[8];
-    bf16x8 zero;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) zero[e] = (__bf16)0.0f;
-
-    VdRow rows[NTB];
-#pragma unroll
-    for (int i = 0; i < NTB; ++i) rows[i] = vd_row(p, m0 + 16 * i + li);
-
-    auto fetch = [&](int k0) {
-        // the chunk's tap and window offset are workgroup-uniform: output (2 y + py, 2 x + px) of a transposed convolution reads input
-        // (y + py - ay, x + px - ax) with ky = 1 - py + 2 ay
-        int steps = p.K >> 5, kstep = (k0 >> 5) + ps, dy = 0, dx = 0;
-        if (p.a_mode != VD_A_ROWS) {
-            const int tap = k0 / p.C;
-            steps = p.C >> 5;
-            kstep = ((k0 - tap * p.C) >> 5) + ps;
-            if (p.a_mode == VD_A_CONV3) {
-                dy = tap / 3 - 1;
-                dx = tap - (tap / 3) * 3 - 1;
-            } else {
-                dy = (cls >> 1) - (tap >> 1);
-                dx = (cls & 1) - (tap & 1);
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < NTB; ++i) {
-            const long long idx = vd_a_piece(p, rows[i], dy, dx, steps, kstep, phl, pgl);
-            ra[i] = idx >= 0 ? p.a[idx] : zero;
-        }
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int j = tid + 256 * i, s = j >> 10, rest = j & 1023;
-            rw[i] = wsrc[((size_t)((k0 >> 5) + s) * nmb + nb0) * 128 + rest];
-        }
-    };
-
-    f32x4 acc[4][NREP];
-#pragma unroll
-    for (int mb = 0; mb < 4; ++mb)
-#pragma unroll
-        for (int nb = 0; nb < NREP; ++nb) acc[mb][nb] = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
-
-    fetch(0);
-#pragma unroll 1
-    for (int k0 = 0; k0 < p.K; k0 += VD_KC) {
-        __syncthreads();                                           // the previous chunk has been read
-#pragma unroll
-        for (int i = 0; i < NTB; ++i) la[i * 256 + tid] = ra[i];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) lw[tid + 256 * i] = rw[i];
-        __syncthreads();
-        if (k0 + VD_KC < p.K) fetch(k0 + VD_KC);                   // in flight during the MFMAs below
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-            bf16x8 ah[4], al[4], bh[NREP], bl[NREP];
-#pragma unroll
-            for (int mb = 0; mb < 4; ++mb) {
-                ah[mb] = lw[((s * 8 + wn * 4 + mb) * 2 + 0) * 64 + lane];
-                al[mb] = lw[((s * 8 + wn * 4 + mb) * 2 + 1) * 64 + lane];
-            }
-#pragma unroll
-            for (int nb = 0; nb < NREP; ++nb) {
-                bh[nb] = la[(((wm * NREP + nb) * 2 + s) * 2 + 0) * 64 + lane];
-                bl[nb] = la[(((wm * NREP + nb) * 2 + s) * 2 + 1) * 64 + lane];
-            }
-#pragma unroll
-            for (int mb = 0; mb < 4; ++mb)
-#pragma unroll
-                for (int nb = 0; nb < NREP; ++nb) acc[mb][nb] = mfma3_bf16(ah[mb], al[mb], bh[nb], bl[nb], acc[mb][nb]);
-        }
-    }
-
-    // ---- epilogue: lane (li, g) holds channels 16 mb + 4 g .. + 3 of token li of block nb ----
-#pragma unroll
-    for (int nb = 0; nb < NREP; ++nb) {
-        const int row = m0 + (wm * NREP + nb) * 16 + li;
-        if (row >= p.M) continue;
-        int orow = row, view = 0, opix = 0, opixn = 1;
-        if (p.a_mode == VD_A_DECONV) {
-            const int hw = p.H * p.W, pix = row - (row / hw) * hw, y = pix / p.W, x = pix - y * p.W;
-            view = row / hw;
-            opixn = 4 * hw;
-            opix = (2 * y + (cls >> 1)) * 2 * p.W + 2 * x + (cls & 1);
-            orow = view * opixn + opix;
-        } else if (p.epi == VD_EPI_PLANAR) {
-            opixn = p.H * p.W;
-            view = row / opixn;
-            opix = row - view * opixn;
-        }
-#pragma unroll
-        for (int mb = 0; mb < 4; ++mb) {
-            const int ch = (nb0 + wn * 4 + mb) * 16 + 4 * g;
-            if (ch >= p.N) continue;
-            float v[4] = {acc[mb][nb][0], acc[mb][nb][1], acc[mb][nb][2], acc[mb][nb][3]};
-            if (p.bias) {
-                const float4 bb = *reinterpret_cast<const float4*>(p.bias + ch);
-                v[0] += bb.x; v[1] += bb.y; v[2] += bb.z; v[3] += bb.w;
-            }
-            if (p.epi == VD_EPI_F32) {
-                if (ch < p.elu_cols) {
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) v[k] = elu1(v[k]);
-                }
-                *reinterpret_cast<float4*>(reinterpret_cast<float*>(p.out) + (size_t)row * p.N + ch) = make_float4(v[0], v[1], v[2], v[3]);
-            } else if (p.epi == VD_EPI_RESID) {
-                const float4 gg = *reinterpret_cast<const float4*>(p.gamma + ch);
-                const float4 rr = *reinterpret_cast<const float4*>(p.res + (size_t)row * p.N + ch);
-                *reinterpret_cast<float4*>(reinterpret_cast<float*>(p.out) + (size_t)row * p.N + ch) =
-                    make_float4(fmaf(gg.x, v[0], rr.x), fmaf(gg.y, v[1], rr.y), fmaf(gg.z, v[2], rr.z), fmaf(gg.w, v[3], rr.w));
-            } else if (p.epi == VD_EPI_QKV) {
-                // q (x q_scale) | k -> packed-split rows of 64 channels per (view, head); v -> transposed (vit_split.h)
-                const int vw = row / p.W, t = row - vw * p.W, part = ch / VD_C, c = ch - part * VD_C;
-                bf16x8* sec = reinterpret_cast<bf16x8*>(p.out) + vit_qkv_section(vw, c >> 6, part, p.W);
-                if (part == 0) {
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) v[k] *= p.q_scale;
-                }
-                if (part < 2) vd_store_split4(sec, VD_HD / 32, t, c & 63, v);
-                else vit_store_vt4(sec, t, c & 63, v);
-            } else if (p.epi == VD_EPI_EMBED) {
-                const int vw = row / p.H, patch = row - vw * p.H;
-                const float4 pp = *reinterpret_cast<const float4*>(p.res + (size_t)(patch + 1) * p.N + ch);
-                *reinterpret_cast<float4*>(reinterpret_cast<float*>(p.out) + ((size_t)vw * p.W + patch + 1) * p.N + ch) =
-                    make_float4(v[0] + pp.x, v[1] + pp.y, v[2] + pp.z, v[3] + pp.w);
-            } else {
-#pragma unroll
-                for (int k = 0; k < 4; ++k) v[k] = vd_act(v[k], p.act);
-                if (p.epi == VD_EPI_SPLIT) {
-                    vd_store_split4(reinterpret_cast<bf16x8*>(p.out), p.N >> 5, orow, ch, v);
-                } else {
-                    float* o = reinterpret_cast<float*>(p.out) + ((size_t)view * p.N + ch) * opixn + opix;
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) o[(size_t)k * opixn] = v[k];
-                }
-            }
-        }
-    }
+    token_gemm<NREP, false>(p, TgRows<VdGemmArgs, true, false>{p}, VdSink{p});
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -496,24 +380,7 @@ static int vd_slabs(int n) {
 }
 
 static int vd_launch_gemm(const VdGemmArgs& p, int classes, hipStream_t st) {
-    const int nrep = p.M <= 32 ? 1 : (p.M <= 2048 ? 2 : 4);
-    const size_t lds = (size_t)(2 * nrep * 256 + 2048) * 16;
-    const dim3 grid(ceil_div(p.M, 32 * nrep), p.Npad / VD_TN, classes);
-    // more than 48 KB of dynamic LDS needs the attribute, once per kernel and device
-    static bool raised[3][64] = {};
-    int dev = 0;
-    hipGetDevice(&dev);
-#define MVS_VD_GO(NR, SLOT) \
-    if (nrep == NR) { \
-        if (lds > 48 * 1024 && !(dev >= 0 && dev < 64 && raised[SLOT][dev])) { \
-            hipFuncSetAttribute(reinterpret_cast<const void*>(&vd_gemm_kernel<NR>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-            if (dev >= 0 && dev < 64) raised[SLOT][dev] = true; \
-        } \
-        hipLaunchKernelGGL((vd_gemm_kernel<NR>), grid, dim3(256), lds, st, p); \
-    }
-    MVS_VD_GO(1, 0) MVS_VD_GO(2, 1) MVS_VD_GO(4, 2)
-#undef MVS_VD_GO
-    return check_launch("vd_gemm_kernel");
+    return token_gemm_launch("vd_gemm_kernel", vd_gemm_kernel<1>, vd_gemm_kernel<2>, vd_gemm_kernel<4>, p, classes, st);
 }
 
 }  // namespace mvs
@@ -593,7 +460,7 @@ extern "C" int mvs_vitdec_linear_fwd(const void* a_packed, const void* w_packed,
     p.w = reinterpret_cast<const bf16x8*>(w_packed);
     p.bias = bias; p.gamma = gamma; p.res = residual; p.out = y;
     p.M = M; p.K = K; p.N = N; p.Npad = N;
-    p.a_mode = VD_A_ROWS; p.epi = epilogue; p.act = epilogue == VD_EPI_SPLIT ? VD_ACT_GELU : VD_ACT_NONE; p.elu_cols = elu_cols;
+    p.a_mode = TG_A_ROWS; p.epi = epilogue; p.act = epilogue == VD_EPI_SPLIT ? VD_ACT_GELU : VD_ACT_NONE; p.elu_cols = elu_cols;
     p.C = K; p.H = 1; p.W = 1;
     return vd_launch_gemm(p, 1, (hipStream_t)stream);
 }
@@ -612,14 +479,14 @@ extern "C" int mvs_vitdec_conv_fwd(const void* x_packed, const void* w_packed, c
         set_error("mvs_vitdec_conv_fwd: bad arguments");
         return MVS_ERR_ARG;
     }
-    static const int cin[3] = {VD_C, 256, 128}, cout[3] = {256, 128, 64}, taps[3] = {9, 4, 4};
+    const VitdecHeadLayer& L = VITDEC_HEAD[layer];
     VdGemmArgs p{};
     p.a = reinterpret_cast<const bf16x8*>(x_packed);
     p.w = reinterpret_cast<const bf16x8*>(w_packed);
     p.bias = bias; p.out = y;
-    p.M = NV * H * W; p.K = taps[layer] * cin[layer]; p.N = cout[layer]; p.Npad = (cout[layer] + VD_TN - 1) / VD_TN * VD_TN;
-    p.a_mode = layer == 0 ? VD_A_CONV3 : VD_A_DECONV; p.epi = planar ? VD_EPI_PLANAR : VD_EPI_SPLIT; p.act = VD_ACT_SILU;
-    p.C = cin[layer]; p.H = H; p.W = W;
+    p.M = NV * H * W; p.K = L.taps * L.cin; p.N = L.cout; p.Npad = (L.cout + TG_TN - 1) / TG_TN * TG_TN;
+    p.a_mode = layer == 0 ? TG_A_CONV3 : TG_A_DECONV; p.epi = planar ? VD_EPI_PLANAR : VD_EPI_SPLIT; p.act = VD_ACT_SILU;
+    p.C = L.cin; p.H = H; p.W = W;
     p.w_class = (size_t)(p.K / 32) * (p.Npad / 16) * 128;
     return vd_launch_gemm(p, layer == 0 ? 1 : 4, (hipStream_t)stream);
 }
@@ -702,7 +569,7 @@ extern "C" int mvs_vit_embed_fwd(const void* a_packed, const void* w_packed, con
     p.w = reinterpret_cast<const bf16x8*>(w_packed);
     p.bias = bias; p.res = pos; p.out = x;
     p.M = NV * n; p.K = VT_KPAD; p.N = VD_C; p.Npad = VD_C;
-    p.a_mode = VD_A_ROWS; p.epi = VD_EPI_EMBED; p.act = VD_ACT_NONE;
+    p.a_mode = TG_A_ROWS; p.epi = VD_EPI_EMBED; p.act = VD_ACT_NONE;
     p.C = VT_KPAD; p.H = n; p.W = npad;
     int rc = vd_launch_gemm(p, 1, (hipStream_t)stream);
     if (rc != MVS_OK) return rc;
@@ -729,7 +596,7 @@ extern "C" int mvs_vit_qkv_fwd(const void* xn_packed, const void* w_packed, cons
     p.w = reinterpret_cast<const bf16x8*>(w_packed);
     p.bias = bias; p.out = qkv;
     p.M = NV * npad; p.K = VD_C; p.N = 3 * VD_C; p.Npad = 3 * VD_C;
-    p.a_mode = VD_A_ROWS; p.epi = VD_EPI_QKV; p.act = VD_ACT_NONE;
+    p.a_mode = TG_A_ROWS; p.epi = VD_EPI_QKV; p.act = VD_ACT_NONE;
     p.C = VD_C; p.H = 1; p.W = npad;
     p.q_scale = q_scale;
     return vd_launch_gemm(p, 1, (hipStream_t)stream);
